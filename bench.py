@@ -7,7 +7,13 @@ exponentiation  out[i] = x[i]^e[i] mod p  over N = 1,000,000 elements, p = RFC 3
 resident in HBM (device arrays of the C ABI), through ``vmn_garray_exp_array`` — the call the
 reference makes as ``PGroupElementArray.exp(PRingElementArray)`` (PoSBasicTW.java:1032).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed steps, times K steps and prints the headline line (value = elements / time of
+the timed steps, ms_per_step = that time / K).  --dump-outputs DIR writes what the last timed step computed (a fixed,
+seeded sample of out[], see dump_outputs) as DIR/*.npy.  --full adds everything else the line used to carry: the
+modexp_by_shape sweep, the mix / decryption legs with their CPU baselines, and the GMP cpu_baseline of the headline
+with its bit-exact check of the GPU output.
 
 N > 1: one process per GPU (torch.distributed / RCCL), every rank holds its own shard of N_per_gpu
 elements (weak scaling, no data-path collective: element-wise op), barrier + synchronize on both
@@ -22,7 +28,7 @@ The JSON line carries
                  the launch stream; peak = 39.3 TMAC/s = 256 CUs x 4 SIMDs x 16 lanes/clk x 2.4 GHz,
                  the issue rate of v_mad_u64_u32 measured by tools/valu_rate.hip
                  (profiles/valu_rate_r01.txt) = the FP64-vector FMA rate of MI355X_MICROARCH.md.
-  cpu_baseline : the GMP oracle (mpz_powm, OpenMP over all host cores) on a bounded sample of the
+  cpu_baseline : (--full) the GMP oracle (mpz_powm, OpenMP over all host cores) on a bounded sample of the
                  same inputs; the GPU output for that sample is compared bit for bit.
 """
 from __future__ import annotations
@@ -111,6 +117,29 @@ def make_inputs(n: int, seed: int, nbytes: int):
     e[:, 0] &= 0x7F
     x[:, -1] |= 1                     # no zero base
     return x.tobytes(), e.tobytes()
+
+
+DUMP_SAMPLE = 16384                   # elements written by --dump-outputs (x 256 float32 values = 16 MiB at 2048 bits)
+
+
+def dump_index(n: int):
+    """The elements --dump-outputs writes: all n when n <= DUMP_SAMPLE, else a fixed, seeded sample, ascending."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return np.arange(n)
+    return np.sort(np.random.Generator(np.random.PCG64(20260001)).choice(n, size=DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(dirname: str, out, rank: int) -> None:
+    """--dump-outputs: the last timed step's out[i] = x[i]^e[i] mod p, the array a caller of the path receives, as
+    DIR/modexp_out.npy (rank r > 0: modexp_out_rank<r>.npy).  The elements of dump_index(n); one row per element: its
+    big-endian bytes, each stored as a float32 (exact), so that two builds compare value for value."""
+    import numpy as np
+    n, width = out.size(), out.group.elem_bytes
+    rows = np.frombuffer(out.toBytes(), dtype=np.uint8).reshape(n, width)[dump_index(n)]
+    os.makedirs(dirname, exist_ok=True)
+    name = "modexp_out" if rank == 0 else f"modexp_out_rank{rank}"
+    np.save(os.path.join(dirname, name + ".npy"), rows.astype(np.float32))
 
 
 def load_sub(entry, name):
@@ -1346,7 +1375,14 @@ def main() -> None:
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = --elements / --mix-elements PER GPU (BASELINE configs[1] on every GPU), strong = in TOTAL "
                          "(north_star's 1M-ciphertext shuffle split over the GPUs); the mix legs always report both")
+    ap.add_argument("--dump-outputs", dest="dump_dir", default=None, metavar="DIR",
+                    help="write a fixed, seeded sample of the last timed step's output to DIR/*.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: modexp_by_shape, the mix / decryption legs and the CPU "
+                         "baselines (the options above that size or skip them apply only here)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python3 bench.py --gpus N` typed without a launcher starts its own ranks (as a child, before any GPU call)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1473,6 +1509,8 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     ctx.timing_enable(False)
     launches, kernel_ms = ctx.timing_get("modpow")
+    if args.dump_dir:
+        dump_outputs(args.dump_dir, out, rank)
 
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_device)
@@ -1700,53 +1738,55 @@ def main() -> None:
         """A leg that reports a one-shot figure starts from a group without cached tables."""
         return vmn.ModPGroup(ctx, p, q, g, nbytes=nbytes)
 
-    if args.n >= 10000 and not distributed and not args.no_shapes:
-        X.free()
-        E.free()
-        guarded("modexp_by_shape", leg_shapes)
-    if args.mix_n > 0:
-        guarded("mix_prove", leg_mix_prove)
-    if args.dec_n > 0 and not distributed:
-        guarded("decrypt_2048", leg_decrypt)
-    if args.mix_n >= 10000 and not distributed:
-        guarded("mix_prove_n10000", leg_small)
-        if "error" not in result.get("mix_prove", {"error": 1}) and "error" not in result.get("mix_prove_n10000", {"error": 1}) and args.mix_n > 10000:
-            guarded("operation_length", leg_fit)
-    if args.ccpos_n > 0:
-        guarded("mix_ccpos_3072", leg_ccpos_sharded if distributed else leg_ccpos)
-    if args.ec_n > 0:
-        guarded("mix_ec_p256", leg_ec_sharded if distributed else leg_ec)
-        if not distributed:
-            guarded("operation_length_p256", leg_fit_p256)
+    # --full: everything beyond the headline (each leg and baseline starts runs of its own); a plain run stops here
+    if args.full:
+        if args.n >= 10000 and not distributed and not args.no_shapes:
+            X.free()
+            E.free()
+            guarded("modexp_by_shape", leg_shapes)
+        if args.mix_n > 0:
+            guarded("mix_prove", leg_mix_prove)
+        if args.dec_n > 0 and not distributed:
+            guarded("decrypt_2048", leg_decrypt)
+        if args.mix_n >= 10000 and not distributed:
+            guarded("mix_prove_n10000", leg_small)
+            if "error" not in result.get("mix_prove", {"error": 1}) and "error" not in result.get("mix_prove_n10000", {"error": 1}) and args.mix_n > 10000:
+                guarded("operation_length", leg_fit)
+        if args.ccpos_n > 0:
+            guarded("mix_ccpos_3072", leg_ccpos_sharded if distributed else leg_ccpos)
+        if args.ec_n > 0:
+            guarded("mix_ec_p256", leg_ec_sharded if distributed else leg_ec)
+            if not distributed:
+                guarded("operation_length_p256", leg_fit_p256)
 
-    if rank == 0 and not args.no_cpu:
-        from oracle.cbind import Oracle
-        orc = Oracle(p, q, nbytes)
-        # host cores this job may use: the affinity mask, capped at the 16-core share of a one-GPU box
-        # (a launcher pins OMP_NUM_THREADS to 1 for its ranks: the oracle's thread count is set explicitly, not inherited)
-        cores = min(len(os.sched_getaffinity(0)), 16 * max(1, world)) if distributed else min(orc.threads, len(os.sched_getaffinity(0)), 16)
-        orc.set_threads(cores)
-        sample = args.cpu_sample or min(n, 6000 * cores)          # ~15 s of mpz_powm
-        t1 = time.perf_counter()
-        want = orc.exp_array_bytes(xb[: sample * nbytes], eb[: sample * nbytes], sample, nbytes)
-        cpu_s = time.perf_counter() - t1
-        got = out.copyOfRange(0, sample).toBytes() if sample < n else out.toBytes()
-        result["cpu_baseline"] = {"value": sample / cpu_s, "unit": "modexp/s", "cores": cores, "kind": "port",
-                                  "sample": f"first {sample} of the {n} elements of rank 0 (GMP mpz_powm, OpenMP static chunks)",
-                                  "bit_exact_vs_gpu": got == want}
-        if got != want:
-            result["parity_error"] = "GPU output differs from the GMP oracle on the sample"
-            result["value"] = None                         # a wrong result has no throughput
-        if "mix_prove" in result and "error" not in result["mix_prove"] and not distributed:
-            try:
-                result["mix_prove"]["cpu_baseline"] = cpu_mix_prove(p, q, g, 30000, cores)
-            except Exception as exc:                   # pragma: no cover
-                result["mix_prove"]["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if "decrypt_2048" in result and "error" not in result["decrypt_2048"]:
-            try:
-                result["decrypt_2048"]["cpu_baseline"] = cpu_decrypt(p, q, g, 20000, cores)
-            except Exception as exc:                   # pragma: no cover
-                result["decrypt_2048"]["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
+        if rank == 0 and not args.no_cpu:
+            from oracle.cbind import Oracle
+            orc = Oracle(p, q, nbytes)
+            # host cores this job may use: the affinity mask, capped at the 16-core share of a one-GPU box
+            # (a launcher pins OMP_NUM_THREADS to 1 for its ranks: the oracle's thread count is set explicitly, not inherited)
+            cores = min(len(os.sched_getaffinity(0)), 16 * max(1, world)) if distributed else min(orc.threads, len(os.sched_getaffinity(0)), 16)
+            orc.set_threads(cores)
+            sample = args.cpu_sample or min(n, 6000 * cores)          # ~15 s of mpz_powm
+            t1 = time.perf_counter()
+            want = orc.exp_array_bytes(xb[: sample * nbytes], eb[: sample * nbytes], sample, nbytes)
+            cpu_s = time.perf_counter() - t1
+            got = out.copyOfRange(0, sample).toBytes() if sample < n else out.toBytes()
+            result["cpu_baseline"] = {"value": sample / cpu_s, "unit": "modexp/s", "cores": cores, "kind": "port",
+                                      "sample": f"first {sample} of the {n} elements of rank 0 (GMP mpz_powm, OpenMP static chunks)",
+                                      "bit_exact_vs_gpu": got == want}
+            if got != want:
+                result["parity_error"] = "GPU output differs from the GMP oracle on the sample"
+                result["value"] = None                         # a wrong result has no throughput
+            if "mix_prove" in result and "error" not in result["mix_prove"] and not distributed:
+                try:
+                    result["mix_prove"]["cpu_baseline"] = cpu_mix_prove(p, q, g, 30000, cores)
+                except Exception as exc:                   # pragma: no cover
+                    result["mix_prove"]["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
+            if "decrypt_2048" in result and "error" not in result["decrypt_2048"]:
+                try:
+                    result["decrypt_2048"]["cpu_baseline"] = cpu_decrypt(p, q, g, 20000, cores)
+                except Exception as exc:                   # pragma: no cover
+                    result["decrypt_2048"]["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
     if rank == 0:
         print(json.dumps(result))
     if distributed:

@@ -52,7 +52,7 @@ def render(bench):
         f"| **decryption half** (row A6 / N3): one of 3 parties, threshold 2, 2048 bits | {dec['total_ms']:.0f} ms = **{dec['ciphertexts_per_s']:.3e} "
         f"ciphertexts/s**; CPU (GMP, {dec['cpu_baseline']['cores']} cores): {dec['cpu_baseline']['value']:.0f} | {fr(dec)} |",
     ]
-    text = (f"`python bench.py` on one MI355X (`{rel}`), every leg at its BASELINE configuration's size (10^6).  Round-4 rules: the set-up of "
+    text = (f"`python bench.py --full` on one MI355X (`{rel}`), every leg at its BASELINE configuration's size (10^6).  Round-4 rules: the set-up of "
             "the long-lived fixed-base tables is timed and counted (one-shot figures), every figure is the MEAN of its passes, every PoS pass "
             "runs on fresh generators, both roofline units are given (executed 28-bit multiply-adds; canonical SURVEY.md §8d MACs):\n\n"
             "| leg | result | roofline (bound: integer VALU, peak 39.3 T multiply-adds/s) |\n|---|---|---|\n" + "\n".join(rows))

@@ -3,7 +3,7 @@
 # usage (GPU box): bash tools/ec_quick.sh <tag>
 tag=${1:-ec_quick}
 mkdir -p gpurun_out
-timeout -k 10 400 python bench.py --steps 1 --warmup 0 --elements 2048 --mix-elements 0 --ec-elements 1000000 --ccpos-elements 0 \
+timeout -k 10 400 python bench.py --full --steps 1 --warmup 0 --elements 2048 --mix-elements 0 --ec-elements 1000000 --ccpos-elements 0 \
     --decrypt-elements 0 --no-e2e --skip-cpu --no-shapes > gpurun_out/$tag.json 2> gpurun_out/$tag.err || { tail -5 gpurun_out/$tag.err; exit 1; }
 python - "$tag" <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 # usage (GPU box): bash tools/small_n_quick.sh <tag>
 tag=${1:-small_n}
 mkdir -p gpurun_out
-timeout -k 10 400 python bench.py --steps 1 --warmup 0 --elements 2048 --mix-elements 10000 --ec-elements 10000 --ccpos-elements 0 \
+timeout -k 10 400 python bench.py --full --steps 1 --warmup 0 --elements 2048 --mix-elements 10000 --ec-elements 10000 --ccpos-elements 0 \
     --decrypt-elements 0 --no-e2e --skip-cpu --no-shapes > gpurun_out/$tag.json 2> gpurun_out/$tag.err || { tail -5 gpurun_out/$tag.err; exit 1; }
 python - "$tag" <<'PY'
 import json, sys

@@ -2,7 +2,7 @@
 # fan-in of the per-bucket product trees (VMN_TREE_FANIN): the mix + prove leg at 2048 bits and the P-256 width-3 leg
 cd "$GRAFT_REPO_ROOT"
 for f in ${FANINS:-8 12 16 24 32}; do
-  VMN_TREE_FANIN=$f python3 bench.py --steps 1 --warmup 0 --elements 2048 --no-e2e --ccpos-elements 0 --decrypt-elements 0 --skip-cpu \
+  VMN_TREE_FANIN=$f python3 bench.py --full --steps 1 --warmup 0 --elements 2048 --no-e2e --ccpos-elements 0 --decrypt-elements 0 --skip-cpu \
       > gpurun_out/fanin_$f.json 2> gpurun_out/fanin_$f.err || { echo "F=$f failed"; tail -3 gpurun_out/fanin_$f.err; exit 1; }
   python3 - "$f" <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 # 2048 bits: 17 GB per table), 20 (33 GB), 21 (61 GB) -- the PoS leg at N = 10^6.
 cd "$GRAFT_REPO_ROOT"
 for w in 19 20 21; do
-  VMN_FIXED_WINDOW_REUSE=$w VMN_FIXED_CACHE_BYTES=220000000000 python3 bench.py --steps 1 --warmup 0 --elements 2048 --no-e2e --ccpos-elements 0 --ec-elements 0 \
+  VMN_FIXED_WINDOW_REUSE=$w VMN_FIXED_CACHE_BYTES=220000000000 python3 bench.py --full --steps 1 --warmup 0 --elements 2048 --no-e2e --ccpos-elements 0 --ec-elements 0 \
       --decrypt-elements 0 --skip-cpu > gpurun_out/fixedw_$w.json 2> gpurun_out/fixedw_$w.err || { echo "w=$w failed"; tail -3 gpurun_out/fixedw_$w.err; continue; }
   python3 - "$w" <<'PY'
 import json, sys

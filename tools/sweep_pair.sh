@@ -6,7 +6,7 @@ out=gpurun_out/pair_sweep.txt
 : > $out
 for n in 2000 5000 10000 20000; do
   for pm in 0 20480; do
-    VMN_PAIR_MAX=$pm python3 bench.py --steps 1 --warmup 0 --elements 2048 --mix-elements $n --ccpos-elements 0 --ec-elements 0 \
+    VMN_PAIR_MAX=$pm python3 bench.py --full --steps 1 --warmup 0 --elements 2048 --mix-elements $n --ccpos-elements 0 --ec-elements 0 \
         --decrypt-elements 0 --skip-cpu --no-e2e 2> gpurun_out/pair_sweep.err |
       python3 -c "
 import json,sys

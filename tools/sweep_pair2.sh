@@ -6,7 +6,7 @@ out=gpurun_out/pair_sweep2.txt
 for n in ${SIZES:-24000 32768 50000 70000 100000}; do
   for mode in "0 32768" "1000000 1000000000" "0 1000000000"; do
     set -- $mode
-    VMN_PAIR_MAX=$1 VMN_COMBINED_MIN=$2 python3 bench.py --steps 1 --warmup 0 --elements 2048 --mix-elements $n --ccpos-elements 0 --ec-elements 0 \
+    VMN_PAIR_MAX=$1 VMN_COMBINED_MIN=$2 python3 bench.py --full --steps 1 --warmup 0 --elements 2048 --mix-elements $n --ccpos-elements 0 --ec-elements 0 \
         --decrypt-elements 0 --skip-cpu --no-e2e 2> gpurun_out/pair_sweep.err |
       python3 -c "
 import json,sys

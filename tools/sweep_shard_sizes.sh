@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"
 for g in 1 2 4 8; do
   n=$((1000000 / g))
-  python3 bench.py --steps 2 --warmup 1 --elements $n --mix-elements $n --ec-elements $n --ccpos-elements $n --decrypt-elements 0 --no-e2e --skip-cpu \
+  python3 bench.py --full --steps 2 --warmup 1 --elements $n --mix-elements $n --ec-elements $n --ccpos-elements $n --decrypt-elements 0 --no-e2e --skip-cpu \
       > gpurun_out/shard_$g.json 2> gpurun_out/shard_$g.err || { echo "G=$g failed"; tail -3 gpurun_out/shard_$g.err; exit 1; }
   python3 - "$g" "$n" <<'PY'
 import json, sys

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for wg in 2 4 8 16; do
-  VMN_BUCKET_AGG_WEIGHT=$wg python3 bench.py --steps 1 --warmup 0 --elements 2048 --mix-elements 0 --ccpos-elements 0 --ec-elements 1000000 --decrypt-elements 0 --skip-cpu --no-e2e 2>/dev/null | python3 -c "
+  VMN_BUCKET_AGG_WEIGHT=$wg python3 bench.py --full --steps 1 --warmup 0 --elements 2048 --mix-elements 0 --ccpos-elements 0 --ec-elements 1000000 --decrypt-elements 0 --skip-cpu --no-e2e 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); m=r['mix_ec_p256']
 k=m['kernel_ms_by_family']

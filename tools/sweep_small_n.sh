@@ -6,7 +6,7 @@ out=$1; shift
 for n in "$@"; do
   for w in 0 1000000000; do
     echo "== N=$n VMN_WIDE_MAX=$w" >> "$out"
-    VMN_WIDE_MAX=$w python3 -u bench.py --elements $n --mix-elements $n --ec-elements 0 --ccpos-elements ${CCPOS_N:-0} --skip-cpu --no-e2e --steps 3 --warmup 1 2>/dev/null \
+    VMN_WIDE_MAX=$w python3 -u bench.py --full --elements $n --mix-elements $n --ec-elements 0 --ccpos-elements ${CCPOS_N:-0} --skip-cpu --no-e2e --steps 3 --warmup 1 2>/dev/null \
       | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for sw in 1 0; do
 for c in ${WIDTHS:-11 12 13 14 15 16}; do
-  VMN_SIGNED_WINDOWS=$sw VMN_WINDOW_BITS=$c python3 bench.py --steps 1 --warmup 0 --elements 2048 --mix-elements 0 --ccpos-elements 0 --ec-elements ${1:-1000000} --decrypt-elements 0 --skip-cpu --no-e2e 2>/dev/null | python3 -c "
+  VMN_SIGNED_WINDOWS=$sw VMN_WINDOW_BITS=$c python3 bench.py --full --steps 1 --warmup 0 --elements 2048 --mix-elements 0 --ccpos-elements 0 --ec-elements ${1:-1000000} --decrypt-elements 0 --skip-cpu --no-e2e 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); m=r['mix_ec_p256']
 k=m['kernel_ms_by_family']

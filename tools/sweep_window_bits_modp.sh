@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for c in default ${WIDTHS:-13 14 15 16}; do
   if [ "$c" = default ]; then unset VMN_WINDOW_BITS; else export VMN_WINDOW_BITS=$c; fi
-  python3 bench.py --steps 1 --warmup 0 --elements 2048 --mix-elements ${1:-1000000} --ccpos-elements ${1:-1000000} --ec-elements 0 --decrypt-elements 0 --skip-cpu --no-e2e 2>/dev/null | python3 -c "
+  python3 bench.py --full --steps 1 --warmup 0 --elements 2048 --mix-elements ${1:-1000000} --ccpos-elements ${1:-1000000} --ec-elements 0 --decrypt-elements 0 --skip-cpu --no-e2e 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); m=r['mix_prove']; c3=r['mix_ccpos_3072']
 k=m['kernel_ms_by_family']; k3=c3['kernel_ms_by_family']
