@@ -106,14 +106,19 @@ size_t vmn_group_table_bytes(const vmn_group* grp);
  * size that holds it). */
 int vmn_modp_group_create(vmn_ctx* ctx, const uint8_t* p_be, const uint8_t* q_be, const uint8_t* g_be,
                           size_t nbytes, vmn_group** out);
-/* ECqPGroup over a named NIST prime curve: "P-256" and "P-384" -- the two north_star names, with the field primes compiled
- * into the kernels (csrc/ec_kernels.h FieldPrime) -- and, untuned, "P-224" (the curve the reference runs its own `check` on,
- * demo/mixnet/.checkbaseconf:59; square roots by Tonelli-Shanks, p = 1 mod 4) and "P-521" (benchmarks/bench_config:37).  Any
- * other name is VMN_ERR_UNSUPPORTED: the kernels assume a = -3 (dbl-2001-b), so the brainpool curves the reference also
- * offers (demo/mixnet/.conf:150-156) would need a general `a`, and P-192 is not instantiated.
+/* ECqPGroup over a named prime curve, any of the 26 names the reference offers (demo/mixnet/.conf:151-176; 19 distinct
+ * curves, all of cofactor 1): "P-256" and "P-384" -- the two north_star names, with the field primes compiled into the
+ * kernels (csrc/ec_kernels.h FieldPrime) -- "P-224" (the curve the reference runs its own `check` on,
+ * demo/mixnet/.checkbaseconf:59; square roots by Tonelli-Shanks, p = 1 mod 4), "P-521" (benchmarks/bench_config:37), "P-192";
+ * the aliases "secp192r1", "prime192v1", "secp224r1", "secp256r1", "prime256v1", "secp384r1", "secp521r1" of these; and, on
+ * the kernels for a general a (dbl-2007-bl, the prime taken at run time), "brainpoolp192r1", "brainpoolp224r1",
+ * "brainpoolp256r1", "brainpoolp320r1", "brainpoolp384r1", "brainpoolp512r1" (OpenSSL's "brainpoolP256r1" spelling is
+ * accepted too), "prime192v2", "prime192v3", "prime239v1", "prime239v2", "prime239v3", "secp192k1", "secp224k1" and
+ * "secp256k1".  Only P-256 and P-384 are tuned.  Any other name is VMN_ERR_UNSUPPORTED.
  * ref: the default group of the reference, demo/mixnet/.conf:153 (P-256); SURVEY.md §2.3 K11.  Group elements cross the boundary as
  * x || y (elem_bytes = 2 * coordinate width, big-endian; the point at infinity is all 0xff bytes);
- * exponents are residues mod the group order.  Every vmn_garray_* call works on such groups with the
+ * exponents are residues mod the group order, exp_bytes wide (the width of the order: secp224k1 has 225 bits of order
+ * on a 224-bit field).  Every vmn_garray_* call works on such groups with the
  * group operation = point addition ("mul") and exponentiation = scalar multiplication ("exp"). */
 int vmn_ec_group_create(vmn_ctx* ctx, const char* curve_name, vmn_group** out);
 void vmn_group_destroy(vmn_group* grp);
@@ -128,12 +133,15 @@ size_t vmn_group_exp_bytes(const vmn_group* grp);      /* bytes per exponent (ri
 int vmn_group_set_wire_bytes(vmn_group* grp, size_t elem_bytes, size_t exp_bytes);
 /* PGroup accessors used by host-side protocol code: getElementOrder() (P/hvzk/PoSBasicTW.java:470 uses its
  * bit length), getg() (P/mixnet/PermutationCommitment.java:200), and the modulus / field prime.
- * kind: 0 = ModPGroup, 1 = ECqPGroup.  order / modulus: exp_bytes big-endian bytes; generator: elem_bytes. */
+ * kind: 0 = ModPGroup, 1 = ECqPGroup.  order: exp_bytes big-endian bytes; modulus: the modulus resp. the field prime (the
+ * width of one element resp. one coordinate); generator: elem_bytes.  curve_a (ECqPGroup only): the coefficient a of
+ * y^2 = x^3 + a x + b as a residue in [0, p), one coordinate's width (p - 3 for the NIST curves). */
 int vmn_group_kind(const vmn_group* grp);
 vmn_ctx* vmn_group_ctx(const vmn_group* grp);        /* the context (main lane) the group was created in */
 int vmn_group_get_order(const vmn_group* grp, uint8_t* q_be);
 int vmn_group_get_modulus(const vmn_group* grp, uint8_t* p_be);
 int vmn_group_get_generator(const vmn_group* grp, uint8_t* g_be);
+int vmn_group_get_curve_a(const vmn_group* grp, uint8_t* a_be);
 
 /* ---- group element arrays (PGroupElementArray) --------------------------------------------- */
 

@@ -7,8 +7,11 @@ import com.verificatum.arithm.PGroup;
 import com.verificatum.arithm.PGroupElement;
 
 /** One GPU context (vmn_ctx) and one group on it (vmn_group) for a VCR {@code PGroup}: a safe-prime {@code ModPGroup} of up
- *  to 4096 bits or {@code ECqPGroup} over P-256 / P-384 (the reference's group shapes,
- *  src/java/com/verificatum/protocol/elgamal/ProtocolElGamal.java:738-800; default group P-256, demo/mixnet/.conf:153).
+ *  to 4096 bits or {@code ECqPGroup} over any of the curve names the reference offers -- P-192 ... P-521, brainpoolp192r1 ...
+ *  brainpoolp512r1, prime192v1-3, prime239v1-3, prime256v1, secp192k1 / r1, secp224k1 / r1, secp256k1 / r1, secp384r1,
+ *  secp521r1 (demo/mixnet/.conf:151-176; {@code getCurveName()} is passed through as it is); P-256 and P-384 are the tuned
+ *  ones (the reference's group shapes, src/java/com/verificatum/protocol/elgamal/ProtocolElGamal.java:738-800; default
+ *  group P-256, demo/mixnet/.conf:153).
  *  The wire widths are the reference's: vmn_group_set_wire_bytes(0, 0) selects Java's BigInteger.toByteArray() lengths.
  *  The VCR accessors used here (getModulus, getElementOrder, getg, toByteArray of an element) are VCR 3.1.0 API
  *  [NOT-IN-REF: the classes are not in the reference tree]. */

@@ -405,16 +405,22 @@ class ModPGroup:
 
 
 class ECqPGroup(ModPGroup):
-    """``com.verificatum.arithm.ECqPGroup`` over a NIST curve (the reference's default group is P-256,
-    demo/mixnet/.conf:153).  Elements are affine points ``(x, y)`` (``None`` = infinity); on the wire
-    x || y fixed width; ``mul`` is point addition, ``exp`` scalar multiplication; exponents live in Z_n."""
+    """``com.verificatum.arithm.ECqPGroup`` over a named curve (the reference's default group is P-256,
+    demo/mixnet/.conf:153).  Any of the reference's 26 names (demo/mixnet/.conf:151-176): P-192 ... P-521,
+    brainpoolp192r1 ... brainpoolp512r1, prime192v1-3, prime239v1-3, prime256v1, secp192k1 / r1, secp224k1 / r1,
+    secp256k1 / r1, secp384r1, secp521r1 (19 distinct curves, all of cofactor 1; OpenSSL's ``brainpoolP256r1``
+    spelling is accepted too).  The curve is y^2 = x^3 + a x + b (``self.a``; a = -3 on the NIST curves).
+    Elements are affine points ``(x, y)`` (``None`` = infinity); on the wire x || y fixed width; ``mul`` is
+    point addition, ``exp`` scalar multiplication; exponents live in Z_n (their width is that of n, which
+    for secp224k1 is one bit wider than p)."""
 
     def __init__(self, ctx: Context, name: str = "P-256", java_widths: bool = False):
         from . import ecscalar
         self._ec = ecscalar
-        c = ecscalar.CURVES[name]
+        c = ecscalar.curve(name)
         self.ctx, self.name = ctx, name
         self.p, self.q, self.b = c["p"], c["n"], c["b"]
+        self.a = ecscalar.curve_a(c)
         self.g = (c["gx"], c["gy"])
         self._h = C.c_void_p()
         _check(lib().vmn_ec_group_create(ctx._h, name.encode(), C.byref(self._h)))
@@ -453,10 +459,10 @@ class ECqPGroup(ModPGroup):
         return [self.dec_el(buf[i:i + w]) for i in range(0, len(buf), w)]
 
     def _py_mul(self, a, b):
-        return self._ec.add(a, b, self.p)
+        return self._ec.add(a, b, self.p, self.a)
 
     def _py_exp(self, a, e: int):
-        return self._ec.mul(e, a, self.p, self.q)
+        return self._ec.mul(e, a, self.p, self.q, self.a)
 
     def _py_inv(self, a):
         return self._ec.neg(a, self.p)

@@ -1,4 +1,5 @@
-// ec_kernels.h — elliptic-curve groups (ECqPGroup: NIST P-224 / P-256 / P-384 / P-521, a = -3) on gfx950.
+// ec_kernels.h — elliptic-curve groups (ECqPGroup: the NIST curves P-192 ... P-521 with a = -3, and the other named curves
+// of the reference -- brainpool, secp*k1, prime239v* -- with a general a) on gfx950.
 //
 // The reference's code is group-agnostic (every call site of K1-K7 is reached with
 // `pGroup` = ECqPGroup, the default group being P-256, demo/mixnet/.conf:153).  In VCR's multiplicative
@@ -22,6 +23,11 @@
 
 namespace vmn {
 
+// The kind of a curve kernel (the last template parameter of every curve kernel and of the field and point code under them):
+//   EC_NIST     a = -3 (dbl-2001-b); the primes of S = 10 (P-256) and S = 15 (P-384) are compile-time constants (FieldPrime)
+//   EC_GENERAL  any a (dbl-2007-bl with the product by a, read from ECDev::a); the prime is known at run time only, whatever S
+enum : int { EC_NIST = 0, EC_GENERAL = 1 };
+
 // Curve constants in device memory (wave-uniform: read through scalar loads)
 struct ECDev {
     const u32* p;      // S limbs of the field prime
@@ -41,6 +47,8 @@ struct ECDev {
     u32 p1p;           // p[1] + 1 (limb 1 of the prime, plus the carry fold of mont_row)
     u32 c16;           // 16, as a run-time value: `hi * 16 + c` must stay ONE v_mad_u64_u32 (mont_row, wide digits)
     int pwords;        // words of pm2
+    const u32* a;      // curve coefficient a, Montgomery form, canonical (< p): read by the EC_GENERAL kernels only
+    int a_zero;        // a = 0 (secp*k1): the EC_GENERAL doubling skips its product by a (wave-uniform)
 };
 
 template <int S>
@@ -96,6 +104,12 @@ struct FieldPrime<15> {
     static constexpr u32 limb[15] = {0xfffffffu, 0xfu, 0u, 0xffff000u, 0xffeffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu,
                                      0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0x00fffffu, 0u};
 };
+// the prime as the kernels of one kind see it: EC_GENERAL kernels take every prime at run time (the generic rows of mont_row,
+// no wide digits, f_maybe_zero always true), whatever its limb count
+template <int S, int KIND>
+struct FieldOf : FieldPrime<S> {};
+template <int S>
+struct FieldOf<S, EC_GENERAL> : FieldPrime<0> {};
 // one reduction row of a CIOS product: P <- (P + m p) / 2^28 with m = -P[0] / p mod 2^28; the top column is left to the caller
 // WIDE rows (the point formulas over P-256): the quotient digit is the whole low WORD of column 0, x = P[0] mod 2^32, not its
 // low 28 bits -- any digit = -P[0] / p mod 2^28 clears the limb, and x is one (x p = -x mod 2^28).  With p[0] = 2^28 - 1,
@@ -107,9 +121,9 @@ struct FieldPrime<15> {
 // column holds S operand products (< 2^58: one operand may be a carry-less sum) + NZ digit products (< 2^60, NZ = non-zero
 // limbs of p above limb 0) -- wide_digit_ok checks that this stays below 2^64: P-256 (6 of 9) yes, P-384 (13 of 14) no.
 // Everything that canonicalises, compares, inverts or exports keeps the exact rows (results < 2 p).
-template <int S>
+template <int S, int KIND = EC_NIST>
 constexpr bool wide_digit_ok() {
-    using FP = FieldPrime<S>;
+    using FP = FieldOf<S, KIND>;
     if constexpr (!FP::known) {
         return false;
     } else {
@@ -120,11 +134,11 @@ constexpr bool wide_digit_ok() {
         return (unsigned)S + 4u * nz + 1u < 64u;
     }
 }
-template <int S, bool WIDE = false>
+template <int S, bool WIDE = false, int KIND = EC_NIST>
 __device__ __forceinline__ void mont_row(u64 (&P)[S], const ECDev& E) {
-    using FP = FieldPrime<S>;
+    using FP = FieldOf<S, KIND>;
     if constexpr (WIDE) {
-        static_assert(wide_digit_ok<S>(), "wide quotient digits need p = -1 mod 2^28 and room in the columns");
+        static_assert(wide_digit_ok<S, KIND>(), "wide quotient digits need p = -1 mod 2^28 and room in the columns");
         const u32 x = (u32)P[0], hi = (u32)(P[0] >> 32);
         P[0] = (u64)x * E.p1p + ((u64)hi * E.c16 + P[1]);  // (a literal 16 becomes shift + mask + 64-bit add)
 #pragma unroll
@@ -158,7 +172,7 @@ __device__ __forceinline__ void mont_row(u64 (&P)[S], const ECDev& E) {
     }
 }
 // r = a * b / R  (mod p), result < 2p for operands with a*b < R*p
-template <int S, bool WIDE = false>
+template <int S, bool WIDE = false, int KIND = EC_NIST>
 __device__ __forceinline__ void f_mul(u32 (&r)[S], const u32 (&a)[S], const u32 (&b)[S], const ECDev& E) {
     u64 P[S];
 #pragma unroll
@@ -168,7 +182,7 @@ __device__ __forceinline__ void f_mul(u32 (&r)[S], const u32 (&a)[S], const u32 
             if (i == 0 || j == S - 1) P[j] = (u64)a[j] * b[i];
             else P[j] = (u64)a[j] * b[i] + P[j];
         }
-        mont_row<S, WIDE>(P, E);
+        mont_row<S, WIDE, KIND>(P, E);
     }
     P[S - 1] = 0;
     f_norm<S>(r, P);
@@ -178,7 +192,7 @@ __device__ __forceinline__ void f_mul(u32 (&r)[S], const u32 (&a)[S], const u32 
 // reduced, in row i + j >= max(i, j)).  S (S + 1) / 2 + S^2 multiply-adds instead of 2 S^2.  Column bound: the operand may be
 // a carry-less sum (f_addl: limbs < 2^29), so a column holds at most S products < 2^58 (a doubled cross product counts twice)
 // + S reduction products < 2^56: < 2^62.8 for S <= 21.
-template <int S, bool WIDE = false>
+template <int S, bool WIDE = false, int KIND = EC_NIST>
 __device__ __forceinline__ void f_sqr(u32 (&r)[S], const u32 (&a)[S], const ECDev& E) {
     u64 P[S];
 #pragma unroll
@@ -190,7 +204,7 @@ __device__ __forceinline__ void f_sqr(u32 (&r)[S], const u32 (&a)[S], const ECDe
             if (i == 0 || j == S - 1) P[j] = (u64)a[j] * mult;         // a fresh column (the top one is vacated by every shift)
             else P[j] = (u64)a[j] * mult + P[j];
         }
-        mont_row<S, WIDE>(P, E);
+        mont_row<S, WIDE, KIND>(P, E);
     }
     P[S - 1] = 0;
     f_norm<S>(r, P);
@@ -219,9 +233,9 @@ __device__ __forceinline__ void f_addl(u32 (&r)[S], const u32 (&a)[S], const u32
 // f_sub) below 2^28 p: then a = k p with k < 2^28, and for a prime that is -1 modulo 2^84 (limbs 0..2 all ones: P-256) the
 // limbs 1 and 2 of k p = k 2^84 (...) - k are all ones (k > 0) or zero (k = 0).  A random difference passes with probability
 // 2^-55; only then does the caller pay the canonical test (f_is_zero: the reduction half of a product).  Other primes: true.
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ bool f_maybe_zero(const u32 (&a)[S]) {
-    using FP = FieldPrime<S>;
+    using FP = FieldOf<S, KIND>;
     if constexpr (FP::known) {
         if constexpr (FP::limb[0] == LIMB_MASK && FP::limb[1] == LIMB_MASK && FP::limb[2] == LIMB_MASK)
             return (a[1] & a[2]) == LIMB_MASK || (a[1] | a[2]) == 0;
@@ -277,12 +291,12 @@ __device__ __forceinline__ void f_small(u32 (&r)[S], const u32 (&a)[S]) {
     }
 }
 // canonical representative (< p) of a lazy value
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void f_canon(u32 (&r)[S], const u32 (&a)[S], const ECDev& E) {
     u32 one[S], t[S], d[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) one[j] = E.one[j];
-    f_mul<S>(t, a, one, E);                            // a * R / R = a, now < 2p
+    f_mul<S, false, KIND>(t, a, one, E);               // a * R / R = a, now < 2p
     int32_t borrow = 0;
 #pragma unroll
     for (int j = 0; j < S; ++j) {
@@ -295,14 +309,14 @@ __device__ __forceinline__ void f_canon(u32 (&r)[S], const u32 (&a)[S], const EC
 }
 // a = 0 mod p ?  Only the reduction half of a product (a * 1 / R): S^2 multiply-adds.  The result is = a / R mod p and
 // lies in [0, p] (a / R < 1 for every lazy value), so a = 0 mod p exactly when it is 0 or p.
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ bool f_is_zero(const u32 (&a)[S], const ECDev& E) {
     u64 P[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) P[j] = a[j];
 #pragma unroll
     for (int i = 0; i < S; ++i) {
-        mont_row<S>(P, E);
+        mont_row<S, false, KIND>(P, E);
         P[S - 1] = 0;
     }
     u32 t[S];
@@ -316,21 +330,21 @@ __device__ __forceinline__ bool f_is_zero(const u32 (&a)[S], const ECDev& E) {
     return nz == 0 || np == 0;
 }
 // r = a^(p-2): Fermat inversion, left-to-right binary (uniform exponent: no divergence).  Export only.
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ void f_pow_words(u32 (&r)[S], const u32 (&a)[S], const u32* __restrict__ ewords, int nwords, const ECDev& E) {
     u32 acc[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) acc[j] = E.one[j];
     for (int bit = nwords * 32 - 1; bit >= 0; --bit) {
-        f_sqr<S>(acc, acc, E);
-        if ((ewords[bit >> 5] >> (bit & 31)) & 1) f_mul<S>(acc, acc, a, E);
+        f_sqr<S, false, KIND>(acc, acc, E);
+        if ((ewords[bit >> 5] >> (bit & 31)) & 1) f_mul<S, false, KIND>(acc, acc, a, E);
     }
 #pragma unroll
     for (int j = 0; j < S; ++j) r[j] = acc[j];
 }
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ void f_inv(u32 (&r)[S], const u32 (&a)[S], const ECDev& E) {
-    f_pow_words<S>(r, a, E.pm2, E.pwords, E);
+    f_pow_words<S, KIND>(r, a, E.pm2, E.pwords, E);
 }
 
 // z = a candidate square root of a (canonical Montgomery-form input): z^2 = a when a is a square; the caller checks.
@@ -338,10 +352,10 @@ __device__ void f_inv(u32 (&r)[S], const u32 (&a)[S], const ECDev& E) {
 // t != 1: i = the least exponent with t^(2^i) = 1, b = c^(2^(M-i-1)), x *= b, c = b^2, t *= c, M = i (c starts as z^Q for a
 // non-residue z).  The loops are data-dependent (lanes of a wave take the longest of their paths): only the derivation of
 // random points runs this, once per candidate.
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ void f_sqrt(u32 (&z)[S], const u32 (&a)[S], const ECDev& E) {
     if (E.ts_s == 0) {
-        f_pow_words<S>(z, a, E.pp14, E.pwords, E);
+        f_pow_words<S, KIND>(z, a, E.pp14, E.pwords, E);
         return;
     }
     u32 one[S], u[S], x[S], t[S], c[S], b[S], tt[S], d[S];
@@ -352,38 +366,38 @@ __device__ void f_sqrt(u32 (&z)[S], const u32 (&a)[S], const ECDev& E) {
     }
     auto is_one = [&](const u32 (&v)[S]) {
         f_sub<S>(d, v, one, E);
-        return f_is_zero<S>(d, E);
+        return f_is_zero<S, KIND>(d, E);
     };
-    f_pow_words<S>(u, a, E.ts_e, E.ts_ewords, E);          // a^((Q-1)/2)
-    f_mul<S>(x, a, u, E);                                  // a^((Q+1)/2)
-    f_mul<S>(t, x, u, E);                                  // a^Q
-    f_canon<S>(t, t, E);
+    f_pow_words<S, KIND>(u, a, E.ts_e, E.ts_ewords, E);    // a^((Q-1)/2)
+    f_mul<S, false, KIND>(x, a, u, E);                     // a^((Q+1)/2)
+    f_mul<S, false, KIND>(t, x, u, E);                     // a^Q
+    f_canon<S, KIND>(t, t, E);
     int M = E.ts_s;
     for (int guard = 0; guard <= E.ts_s; ++guard) {        // M strictly decreases: at most ts_s rounds
-        if (is_one(t) || f_is_zero<S>(t, E)) break;        // done (t = 0: a = 0, x = 0 is its root)
+        if (is_one(t) || f_is_zero<S, KIND>(t, E)) break;  // done (t = 0: a = 0, x = 0 is its root)
         int i = 0;
 #pragma unroll
         for (int j = 0; j < S; ++j) tt[j] = t[j];
         do {
-            f_sqr<S>(tt, tt, E);
-            f_canon<S>(tt, tt, E);
+            f_sqr<S, false, KIND>(tt, tt, E);
+            f_canon<S, KIND>(tt, tt, E);
             ++i;
         } while (i < M && !is_one(tt));
         if (i >= M) break;                                 // a is not a square: the caller's check rejects x
 #pragma unroll
         for (int j = 0; j < S; ++j) b[j] = c[j];
         for (int k = 0; k < M - i - 1; ++k) {
-            f_sqr<S>(b, b, E);
-            f_canon<S>(b, b, E);
+            f_sqr<S, false, KIND>(b, b, E);
+            f_canon<S, KIND>(b, b, E);
         }
-        f_mul<S>(x, x, b, E);
-        f_sqr<S>(c, b, E);
-        f_canon<S>(c, c, E);
-        f_mul<S>(t, t, c, E);
-        f_canon<S>(t, t, E);
+        f_mul<S, false, KIND>(x, x, b, E);
+        f_sqr<S, false, KIND>(c, b, E);
+        f_canon<S, KIND>(c, c, E);
+        f_mul<S, false, KIND>(t, t, c, E);
+        f_canon<S, KIND>(t, t, E);
         M = i;
     }
-    f_canon<S>(z, x, E);
+    f_canon<S, KIND>(z, x, E);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -454,31 +468,89 @@ __device__ __forceinline__ void pt_store(u32* __restrict__ row, const Pt<S>& P) 
     put(row + 2 * FW, P.Z, P.inf);
 }
 
-// dbl-2001-b (a = -3): 3M + 5S, valid for every input (infinity stays infinity through the flag)
+// EC_GENERAL: dbl-2007-bl (any a): 1M + 8S + one product by a (none when a = 0), valid for every input like the one below.
+// Bounds (multiples of p; exact rows only, so every product is < 2): the coordinates that reach a doubling are < 546 (Z of
+// pt_mmadd; X, Y leave a formula below 82 and a negated Y is < 256), all below B = 2^10.
+//   XX = X^2, YY = Y^2, ZZ = Z^2 (B^2 = 2^20), YYYY = YY^2, u = (X + YY)^2 ((B + 2)^2 < 2^20.1), ZZ^2, a ZZ^2 (a < 1): all < 2
+//   M = 3 XX + a ZZ^2 < 8                          M^2: 8^2
+//   w = XX + YYYY < 4                              S' = u - w + 64p < 66 (w of the 64p form),  S = 2 S' < 132
+//   X3 = T = M^2 + 4 w - 4 u + 64p < 82            (T = M^2 - 2 S: the subtrahend 4 u < 8 fits the 64p form, 2 S would not)
+//   S - T + 256p < 388 (T < 82: the 256p form)     M (S - T): 8 x 388 < 2^12
+//   Y3 = M (S - T) - 8 YYYY + 64p < 66             (8 YYYY < 16)
+//   Z3 = (Y + Z)^2 - (YY + ZZ) + 64p < 66          ((2B)^2 = 2^22; YY + ZZ < 4)
+// Every product has operands whose bounds multiply to less than 2^22 < R / p.  The coordinates leave below 82: the other
+// formulas take a coordinate as a subtrahend in the 256p form only, and with exact rows (products < 2, not 17) their own
+// bounds (stated below for c = 17) shrink by far more than the one p that X3 has above 81.
 template <int S>
-__device__ __forceinline__ void pt_dbl(Pt<S>& R, const Pt<S>& P, const ECDev& E) {
-    constexpr bool W = wide_digit_ok<S>();             // products below 17 p instead of 2 p (mont_row)
+__device__ __forceinline__ void pt_dbl_general(Pt<S>& R, const Pt<S>& P, const ECDev& E) {
+    u32 XX[S], YY[S], YYYY[S], ZZ[S], w[S], M[S], t1[S], t2[S], t3[S];
+    f_sqr<S, false, EC_GENERAL>(XX, P.X, E);
+    f_sqr<S, false, EC_GENERAL>(YY, P.Y, E);
+    f_sqr<S, false, EC_GENERAL>(YYYY, YY, E);
+    f_sqr<S, false, EC_GENERAL>(ZZ, P.Z, E);
+    f_small<S, 3>(M, XX);
+    if (!E.a_zero) {                                   // (wave-uniform)
+        u32 aa[S];
+#pragma unroll
+        for (int j = 0; j < S; ++j) aa[j] = E.a[j];
+        f_sqr<S, false, EC_GENERAL>(t1, ZZ, E);
+        f_mul<S, false, EC_GENERAL>(t2, t1, aa, E);
+        f_add<S>(M, M, t2);                            // M = 3 XX + a ZZ^2
+    }
+    f_add<S>(w, XX, YYYY);
+    f_addl<S>(t1, P.X, YY);
+    u32 u[S];
+    f_sqr<S, false, EC_GENERAL>(u, t1, E);             // (X + YY)^2
+    f_sqr<S, false, EC_GENERAL>(t1, M, E);
+    f_small<S, 4>(t2, w);
+    f_addl<S>(t1, t1, t2);
+    f_small<S, 4>(t2, u);
+    u32 X3[S];
+    f_sub<S>(X3, t1, t2, E);                           // T = M^2 - 2 S = M^2 + 4 w - 4 u
+    f_sub<S>(t1, u, w, E);
+    f_small<S, 2>(t2, t1);                             // S = 2 ((X + YY)^2 - XX - YYYY)
+    f_sub<S, true>(t1, t2, X3, E);
+    f_mul<S, false, EC_GENERAL>(t3, M, t1, E);
+    f_small<S, 8>(t2, YYYY);
+    u32 Y3[S];
+    f_sub<S>(Y3, t3, t2, E);                           // M (S - T) - 8 YYYY
+    f_addl<S>(t1, P.Y, P.Z);
+    f_sqr<S, false, EC_GENERAL>(t2, t1, E);
+    f_add<S>(t1, YY, ZZ);
+    f_sub<S>(R.Z, t2, t1, E);                          // (Y + Z)^2 - YY - ZZ
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+        R.X[j] = X3[j];
+        R.Y[j] = Y3[j];
+    }
+    R.inf = P.inf;
+}
+
+// dbl-2001-b (a = -3): 3M + 5S, valid for every input (infinity stays infinity through the flag)
+template <int S, int KIND = EC_NIST>
+__device__ __forceinline__ void pt_dbl_a3(Pt<S>& R, const Pt<S>& P, const ECDev& E) {
+    constexpr bool W = wide_digit_ok<S, KIND>();       // products below 17 p instead of 2 p (mont_row)
     u32 delta[S], gamma[S], beta[S], alpha[S], t1[S], t2[S], t3[S];
-    f_sqr<S, W>(delta, P.Z, E);
-    f_sqr<S, W>(gamma, P.Y, E);
-    f_mul<S, false>(beta, P.X, gamma, E);
+    f_sqr<S, W, KIND>(delta, P.Z, E);
+    f_sqr<S, W, KIND>(gamma, P.Y, E);
+    f_mul<S, false, KIND>(beta, P.X, gamma, E);
     f_sub<S>(t1, P.X, delta, E);
     f_addl<S>(t2, P.X, delta);
-    f_mul<S, W>(t3, t1, t2, E);
+    f_mul<S, W, KIND>(t3, t1, t2, E);
     f_small<S, 3>(alpha, t3);                          // alpha = 3 (X - delta)(X + delta)
     f_addl<S>(t1, P.Y, P.Z);
-    f_sqr<S, W>(t2, t1, E);
+    f_sqr<S, W, KIND>(t2, t1, E);
     f_addl<S>(t3, gamma, delta);
     u32 Z3[S];
     f_sub<S>(Z3, t2, t3, E);                           // (Y + Z)^2 - gamma - delta
-    f_sqr<S, W>(t1, alpha, E);
+    f_sqr<S, W, KIND>(t1, alpha, E);
     f_small<S, 8>(t2, beta);
     u32 X3[S];
     f_sub<S>(X3, t1, t2, E);                           // alpha^2 - 8 beta
     f_small<S, 4>(t1, beta);
     f_sub<S, true>(t2, t1, X3, E);
-    f_mul<S, W>(t3, alpha, t2, E);
-    f_sqr<S, false>(t1, gamma, E);
+    f_mul<S, W, KIND>(t3, alpha, t2, E);
+    f_sqr<S, false, KIND>(t1, gamma, E);
     f_small<S, 8>(t2, t1);
     f_sub<S>(R.Y, t3, t2, E);                          // alpha (4 beta - X3) - 8 gamma^2
 #pragma unroll
@@ -488,46 +560,51 @@ __device__ __forceinline__ void pt_dbl(Pt<S>& R, const Pt<S>& P, const ECDev& E)
     }
     R.inf = P.inf;
 }
+template <int S, int KIND = EC_NIST>
+__device__ __forceinline__ void pt_dbl(Pt<S>& R, const Pt<S>& P, const ECDev& E) {
+    if constexpr (KIND == EC_GENERAL) pt_dbl_general<S>(R, P, E);
+    else pt_dbl_a3<S, KIND>(R, P, E);
+}
 
 // add-2007-bl: 11M + 5S; exceptional inputs handled exactly
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void pt_add(Pt<S>& R, const Pt<S>& P, const Pt<S>& Q, const ECDev& E) {
-    constexpr bool W = wide_digit_ok<S>();             // products below 17 p instead of 2 p (mont_row)
+    constexpr bool W = wide_digit_ok<S, KIND>();       // products below 17 p instead of 2 p (mont_row)
     u32 Z1Z1[S], Z2Z2[S], U1[S], U2[S], S1[S], S2[S], H[S], rr[S], t1[S], t2[S];
-    f_sqr<S, W>(Z1Z1, P.Z, E);
-    f_sqr<S, W>(Z2Z2, Q.Z, E);
-    f_mul<S, W>(U1, P.X, Z2Z2, E);
-    f_mul<S, W>(U2, Q.X, Z1Z1, E);
-    f_mul<S, W>(t1, P.Y, Q.Z, E);
-    f_mul<S, W>(S1, t1, Z2Z2, E);
-    f_mul<S, W>(t1, Q.Y, P.Z, E);
-    f_mul<S, W>(S2, t1, Z1Z1, E);
+    f_sqr<S, W, KIND>(Z1Z1, P.Z, E);
+    f_sqr<S, W, KIND>(Z2Z2, Q.Z, E);
+    f_mul<S, W, KIND>(U1, P.X, Z2Z2, E);
+    f_mul<S, W, KIND>(U2, Q.X, Z1Z1, E);
+    f_mul<S, W, KIND>(t1, P.Y, Q.Z, E);
+    f_mul<S, W, KIND>(S1, t1, Z2Z2, E);
+    f_mul<S, W, KIND>(t1, Q.Y, P.Z, E);
+    f_mul<S, W, KIND>(S2, t1, Z1Z1, E);
     f_sub<S>(H, U2, U1, E);
     f_sub<S>(rr, S2, S1, E);
-    bool hz = f_maybe_zero<S>(H) && f_is_zero<S>(H, E);
+    bool hz = f_maybe_zero<S, KIND>(H) && f_is_zero<S, KIND>(H, E);
     bool special = P.inf || Q.inf || hz;
     Pt<S> G;                                           // general-case result
     {
         u32 I[S], J[S], r[S], V[S];
         f_addl<S>(t1, H, H);
-        f_sqr<S, W>(I, t1, E);                            // (2H)^2
-        f_mul<S, W>(J, H, I, E);
+        f_sqr<S, W, KIND>(I, t1, E);                      // (2H)^2
+        f_mul<S, W, KIND>(J, H, I, E);
         f_addl<S>(r, rr, rr);
-        f_mul<S, W>(V, U1, I, E);
-        f_sqr<S, W>(t1, r, E);
+        f_mul<S, W, KIND>(V, U1, I, E);
+        f_sqr<S, W, KIND>(t1, r, E);
         f_addl<S>(t2, V, V);
         f_addl<S>(t2, t2, J);
         f_sub<S>(G.X, t1, t2, E);                      // r^2 - J - 2V
         f_sub<S, true>(t1, V, G.X, E);
-        f_mul<S, W>(t2, r, t1, E);
-        f_mul<S, W>(t1, S1, J, E);
+        f_mul<S, W, KIND>(t2, r, t1, E);
+        f_mul<S, W, KIND>(t1, S1, J, E);
         f_addl<S>(t1, t1, t1);
         f_sub<S>(G.Y, t2, t1, E);                      // r (V - X3) - 2 S1 J
         f_addl<S>(t1, P.Z, Q.Z);
-        f_sqr<S, W>(t2, t1, E);
+        f_sqr<S, W, KIND>(t2, t1, E);
         f_addl<S>(t1, Z1Z1, Z2Z2);
         f_sub<S>(t2, t2, t1, E);
-        f_mul<S, W>(G.Z, t2, H, E);                       // ((Z1 + Z2)^2 - Z1Z1 - Z2Z2) H
+        f_mul<S, W, KIND>(G.Z, t2, H, E);                 // ((Z1 + Z2)^2 - Z1Z1 - Z2Z2) H
         G.inf = 0;
     }
     if (special) {                                     // rare: wave-divergent
@@ -535,8 +612,8 @@ __device__ __forceinline__ void pt_add(Pt<S>& R, const Pt<S>& P, const Pt<S>& Q,
             G = Q;
         } else if (Q.inf) {
             G = P;
-        } else if (f_is_zero<S>(rr, E)) {
-            pt_dbl<S>(G, P, E);                        // P == Q
+        } else if (f_is_zero<S, KIND>(rr, E)) {
+            pt_dbl<S, KIND>(G, P, E);                  // P == Q
         } else {
             pt_set_inf<S>(G, E);                       // P == -Q
         }
@@ -548,37 +625,37 @@ __device__ __forceinline__ void pt_add(Pt<S>& R, const Pt<S>& P, const Pt<S>& Q,
 // a normalised array keep the three-coordinate layout (Z = the Montgomery one), so every other kernel reads them as they
 // are.  Bounds (multiples of p): X1, Y1, Z1 < 81 as they leave an addition or a doubling, so the differences with them as
 // subtrahend use the 256p form (< 273); the largest product is r * (V - X3) < 546 * 273 p^2, far below R p = 2^24 p^2.
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void pt_madd(Pt<S>& R, const Pt<S>& P, const Pt<S>& Q, const ECDev& E) {
-    constexpr bool W = wide_digit_ok<S>();             // products below 17 p instead of 2 p (mont_row)
+    constexpr bool W = wide_digit_ok<S, KIND>();       // products below 17 p instead of 2 p (mont_row)
     u32 Z1Z1[S], U2[S], S2[S], H[S], HH[S], I[S], J[S], r[S], V[S], t1[S], t2[S];
-    f_sqr<S, W>(Z1Z1, P.Z, E);
-    f_mul<S, W>(U2, Q.X, Z1Z1, E);
-    f_mul<S, W>(t1, P.Z, Z1Z1, E);
-    f_mul<S, W>(S2, Q.Y, t1, E);
+    f_sqr<S, W, KIND>(Z1Z1, P.Z, E);
+    f_mul<S, W, KIND>(U2, Q.X, Z1Z1, E);
+    f_mul<S, W, KIND>(t1, P.Z, Z1Z1, E);
+    f_mul<S, W, KIND>(S2, Q.Y, t1, E);
     f_sub<S, true>(H, U2, P.X, E);
     f_sub<S, true>(t1, S2, P.Y, E);                    // S2 - Y1
-    bool hz = f_maybe_zero<S>(H) && f_is_zero<S>(H, E);
+    bool hz = f_maybe_zero<S, KIND>(H) && f_is_zero<S, KIND>(H, E);
     bool special = P.inf || Q.inf || hz;
     Pt<S> G;
     {
-        f_sqr<S, W>(HH, H, E);
+        f_sqr<S, W, KIND>(HH, H, E);
         f_small<S, 4>(I, HH);
-        f_mul<S, W>(J, H, I, E);
+        f_mul<S, W, KIND>(J, H, I, E);
         f_addl<S>(r, t1, t1);
-        f_mul<S, W>(V, P.X, I, E);
-        f_sqr<S, W>(t2, r, E);
+        f_mul<S, W, KIND>(V, P.X, I, E);
+        f_sqr<S, W, KIND>(t2, r, E);
         u32 t3[S];
         f_addl<S>(t3, V, V);
         f_addl<S>(t3, t3, J);
         f_sub<S>(G.X, t2, t3, E);                      // r^2 - J - 2V
         f_sub<S, true>(t2, V, G.X, E);
-        f_mul<S, W>(t3, r, t2, E);
-        f_mul<S, W>(t2, P.Y, J, E);
+        f_mul<S, W, KIND>(t3, r, t2, E);
+        f_mul<S, W, KIND>(t2, P.Y, J, E);
         f_addl<S>(t2, t2, t2);
         f_sub<S>(G.Y, t3, t2, E);                      // r (V - X3) - 2 Y1 J
         f_addl<S>(t2, P.Z, H);
-        f_sqr<S, W>(t3, t2, E);
+        f_sqr<S, W, KIND>(t3, t2, E);
         f_addl<S>(t2, Z1Z1, HH);
         f_sub<S>(G.Z, t3, t2, E);                      // (Z1 + H)^2 - Z1Z1 - HH
         G.inf = 0;
@@ -590,8 +667,8 @@ __device__ __forceinline__ void pt_madd(Pt<S>& R, const Pt<S>& P, const Pt<S>& Q
             for (int j = 0; j < S; ++j) G.Z[j] = Q.inf ? 0u : E.one[j];       // (Q.Z is not loaded: it is one by contract)
         } else if (Q.inf) {
             G = P;
-        } else if (f_is_zero<S>(t1, E)) {
-            pt_dbl<S>(G, P, E);                        // P == Q
+        } else if (f_is_zero<S, KIND>(t1, E)) {
+            pt_dbl<S, KIND>(G, P, E);                  // P == Q
         } else {
             pt_set_inf<S>(G, E);                       // P == -Q
         }
@@ -604,28 +681,28 @@ __device__ __forceinline__ void pt_madd(Pt<S>& R, const Pt<S>& P, const Pt<S>& Q
 // level at 6 field products instead of 11).  P.Z is not read.  Bounds: X, Y of a normalised row < 2 (a negated Y < 66), so
 // H, Y2 - Y1 in the 256p form < 273 (wide-digit products: rows < 17); Z3 = 2H < 546, inside what the next mixed addition
 // accepts (operands up to 2^12 p).
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void pt_mmadd(Pt<S>& R, const Pt<S>& P, const Pt<S>& Q, const ECDev& E) {
-    constexpr bool W = wide_digit_ok<S>();
+    constexpr bool W = wide_digit_ok<S, KIND>();
     u32 H[S], HH[S], I[S], J[S], r[S], V[S], t1[S], t2[S], t3[S];
     f_sub<S, true>(H, Q.X, P.X, E);
     f_sub<S, true>(t1, Q.Y, P.Y, E);                   // Y2 - Y1
-    bool hz = f_maybe_zero<S>(H) && f_is_zero<S>(H, E);
+    bool hz = f_maybe_zero<S, KIND>(H) && f_is_zero<S, KIND>(H, E);
     bool special = P.inf || Q.inf || hz;
     Pt<S> G;
     {
-        f_sqr<S, W>(HH, H, E);
+        f_sqr<S, W, KIND>(HH, H, E);
         f_small<S, 4>(I, HH);
-        f_mul<S, W>(J, H, I, E);
+        f_mul<S, W, KIND>(J, H, I, E);
         f_addl<S>(r, t1, t1);
-        f_mul<S, W>(V, P.X, I, E);
-        f_sqr<S, W>(t2, r, E);
+        f_mul<S, W, KIND>(V, P.X, I, E);
+        f_sqr<S, W, KIND>(t2, r, E);
         f_addl<S>(t3, V, V);
         f_addl<S>(t3, t3, J);
         f_sub<S>(G.X, t2, t3, E);                      // r^2 - J - 2V
         f_sub<S, true>(t2, V, G.X, E);
-        f_mul<S, W>(t3, r, t2, E);
-        f_mul<S, W>(t2, P.Y, J, E);
+        f_mul<S, W, KIND>(t3, r, t2, E);
+        f_mul<S, W, KIND>(t2, P.Y, J, E);
         f_addl<S>(t2, t2, t2);
         f_sub<S>(G.Y, t3, t2, E);                      // r (V - X3) - 2 Y1 J
         f_add<S>(G.Z, H, H);                           // 2 H
@@ -643,7 +720,7 @@ __device__ __forceinline__ void pt_mmadd(Pt<S>& R, const Pt<S>& P, const Pt<S>& 
                 G.Z[j] = E.one[j];                     // (Z of a normalised row is one by contract)
             }
             G.inf = 0;
-        } else if (f_is_zero<S>(t1, E)) {
+        } else if (f_is_zero<S, KIND>(t1, E)) {
             Pt<S> D;                                   // P == Q: double the affine point
 #pragma unroll
             for (int j = 0; j < S; ++j) {
@@ -652,7 +729,7 @@ __device__ __forceinline__ void pt_mmadd(Pt<S>& R, const Pt<S>& P, const Pt<S>& 
                 D.Z[j] = E.one[j];
             }
             D.inf = 0;
-            pt_dbl<S>(G, D, E);
+            pt_dbl<S, KIND>(G, D, E);
         } else {
             pt_set_inf<S>(G, E);                       // P == -Q
         }
@@ -685,10 +762,10 @@ __device__ __forceinline__ void ptx_from_normalised(PtX<S>& A, const Pt<S>& P, c
     }
     A.inf = P.inf;
 }
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void ptx_from_jacobian(PtX<S>& A, const Pt<S>& P, const ECDev& E) {
-    f_sqr<S>(A.ZZ, P.Z, E);
-    f_mul<S>(A.ZZZ, A.ZZ, P.Z, E);
+    f_sqr<S, false, KIND>(A.ZZ, P.Z, E);
+    f_mul<S, false, KIND>(A.ZZZ, A.ZZ, P.Z, E);
 #pragma unroll
     for (int j = 0; j < S; ++j) {
         A.X[j] = P.X[j];
@@ -696,51 +773,51 @@ __device__ __forceinline__ void ptx_from_jacobian(PtX<S>& A, const Pt<S>& P, con
     }
     A.inf = P.inf;
 }
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void ptx_to_jacobian(Pt<S>& R, const PtX<S>& A, const ECDev& E) {
     if (A.inf) {
         pt_set_inf<S>(R, E);
     } else {
-        f_mul<S>(R.X, A.X, A.ZZ, E);
-        f_mul<S>(R.Y, A.Y, A.ZZZ, E);
+        f_mul<S, false, KIND>(R.X, A.X, A.ZZ, E);
+        f_mul<S, false, KIND>(R.Y, A.Y, A.ZZZ, E);
 #pragma unroll
         for (int j = 0; j < S; ++j) R.Z[j] = A.ZZ[j];
         R.inf = 0;
     }
 }
 // the tail both additions share: from Pd = x2' - X1, Rd = y2' - Y1 (256p form), X1, Y1 to X3, Y3, PP, PPP
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void ptx_tail(u32 (&X3)[S], u32 (&Y3)[S], u32 (&PP)[S], u32 (&PPP)[S], const u32 (&Pd)[S], const u32 (&Rd)[S],
                                          const u32 (&X1)[S], const u32 (&Y1)[S], const ECDev& E) {
-    constexpr bool W = wide_digit_ok<S>();
+    constexpr bool W = wide_digit_ok<S, KIND>();
     u32 Qv[S], t1[S], t2[S], t3[S];
-    f_sqr<S, W>(PP, Pd, E);
-    f_mul<S, W>(PPP, Pd, PP, E);
-    f_mul<S, W>(Qv, X1, PP, E);
-    f_sqr<S, W>(t1, Rd, E);
+    f_sqr<S, W, KIND>(PP, Pd, E);
+    f_mul<S, W, KIND>(PPP, Pd, PP, E);
+    f_mul<S, W, KIND>(Qv, X1, PP, E);
+    f_sqr<S, W, KIND>(t1, Rd, E);
     f_addl<S>(t2, Qv, Qv);
     f_addl<S>(t2, t2, PPP);                            // 2Q + PPP < 51
     f_sub<S>(X3, t1, t2, E);                           // R^2 - PPP - 2Q
     f_sub<S, true>(t1, Qv, X3, E);
-    f_mul<S, W>(t2, Rd, t1, E);
-    f_mul<S, W>(t3, Y1, PPP, E);
+    f_mul<S, W, KIND>(t2, Rd, t1, E);
+    f_mul<S, W, KIND>(t3, Y1, PPP, E);
     f_sub<S>(Y3, t2, t3, E);                           // R (Q - X3) - Y1 PPP
 }
 // A += Q, Q normalised (madd-2008-s)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void ptx_madd(PtX<S>& A, const Pt<S>& Q, const ECDev& E) {
-    constexpr bool W = wide_digit_ok<S>();
+    constexpr bool W = wide_digit_ok<S, KIND>();
     u32 U2[S], S2[S], Pd[S], Rd[S], PP[S], PPP[S], X3[S], Y3[S];
-    f_mul<S, W>(U2, Q.X, A.ZZ, E);
-    f_mul<S, W>(S2, Q.Y, A.ZZZ, E);
+    f_mul<S, W, KIND>(U2, Q.X, A.ZZ, E);
+    f_mul<S, W, KIND>(S2, Q.Y, A.ZZZ, E);
     f_sub<S, true>(Pd, U2, A.X, E);
     f_sub<S, true>(Rd, S2, A.Y, E);
-    const bool hz = f_maybe_zero<S>(Pd) && f_is_zero<S>(Pd, E);
+    const bool hz = f_maybe_zero<S, KIND>(Pd) && f_is_zero<S, KIND>(Pd, E);
     const bool special = A.inf || Q.inf || hz;
     if (!special) {
-        ptx_tail<S>(X3, Y3, PP, PPP, Pd, Rd, A.X, A.Y, E);
-        f_mul<S, W>(A.ZZ, A.ZZ, PP, E);
-        f_mul<S, W>(A.ZZZ, A.ZZZ, PPP, E);
+        ptx_tail<S, KIND>(X3, Y3, PP, PPP, Pd, Rd, A.X, A.Y, E);
+        f_mul<S, W, KIND>(A.ZZ, A.ZZ, PP, E);
+        f_mul<S, W, KIND>(A.ZZZ, A.ZZZ, PPP, E);
 #pragma unroll
         for (int j = 0; j < S; ++j) {
             A.X[j] = X3[j];
@@ -749,7 +826,7 @@ __device__ __forceinline__ void ptx_madd(PtX<S>& A, const Pt<S>& Q, const ECDev&
     } else if (A.inf) {                                // rare from here on
         ptx_from_normalised<S>(A, Q, E);
     } else if (Q.inf) {
-    } else if (f_is_zero<S>(Rd, E)) {                  // the same point: double the normalised one
+    } else if (f_is_zero<S, KIND>(Rd, E)) {            // the same point: double the normalised one
         Pt<S> D, G;
 #pragma unroll
         for (int j = 0; j < S; ++j) {
@@ -758,28 +835,28 @@ __device__ __forceinline__ void ptx_madd(PtX<S>& A, const Pt<S>& Q, const ECDev&
             D.Z[j] = E.one[j];
         }
         D.inf = 0;
-        pt_dbl<S>(G, D, E);
-        ptx_from_jacobian<S>(A, G, E);
+        pt_dbl<S, KIND>(G, D, E);
+        ptx_from_jacobian<S, KIND>(A, G, E);
     } else {
         A.inf = 1;                                     // opposite points
     }
 }
 // A = P + Q, both normalised (mmadd-2008-s: ZZ3 = PP, ZZZ3 = PPP)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __device__ __forceinline__ void ptx_mmadd(PtX<S>& A, const Pt<S>& P, const Pt<S>& Q, const ECDev& E) {
     u32 Pd[S], Rd[S];
     f_sub<S, true>(Pd, Q.X, P.X, E);
     f_sub<S, true>(Rd, Q.Y, P.Y, E);
-    const bool hz = f_maybe_zero<S>(Pd) && f_is_zero<S>(Pd, E);
+    const bool hz = f_maybe_zero<S, KIND>(Pd) && f_is_zero<S, KIND>(Pd, E);
     const bool special = P.inf || Q.inf || hz;
     if (!special) {
-        ptx_tail<S>(A.X, A.Y, A.ZZ, A.ZZZ, Pd, Rd, P.X, P.Y, E);
+        ptx_tail<S, KIND>(A.X, A.Y, A.ZZ, A.ZZZ, Pd, Rd, P.X, P.Y, E);
         A.inf = 0;
     } else if (P.inf) {
         ptx_from_normalised<S>(A, Q, E);
     } else if (Q.inf) {
         ptx_from_normalised<S>(A, P, E);
-    } else if (f_is_zero<S>(Rd, E)) {
+    } else if (f_is_zero<S, KIND>(Rd, E)) {
         Pt<S> D, G;
 #pragma unroll
         for (int j = 0; j < S; ++j) {
@@ -788,8 +865,8 @@ __device__ __forceinline__ void ptx_mmadd(PtX<S>& A, const Pt<S>& P, const Pt<S>
             D.Z[j] = E.one[j];
         }
         D.inf = 0;
-        pt_dbl<S>(G, D, E);
-        ptx_from_jacobian<S>(A, G, E);
+        pt_dbl<S, KIND>(G, D, E);
+        ptx_from_jacobian<S, KIND>(A, G, E);
     } else {
         ptx_from_normalised<S>(A, P, E);               // (any finite coordinates: the flag is what counts)
         A.inf = 1;
@@ -801,7 +878,7 @@ __device__ __forceinline__ void ptx_mmadd(PtX<S>& A, const Pt<S>& P, const Pt<S>
 // ---------------------------------------------------------------------------------------------
 // big-endian x || y (nbytes each; all 0xff = infinity) -> rows.  flags |= 1: coordinate >= p or point not on the
 // curve (replaced by the identity, the reference's "trivial value" convention).
-template <int S, int NW>
+template <int S, int NW, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK) k_ec_import(u32* __restrict__ out, const uint8_t* __restrict__ be, size_t nbytes,
                                                      size_t stride, int framed, size_t n, ECDev E, u32* __restrict__ flags) {
     // framed: every point is the byte tree node(leaf(x), leaf(y)) = 00 00000002 | 01 len x | 01 len y (the form VCR gives a
@@ -847,30 +924,40 @@ __global__ void __launch_bounds__(BLOCK) k_ec_import(u32* __restrict__ out, cons
         u32 rrc[S];
 #pragma unroll
         for (int j = 0; j < S; ++j) rrc[j] = E.rr[j];
-        f_mul<S>(P.X, x, rrc, E);
-        f_mul<S>(P.Y, y, rrc, E);
+        f_mul<S, false, KIND>(P.X, x, rrc, E);
+        f_mul<S, false, KIND>(P.Y, y, rrc, E);
 #pragma unroll
         for (int j = 0; j < S; ++j) P.Z[j] = E.one[j];
         P.inf = 0;
-        // on the curve?  y^2 == x^3 - 3x + b
+        // on the curve?  y^2 == x^3 - 3x + b  (EC_GENERAL: x^3 + a x + b)
         u32 lhs[S], t[S], x3[S], rhs[S], bb[S];
 #pragma unroll
         for (int j = 0; j < S; ++j) bb[j] = E.b[j];
-        f_sqr<S>(lhs, P.Y, E);
-        f_sqr<S>(t, P.X, E);
-        f_mul<S>(x3, t, P.X, E);
-        f_small<S, 3>(t, P.X);
-        f_add<S>(rhs, x3, bb);
-        f_sub<S>(rhs, rhs, t, E);                       // < 4p + 64p
-        f_sub<S, true>(t, lhs, rhs, E);                 // subtrahend up to 68p: the 256p form
-        bad = bad || !f_is_zero<S>(t, E);
+        f_sqr<S, false, KIND>(lhs, P.Y, E);
+        f_sqr<S, false, KIND>(t, P.X, E);
+        f_mul<S, false, KIND>(x3, t, P.X, E);
+        if constexpr (KIND == EC_GENERAL) {
+            u32 aa[S];
+#pragma unroll
+            for (int j = 0; j < S; ++j) aa[j] = E.a[j];
+            f_mul<S, false, KIND>(t, aa, P.X, E);
+            f_add<S>(rhs, x3, bb);
+            f_add<S>(rhs, rhs, t);                      // < 5p
+            f_sub<S>(t, lhs, rhs, E);
+        } else {
+            f_small<S, 3>(t, P.X);
+            f_add<S>(rhs, x3, bb);
+            f_sub<S>(rhs, rhs, t, E);                       // < 4p + 64p
+            f_sub<S, true>(t, lhs, rhs, E);                 // subtrahend up to 68p: the 256p form
+        }
+        bad = bad || !f_is_zero<S, KIND>(t, E);
         if (bad) pt_set_inf<S>(P, E);
     }
     if (bad) atomicOr(flags, 1u);
     pt_store<S>(out + el * ROW, P);
 }
 
-template <int S, int NW>
+template <int S, int NW, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK) k_ec_export(uint8_t* __restrict__ be, size_t nbytes, size_t stride, int framed,
                                                      const u32* __restrict__ in, size_t n, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
@@ -909,18 +996,18 @@ __global__ void __launch_bounds__(BLOCK) k_ec_export(uint8_t* __restrict__ be, s
         }
     } else {                                           // one Fermat power per point: ~380 products where the rest of the export is 5
         u32 zi[S], zi2[S], zi3[S];
-        f_inv<S>(zi, P.Z, E);
-        f_sqr<S>(zi2, zi, E);
-        f_mul<S>(zi3, zi2, zi, E);
-        f_mul<S>(xa, P.X, zi2, E);
-        f_mul<S>(ya, P.Y, zi3, E);
+        f_inv<S, KIND>(zi, P.Z, E);
+        f_sqr<S, false, KIND>(zi2, zi, E);
+        f_mul<S, false, KIND>(zi3, zi2, zi, E);
+        f_mul<S, false, KIND>(xa, P.X, zi2, E);
+        f_mul<S, false, KIND>(ya, P.Y, zi3, E);
     }
 #pragma unroll
     for (int j = 0; j < S; ++j) one1[j] = j == 0 ? 1u : 0u;
     // leave the Montgomery domain (multiply by 1) and canonicalise
     auto out_coord = [&](const u32 (&v)[S], uint8_t* d) {
         u32 s[S], c[S], w[NW];
-        f_mul<S>(s, v, one1, E);                       // v / R : standard representative, < 2p
+        f_mul<S, false, KIND>(s, v, one1, E);          // v / R : standard representative, < 2p
         int32_t borrow = 0;
 #pragma unroll
         for (int j = 0; j < S; ++j) {
@@ -940,7 +1027,7 @@ __global__ void __launch_bounds__(BLOCK) k_ec_export(uint8_t* __restrict__ be, s
 }
 
 // K4: out[i] = x[i] + y[i]   (ystride = 0: one shared point)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_add(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ y,
                                                   size_t ystride, size_t n, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
@@ -949,12 +1036,12 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_add(u32* __restrict
     Pt<S> P, Q, R;
     pt_load<S>(P, x + el * ROW);
     pt_load<S>(Q, y + el * ystride);
-    pt_add<S>(R, P, Q, E);
+    pt_add<S, KIND>(R, P, Q, E);
     pt_store<S>(out + el * ROW, R);
 }
 
 // inverse of every element: (X, -Y, Z)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK) k_ec_neg(u32* __restrict__ out, const u32* __restrict__ x, size_t n, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
     size_t el = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -971,7 +1058,7 @@ __global__ void __launch_bounds__(BLOCK) k_ec_neg(u32* __restrict__ out, const u
 }
 
 // K6: flags |= 1 where x[i] != y[i] as group elements (cross-multiplied Jacobian comparison)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK) k_ec_equal(const u32* __restrict__ x, const u32* __restrict__ y, size_t n, ECDev E,
                                                     u32* __restrict__ flags) {
     constexpr int ROW = ECfg<S>::ROW;
@@ -985,24 +1072,24 @@ __global__ void __launch_bounds__(BLOCK) k_ec_equal(const u32* __restrict__ x, c
         eq = P.inf && Q.inf;
     } else {
         u32 a[S], b[S], c[S], d[S], t[S];
-        f_sqr<S>(a, P.Z, E);
-        f_sqr<S>(b, Q.Z, E);
-        f_mul<S>(c, P.X, b, E);
-        f_mul<S>(d, Q.X, a, E);
+        f_sqr<S, false, KIND>(a, P.Z, E);
+        f_sqr<S, false, KIND>(b, Q.Z, E);
+        f_mul<S, false, KIND>(c, P.X, b, E);
+        f_mul<S, false, KIND>(d, Q.X, a, E);
         f_sub<S>(t, c, d, E);
-        eq = f_is_zero<S>(t, E);
-        f_mul<S>(c, a, P.Z, E);
-        f_mul<S>(d, b, Q.Z, E);
-        f_mul<S>(a, P.Y, d, E);
-        f_mul<S>(b, Q.Y, c, E);
+        eq = f_is_zero<S, KIND>(t, E);
+        f_mul<S, false, KIND>(c, a, P.Z, E);
+        f_mul<S, false, KIND>(d, b, Q.Z, E);
+        f_mul<S, false, KIND>(a, P.Y, d, E);
+        f_mul<S, false, KIND>(b, Q.Y, c, E);
         f_sub<S>(t, a, b, E);
-        eq = eq && f_is_zero<S>(t, E);
+        eq = eq && f_is_zero<S, KIND>(t, E);
     }
     if (!eq) atomicOr(flags, 1u);
 }
 
 // K1a / K1b: out[i] = e[i] * x[i]  (fixed window, per-lane table of multiples in scratch)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e,
                                                      int ewords, size_t estride, int ebits, int wbits, size_t n, ECDev E,
                                                      u32* __restrict__ tab) {
@@ -1024,7 +1111,7 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar(u32* __restr
         A = P;
 #pragma unroll 1
         for (int k = 2; k < tsize; ++k) {
-            pt_add<S>(A, A, P, E);
+            pt_add<S, KIND>(A, A, P, E);
             pt_store<S>(mytab + (size_t)k * ROW, A);
         }
         u32 d = exp_digit(ep, ewords, (nwin - 1) * wbits, wbits);
@@ -1032,11 +1119,11 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar(u32* __restr
 #pragma unroll 1
         for (int wi = nwin - 2; wi >= 0; --wi) {
 #pragma unroll 1
-            for (int s = 0; s < wbits; ++s) pt_dbl<S>(A, A, E);
+            for (int s = 0; s < wbits; ++s) pt_dbl<S, KIND>(A, A, E);
             d = exp_digit(ep, ewords, wi * wbits, wbits);
             Pt<S> T;
             pt_load<S>(T, mytab + (size_t)d * ROW);
-            pt_add<S>(A, A, T, E);
+            pt_add<S, KIND>(A, A, T, E);
         }
         if (live) pt_store<S>(out + el * ROW, A);
     }
@@ -1047,7 +1134,7 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar(u32* __restr
 // caller hands in y = -B_shift (a negation is free on a curve).  Fixed windows of wbits bits for both scalars, two per-lane
 // tables in scratch: max(ebits, fbits) doublings + ceil(ebits / w) + ceil(fbits / w) additions + 2 (2^w - 2) for the tables,
 // against twice the doublings of two k_ec_mulvar launches.
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar2(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e,
                                                       int ewords, int ebits, const u32* __restrict__ y, const u32* __restrict__ f,
                                                       int fwords, size_t fstride, int fbits, int wbits, size_t n, ECDev E,
@@ -1076,7 +1163,7 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar2(u32* __rest
             A = P;
 #pragma unroll 1
             for (int k = 2; k < tsize; ++k) {
-                pt_add<S>(A, A, P, E);
+                pt_add<S, KIND>(A, A, P, E);
                 pt_store<S>(mytab + (size_t)k * ROW, A);
             }
         }
@@ -1084,16 +1171,16 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar2(u32* __rest
 #pragma unroll 1
         for (int wi = nwin - 1; wi >= 0; --wi) {
 #pragma unroll 1
-            for (int s = 0; s < wbits; ++s) pt_dbl<S>(A, A, E);      // (infinity stays infinity: the first window costs nothing real)
+            for (int s = 0; s < wbits; ++s) pt_dbl<S, KIND>(A, A, E); // (infinity stays infinity: the first window costs nothing real)
             const u32 de = wi * wbits < ebits ? exp_digit(e, ewords, wi * wbits, wbits) : 0u;
             const u32 df = wi * wbits < fbits ? exp_digit(fp, fwords, wi * wbits, wbits) : 0u;
             Pt<S> T;
             if (de) {                                                // (wave-uniform: e is shared)
                 pt_load<S>(T, tx + (size_t)de * ROW);
-                pt_add<S>(A, A, T, E);
+                pt_add<S, KIND>(A, A, T, E);
             }
             pt_load<S>(T, ty + (size_t)df * ROW);                    // entry 0 is the identity: no branch per lane
-            pt_add<S>(A, A, T, E);
+            pt_add<S, KIND>(A, A, T, E);
         }
         if (live) pt_store<S>(out + el * ROW, A);
     }
@@ -1102,7 +1189,7 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar2(u32* __rest
 // sq[j] = 2^j * base, j < count: the doubling chain of a fixed-base table, one lane (count ~ 256-400 doublings)
 // (launch bounds: without them the compiler budgets registers for 1024 threads per block and the point doubling spills --
 // the chain then took 27 us per doubling instead of 5)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(64) k_ec_chain(u32* __restrict__ sq, const u32* __restrict__ base, int count, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -1110,12 +1197,12 @@ __global__ void __launch_bounds__(64) k_ec_chain(u32* __restrict__ sq, const u32
     pt_load<S>(A, base);
     for (int j = 0; j < count; ++j) {
         pt_store<S>(sq + (size_t)j * ROW, A);
-        pt_dbl<S>(A, A, E);
+        pt_dbl<S, KIND>(A, A, E);
     }
 }
 
 // K2 table level l: T[k][2^l + r] = T[k][r] + T[k][2^l]
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_fixed_level(u32* __restrict__ T, int w, int nwin, int l, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
     size_t per = ((size_t)1 << l) - 1;
@@ -1126,12 +1213,12 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_fixed_level(u32* __
     Pt<S> A, B, R;
     pt_load<S>(A, row + r * ROW);
     pt_load<S>(B, row + ((size_t)1 << l) * ROW);
-    pt_add<S>(R, A, B, E);
+    pt_add<S, KIND>(R, A, B, E);
     pt_store<S>(row + (((size_t)1 << l) + r) * ROW, R);
 }
 
 // K2: out[i] = sum_k T[k][digit_k(e[i])]
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW_RUN) k_ec_fixed_exp(u32* __restrict__ out, const u32* __restrict__ T, int w, int nwin,
                                                         const u32* __restrict__ e, int ewords, size_t n, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
@@ -1148,9 +1235,9 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW_RUN) k_ec_fixed_exp(u32* 
         for (int k = 1; k < nwin; ++k) {
             d = exp_digit(ep, ewords, k * w, w);
             pt_load_normalised<S>(B, T + (((size_t)k << w) + d) * ROW);
-            ptx_madd<S>(R, B, E);
+            ptx_madd<S, KIND>(R, B, E);
         }
-        ptx_to_jacobian<S>(A, R, E);
+        ptx_to_jacobian<S, KIND>(A, R, E);
     }
     pt_store<S>(out + el * ROW, A);
 }
@@ -1192,7 +1279,7 @@ __device__ __forceinline__ void z_of_row(u32 (&z)[S], const u32* __restrict__ ro
 // The k arrays of one call go through the two ROW-level kernels in ONE launch (block b works for array b / blocks_per_array,
 // as in k_ec_bucket_level): a lane's chunk is a chain of K dependent load + product steps, so a launch lasts one chain whatever
 // its size -- seven launches of a third of the device each were seven chains in a row (round 4: 4.1 -> 1.6 ms per pass of configs[4]).
-template <int S, bool ROWS>
+template <int S, bool ROWS, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_finv_up(u32* __restrict__ pref, u32* __restrict__ tot, LevelInputs vs,
                                                                   unsigned blocks_per_array, size_t n, size_t K, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW, FW = ECfg<S>::FW;
@@ -1218,25 +1305,25 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_finv_up(u32* __restric
         const size_t nx = i + nl < n ? i + nl : i;     // (the last step fetches its own value again)
         fetch(zn, nx);
         f_store<S>(pref + i * FW, acc);
-        f_mul<S>(acc, acc, z, E);
+        f_mul<S, false, KIND>(acc, acc, z, E);
 #pragma unroll
         for (int j = 0; j < S; ++j) z[j] = zn[j];
     }
     f_store<S>(tot + c * FW, acc);
 }
 // top: inv[i] = 1 / v[i] by Fermat
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_finv_top(u32* __restrict__ inv, const u32* __restrict__ v, size_t n, ECDev E) {
     constexpr int FW = ECfg<S>::FW;
     size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     u32 a[S], r[S];
     f_load<S>(a, v + i * FW);
-    f_inv<S>(r, a, E);
+    f_inv<S, KIND>(r, a, E);
     f_store<S>(inv + i * FW, r);
 }
 // down: inv[i] = 1 / v[i] from invtot[c] = 1 / (the product of chunk c)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_finv_down(u32* __restrict__ inv, const u32* __restrict__ invtot, const u32* __restrict__ pref,
                                                                     const u32* __restrict__ v, size_t n, size_t K, ECDev E) {
     constexpr int FW = ECfg<S>::FW;
@@ -1249,14 +1336,14 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_finv_down(u32* __restr
     for (size_t k = cnt; k-- > 0;) {
         const size_t i = c + k * nl;
         f_load<S>(pr, pref + i * FW);
-        f_mul<S>(zi, run, pr, E);
+        f_mul<S, false, KIND>(zi, run, pr, E);
         f_load<S>(z, v + i * FW);
-        f_mul<S>(run, run, z, E);
+        f_mul<S, false, KIND>(run, run, z, E);
         f_store<S>(inv + i * FW, zi);
     }
 }
 // the lowest level, fused with the use of the inverses: out[i] = (X zi^2, Y zi^3, 1)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_normalize_down(u32* __restrict__ out, LevelInputs ins, unsigned blocks_per_array,
                                                                             const u32* __restrict__ invtot, const u32* __restrict__ pref,
                                                                             size_t n, size_t K, ECDev E) {
@@ -1286,15 +1373,15 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_normalize_down(u32*
         f_load<S>(prn, pref + nx * FW);
         pt_load<S>(Pn, in + nx * ROW);
         u32 zi[S], zi2[S], zi3[S];
-        f_mul<S>(zi, run, pr, E);                      // 1 / Z_i
+        f_mul<S, false, KIND>(zi, run, pr, E);         // 1 / Z_i
         if (P.inf) {
             pt_set_inf<S>(P, E);                       // (took part with Z = 1: the running inverse is unchanged)
         } else {
-            f_mul<S>(run, run, P.Z, E);
-            f_sqr<S>(zi2, zi, E);
-            f_mul<S>(zi3, zi2, zi, E);
-            f_mul<S>(P.X, P.X, zi2, E);
-            f_mul<S>(P.Y, P.Y, zi3, E);
+            f_mul<S, false, KIND>(run, run, P.Z, E);
+            f_sqr<S, false, KIND>(zi2, zi, E);
+            f_mul<S, false, KIND>(zi3, zi2, zi, E);
+            f_mul<S, false, KIND>(P.X, P.X, zi2, E);
+            f_mul<S, false, KIND>(P.Y, P.Y, zi3, E);
 #pragma unroll
             for (int j = 0; j < S; ++j) P.Z[j] = E.one[j];
         }
@@ -1307,7 +1394,7 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_normalize_down(u32*
 
 // K3 product-tree level (see k_bucket_level, also for the arrays of one launch).  FIRST: the inputs are NORMALISED arrays
 // (k_ec_normalize), read through `sorted`.
-template <int S, bool FIRST>
+template <int S, bool FIRST, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, FIRST ? ECfg<S>::MINW_RUN : ECfg<S>::MINW) k_ec_bucket_level(u32* __restrict__ out, size_t out_stride, LevelInputs ins,
                                                            unsigned blocks_per_array,
                                                            const u32* __restrict__ sorted, const u32* __restrict__ off_in,
@@ -1343,21 +1430,21 @@ __global__ void __launch_bounds__(BLOCK, FIRST ? ECfg<S>::MINW_RUN : ECfg<S>::MI
             PtX<S> R;
             pt_load_normalised<S>(B, row(k0));
             if (sorted[k0] >> 31) f_neg<S>(B.Y, B.Y, E);
-            ptx_mmadd<S>(R, A, B, E);
+            ptx_mmadd<S, KIND>(R, A, B, E);
             // (Running one row ahead of the addition -- the index and the row of k + 1 in flight while row k is added -- was
             // measured and changes nothing, profiles/r04_ec_instruction_diet.txt: the other wave of the SIMD already hides the
             // gather; the kernel is bound by the instructions it issues.)
             for (u32 k = k0 + 1; k < end; ++k) {
                 pt_load_normalised<S>(B, row(k));
                 if (sorted[k] >> 31) f_neg<S>(B.Y, B.Y, E);
-                ptx_madd<S>(R, B, E);
+                ptx_madd<S, KIND>(R, B, E);
             }
-            ptx_to_jacobian<S>(A, R, E);
+            ptx_to_jacobian<S, KIND>(A, R, E);
         }
     } else {
         for (u32 k = k0; k < end; ++k) {
             pt_load<S>(B, row(k));
-            pt_add<S>(A, A, B, E);
+            pt_add<S, KIND>(A, A, B, E);
         }
     }
     pt_store<S>(out + t * ROW, A);
@@ -1366,7 +1453,7 @@ __global__ void __launch_bounds__(BLOCK, FIRST ? ECfg<S>::MINW_RUN : ECfg<S>::MI
 // The first level over rows that are NOT normalised (small calls, vmnhip.hip ec_normalise_pays): the gather through `sorted` and
 // the signs of k_ec_bucket_level<S, true>, full additions.  Normalising costs a fixed chain of launches with one Fermat power
 // at its top (~0.3 ms per call whatever the size); below ~10^5 points the dearer additions are cheaper than that.
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_bucket_first_jacobian(u32* __restrict__ out, size_t out_stride, LevelInputs ins,
                                                            unsigned blocks_per_array,
                                                            const u32* __restrict__ sorted, const u32* __restrict__ off_in,
@@ -1404,13 +1491,13 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_bucket_first_jacobi
     load_signed(A, start);
     for (u32 k = start + 1; k < end; ++k) {
         load_signed(B, k);
-        pt_add<S>(A, A, B, E);
+        pt_add<S, KIND>(A, A, B, E);
     }
     pt_store<S>(out + t * ROW, A);
 }
 
 // K5: strided sum (see k_reduce_strided)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_reduce(u32* __restrict__ out, const u32* __restrict__ x, size_t len, size_t Lout,
                                                      size_t nseg, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
@@ -1423,13 +1510,13 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_reduce(u32* __restr
     size_t cnt = (len - j + Lout - 1) / Lout;
     for (size_t k = 1; k < cnt; ++k) {
         pt_load<S>(B, base + (j + k * Lout) * ROW);
-        pt_add<S>(A, A, B, E);
+        pt_add<S, KIND>(A, A, B, E);
     }
     pt_store<S>(out + t * ROW, A);
 }
 
 // running sums (the "prods" scan of the modular kernels with + as the operation)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_scan_totals(u32* __restrict__ tot, const u32* __restrict__ e, size_t n, size_t Cc,
                                                           size_t seglen, int rev, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
@@ -1442,11 +1529,11 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_scan_totals(u32* __
     for (size_t i = lo; i < hi; ++i) {
         size_t pos = rev ? (i / seglen) * seglen + (seglen - 1 - i % seglen) : i;
         pt_load<S>(B, e + pos * ROW);
-        pt_add<S>(A, A, B, E);
+        pt_add<S, KIND>(A, A, B, E);
     }
     pt_store<S>(tot + c * ROW, A);
 }
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_scan_apply(u32* __restrict__ out, const u32* __restrict__ e,
                                                          const u32* __restrict__ incoming, size_t n, size_t Cc, size_t seglen,
                                                          int rev, ECDev E) {
@@ -1462,14 +1549,14 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_scan_apply(u32* __r
     for (size_t i = lo; i < hi; ++i) {
         size_t pos = rev ? (i / seglen) * seglen + (seglen - 1 - i % seglen) : i;
         pt_load<S>(B, e + pos * ROW);
-        pt_add<S>(A, A, B, E);
+        pt_add<S, KIND>(A, A, B, E);
         pt_store<S>(out + pos * ROW, A);
     }
 }
 
 // Horner over the window results of a multi-exponentiation: out[a] = sum_w 2^(c w) W[a][w]; one lane per array
 // (the chain of c * nwin doublings is sequential, so the k arrays of a multi-array call share its latency)
-template <int S>
+template <int S, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK) k_ec_horner(u32* __restrict__ out, const u32* __restrict__ wres, int nwin, int c, int k, ECDev E) {
     constexpr int ROW = ECfg<S>::ROW;
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1478,9 +1565,9 @@ __global__ void __launch_bounds__(BLOCK) k_ec_horner(u32* __restrict__ out, cons
     Pt<S> A, B;
     pt_set_inf<S>(A, E);
     for (int w = nwin - 1; w >= 0; --w) {
-        for (int s = 0; s < c; ++s) pt_dbl<S>(A, A, E);
+        for (int s = 0; s < c; ++s) pt_dbl<S, KIND>(A, A, E);
         pt_load<S>(B, wa + (size_t)w * ROW);
-        pt_add<S>(A, A, B, E);
+        pt_add<S, KIND>(A, A, B, E);
     }
     pt_store<S>(out + (size_t)a * ROW, A);
 }

@@ -6,12 +6,13 @@
 namespace vmn {
 namespace num64 {
 
-// Short Weierstrass, a = -3, Jacobian coordinates over
+// Short Weierstrass, y^2 = x^3 + a x + b (a = -3 unless `a` is set), Jacobian coordinates over
 // the Montgomery form of Mod.  Points cross as x || y (infinity = all 0xff), the encoding of include/vmnhip.h.
 // Inputs are points the GPU import has validated (see check_elements) or results of this code.
 struct HostCurve {
     const Mod* F = nullptr;
     size_t cb = 0, fl = 0;                         // coordinate bytes, field limbs
+    Num a;                                         // the coefficient a in Montgomery form; empty: a = -3 (the NIST curves)
     struct Jac {
         Num X, Y, Z;
         bool inf = true;
@@ -41,8 +42,21 @@ struct HostCurve {
         to_be(y, out.data() + cb, cb);
         return out;
     }
-    Jac dbl(const Jac& P) const {                                // dbl-2001-b
+    Jac dbl(const Jac& P) const {                                // dbl-2001-b (a = -3), dbl-2007-bl (any a)
         if (P.inf || is_zero(P.Y)) return Jac();
+        if (!a.empty()) {
+            Num XX = mul(P.X, P.X), YY = mul(P.Y, P.Y), YYYY = mul(YY, YY), ZZ = mul(P.Z, P.Z);
+            Num xy = F->add(P.X, YY);
+            Num S = twice(sub(sub(mul(xy, xy), XX), YYYY));
+            Num M = F->add(F->add(twice(XX), XX), mul(a, mul(ZZ, ZZ)));
+            Jac R;
+            R.inf = false;
+            R.X = sub(mul(M, M), twice(S));
+            R.Y = sub(mul(M, sub(S, R.X)), twice(twice(twice(YYYY))));
+            Num yz = F->add(P.Y, P.Z);
+            R.Z = sub(sub(mul(yz, yz), YY), ZZ);
+            return R;
+        }
         Num delta = mul(P.Z, P.Z), gamma = mul(P.Y, P.Y), beta = mul(P.X, gamma);
         Num t = mul(sub(P.X, delta), F->add(P.X, delta));
         Num alpha = F->add(twice(t), t);

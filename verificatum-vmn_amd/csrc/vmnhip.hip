@@ -33,6 +33,11 @@ VMN_UNIT_P224(extern template)
 VMN_UNIT_P256(extern template)
 VMN_UNIT_P384(extern template)
 VMN_UNIT_P521(extern template)
+VMN_UNIT_G9(extern template)
+VMN_UNIT_G10(extern template)
+VMN_UNIT_G13(extern template)
+VMN_UNIT_G15(extern template)
+VMN_UNIT_G21(extern template)
 
 using namespace vmn;
 using vmn::hostbig::Big;
@@ -74,9 +79,10 @@ extern "C" const char* vmn_version(void) { return "vmnhip 0.1 (gfx950, radix-2^2
 // demo/mixnet/.conf:189-195, and benchmarks with a 15 492-bit group, benchmarks/bench_config:43): eight / sixteen lanes per
 // element, the same kernels; built for completeness, outside north_star's 2048-4096 range and not tuned.
 #define VMN_FOR_SIZES(X) X(10, 8, 1) X(14, 12, 1) X(19, 16, 1) X(37, 32, 1) X(74, 64, 1) X(76, 64, 4) X(80, 64, 8) X(110, 96, 2) X(112, 96, 4) X(148, 128, 4) X(296, 256, 8) X(592, 512, 16)
-// elliptic curves: X(field limbs, packed words)
+// elliptic curves: X(field limbs, packed words, kind) -- ec_kernels.h: EC_NIST (a = -3) and EC_GENERAL (any a, any prime)
 // (field limbs are chosen so that R/p >= 2^24: the lazy operand bounds of the point formulas need it)
-#define VMN_FOR_CURVES(X) X(9, 7) X(10, 8) X(15, 12) X(21, 17)
+#define VMN_FOR_CURVES(X) X(9, 7, EC_NIST) X(10, 8, EC_NIST) X(15, 12, EC_NIST) X(21, 17, EC_NIST) \
+    X(9, 7, EC_GENERAL) X(10, 8, EC_GENERAL) X(13, 10, EC_GENERAL) X(15, 12, EC_GENERAL) X(21, 17, EC_GENERAL)
 
 static bool size_for_bits(int nbits, int* S, int* NW, int* LPE) {
     const int sizes[][4] = {{256, 10, 8, 1}, {384, 14, 12, 1}, {512, 19, 16, 1}, {1024, 37, 32, 1}, {2048, 74, 64, 1},
@@ -193,8 +199,10 @@ static int note_work(vmn_ctx* ctx, const vmn_modulus& m, double products, double
                       squarings * (m.ec ? 2 * s32 * s32 + s32 : s32 * (s32 + 1) / 2 + s32 * s32 + s32);
     if (m.ec) {
         // a field product: S^2 for the multiplication half + S x (non-zero limbs of p, less limb 0 whose carry is folded into
-        // column 1) for the reduction rows of the compile-time primes (ec_kernels.h mont_row: 6 of 10 for P-256, 12 of 15 for P-384)
-        const double nz = m.ec->S == 10 ? 7 : m.ec->S == 15 ? 12 : S;       // (P-256: 6 limbs + the carry product of the wide-digit rows)
+        // column 1) for the reduction rows of the compile-time primes (ec_kernels.h mont_row: 6 of 10 for P-256, 12 of 15 for P-384;
+        // the EC_GENERAL kernels take every prime at run time: S)
+        const bool known = m.ec->kind == EC_NIST;
+        const double nz = known && m.ec->S == 10 ? 7 : known && m.ec->S == 15 ? 12 : S;   // (P-256: 6 limbs + the carry product of the wide-digit rows)
         ctx->next_mads = (products + squarings) * (S * S + S * nz);
         return 0;
     }
@@ -917,6 +925,11 @@ extern "C" int vmn_group_get_modulus(const vmn_group* grp, uint8_t* p_be) {
     hostbig::to_be(grp->curve ? grp->curve->p_words : grp->P.n_words, p_be, grp->nbytes);
     return VMN_OK;
 }
+extern "C" int vmn_group_get_curve_a(const vmn_group* grp, uint8_t* a_be) {
+    ARG_CHECK(grp && grp->curve && a_be, "null argument or not a curve group");
+    hostbig::to_be(grp->curve->a_words, a_be, grp->nbytes);
+    return VMN_OK;
+}
 extern "C" int vmn_group_get_generator(const vmn_group* grp, uint8_t* g_be) {
     ARG_CHECK(grp && g_be, "null argument");
     if (grp->curve) {
@@ -950,6 +963,8 @@ static ECDev ecdev(const vmn_curve* c) {
     E.ts_ewords = c->ts_ewords;
     E.ts_e = c->d_ts_e;
     E.ts_c = c->d_ts_c;
+    E.a = c->d_a;
+    E.a_zero = c->a_zero;
     return E;
 }
 
@@ -963,6 +978,7 @@ struct CurveParams {
     const char* b;
     const char* gx;
     const char* gy;
+    const char* a = nullptr;   // curve coefficient a (absent: a = -3, the NIST curves)
 };
 static const CurveParams kCurves[] = {
     {"P-224", 224, 9, 7, "ffffffffffffffffffffffffffffffff000000000000000000000001",
@@ -988,6 +1004,120 @@ static const CurveParams kCurves[] = {
      "0051953eb9618e1c9a1f929a21a0b68540eea2da725b99b315f3b8b489918ef109e156193951ec7e937b1652c0bd3bb1bf073573df883d2c34f1ef451fd46b503f00",
      "00c6858e06b70404e9cd9e3ecb662395b4429c648139053fb521f828af606b4d3dbaa14b5e77efe75928fe1dc127a2ffa8de3348b3c1856a429bf97e7e31c2e5bd66",
      "011839296a789a3bc0045c8a5fb42c7d1bd998f54449579b446817afbd17273e662c97ee72995ef42640c550b9013fad0761353c7086a272c24088be94769fd16650"},
+    // The other named curves of the reference (demo/mixnet/.conf:151-176), constants as libcrypto has them; every one has
+    // cofactor 1.  An entry without `a` (a = -3: P-192, prime192v2 / v3) runs on the EC_NIST kernels -- the 9-limb ones of
+    // P-224 take their prime at run time, and dbl-2001-b is cheaper than the general doubling by a product or two.  An entry
+    // that names its `a` runs on the EC_GENERAL kernels: brainpool, secp*k1 (a = 0), and prime239v1-3, whose a is -3 but whose
+    // 10-limb primes are not the one the EC_NIST kernels of that size have compiled in (P-256).
+    {"P-192", 192, 9, 7,
+     "fffffffffffffffffffffffffffffffeffffffffffffffff",
+     "ffffffffffffffffffffffff99def836146bc9b1b4d22831",
+     "64210519e59c80e70fa7e9ab72243049feb8deecc146b9b1",
+     "188da80eb03090f67cbf20eb43a18800f4ff0afd82ff1012",
+     "07192b95ffc8da78631011ed6b24cdd573f977a11e794811"},
+    {"brainpoolp192r1", 192, 9, 7,
+     "c302f41d932a36cda7a3463093d18db78fce476de1a86297",
+     "c302f41d932a36cda7a3462f9e9e916b5be8f1029ac4acc1",
+     "469a28ef7c28cca3dc721d044f4496bcca7ef4146fbf25c9",
+     "c0a0647eaab6a48753b033c56cb0f0900a2f5c4853375fd6",
+     "14b690866abd5bb88b5f4828c1490002e6773fa2fa299b8f",
+     "6a91174076b1e0e19c39c031fe8685c1cae040e5c69a28ef"},
+    {"brainpoolp224r1", 224, 9, 7,
+     "d7c134aa264366862a18302575d1d787b09f075797da89f57ec8c0ff",
+     "d7c134aa264366862a18302575d0fb98d116bc4b6ddebca3a5a7939f",
+     "2580f63ccfe44138870713b1a92369e33e2135d266dbb372386c400b",
+     "0d9029ad2c7e5cf4340823b2a87dc68c9e4ce3174c1e6efdee12c07d",
+     "58aa56f772c0726f24c6b89e4ecdac24354b9e99caa3f6d3761402cd",
+     "68a5e62ca9ce6c1c299803a6c1530b514e182ad8b0042a59cad29f43"},
+    {"brainpoolp256r1", 256, 10, 8,
+     "a9fb57dba1eea9bc3e660a909d838d726e3bf623d52620282013481d1f6e5377",
+     "a9fb57dba1eea9bc3e660a909d838d718c397aa3b561a6f7901e0e82974856a7",
+     "26dc5c6ce94a4b44f330b5d9bbd77cbf958416295cf7e1ce6bccdc18ff8c07b6",
+     "8bd2aeb9cb7e57cb2c4b482ffc81b7afb9de27e1e3bd23c23a4453bd9ace3262",
+     "547ef835c3dac4fd97f8461a14611dc9c27745132ded8e545c1d54c72f046997",
+     "7d5a0975fc2c3057eef67530417affe7fb8055c126dc5c6ce94a4b44f330b5d9"},
+    {"brainpoolp320r1", 320, 13, 10,
+     "d35e472036bc4fb7e13c785ed201e065f98fcfa6f6f40def4f92b9ec7893ec28fcd412b1f1b32e27",
+     "d35e472036bc4fb7e13c785ed201e065f98fcfa5b68f12a32d482ec7ee8658e98691555b44c59311",
+     "520883949dfdbc42d3ad198640688a6fe13f41349554b49acc31dccd884539816f5eb4ac8fb1f1a6",
+     "43bd7e9afb53d8b85289bcc48ee5bfe6f20137d10a087eb6e7871e2a10a599c710af8d0d39e20611",
+     "14fdd05545ec1cc8ab4093247f77275e0743ffed117182eaa9c77877aaac6ac7d35245d1692e8ee1",
+     "3ee30b568fbab0f883ccebd46d3f3bb8a2a73513f5eb79da66190eb085ffa9f492f375a97d860eb4"},
+    {"brainpoolp384r1", 384, 15, 12,
+     "8cb91e82a3386d280f5d6f7e50e641df152f7109ed5456b412b1da197fb71123acd3a729901d1a71874700133107ec53",
+     "8cb91e82a3386d280f5d6f7e50e641df152f7109ed5456b31f166e6cac0425a7cf3ab6af6b7fc3103b883202e9046565",
+     "04a8c7dd22ce28268b39b55416f0447c2fb77de107dcd2a62e880ea53eeb62d57cb4390295dbc9943ab78696fa504c11",
+     "1d1c64f068cf45ffa2a63a81b7c13f6b8847a3e77ef14fe3db7fcafe0cbd10e8e826e03436d646aaef87b2e247d4af1e",
+     "8abe1d7520f9c2a45cb1eb8e95cfd55262b70b29feec5864e19c054ff99129280e4646217791811142820341263c5315",
+     "7bc382c63d8c150c3c72080ace05afa0c2bea28e4fb22787139165efba91f90f8aa5814a503ad4eb04a8c7dd22ce2826"},
+    {"brainpoolp512r1", 512, 21, 17,
+     "aadd9db8dbe9c48b3fd4e6ae33c9fc07cb308db3b3c9d20ed6639cca703308717d4d9b009bc66842aecda12ae6a380e62881ff2f2d82c68528aa6056583a48f3",
+     "aadd9db8dbe9c48b3fd4e6ae33c9fc07cb308db3b3c9d20ed6639cca70330870553e5c414ca92619418661197fac10471db1d381085ddaddb58796829ca90069",
+     "3df91610a83441caea9863bc2ded5d5aa8253aa10a2ef1c98b9ac8b57f1117a72bf2c7b9e7c1ac4d77fc94cadc083e67984050b75ebae5dd2809bd638016f723",
+     "81aee4bdd82ed9645a21322e9c4c6a9385ed9f70b5d916c1b43b62eef4d0098eff3b1f78e2d0d48d50d1687b93b97d5f7c6d5047406a5e688b352209bcb9f822",
+     "7dde385d566332ecc0eabfa9cf7822fdf209f70024a57b1aa000c55b881f8111b2dcde494a5f485e5bca4bd88a2763aed1ca2b2fa8f0540678cd1e0f3ad80892",
+     "7830a3318b603b89e2327145ac234cc594cbdd8d3df91610a83441caea9863bc2ded5d5aa8253aa10a2ef1c98b9ac8b57f1117a72bf2c7b9e7c1ac4d77fc94ca"},
+    {"prime192v2", 192, 9, 7,
+     "fffffffffffffffffffffffffffffffeffffffffffffffff",
+     "fffffffffffffffffffffffe5fb1a724dc80418648d8dd31",
+     "cc22d6dfb95c6b25e49c0d6364a4e5980c393aa21668d953",
+     "eea2bae7e1497842f2de7769cfe9c989c072ad696f48034a",
+     "6574d11d69b6ec7a672bb82a083df2f2b0847de970b2de15"},
+    {"prime192v3", 192, 9, 7,
+     "fffffffffffffffffffffffffffffffeffffffffffffffff",
+     "ffffffffffffffffffffffff7a62d031c83f4294f640ec13",
+     "22123dc2395a05caa7423daeccc94760a7d462256bd56916",
+     "7d29778100c65a1da1783716588dce2b8b4aee8e228f1896",
+     "38a90f22637337334b49dcb66a6dc8f9978aca7648a943b0"},
+    {"prime239v1", 239, 10, 8,
+     "7fffffffffffffffffffffff7fffffffffff8000000000007fffffffffff",
+     "7fffffffffffffffffffffff7fffff9e5e9a9f5d9071fbd1522688909d0b",
+     "6b016c3bdcf18941d0d654921475ca71a9db2fb27d1d37796185c2942c0a",
+     "0ffa963cdca8816ccc33b8642bedf905c3d358573d3f27fbbd3b3cb9aaaf",
+     "7debe8e4e90a5dae6e4054ca530ba04654b36818ce226b39fccb7b02f1ae",
+     "7fffffffffffffffffffffff7fffffffffff8000000000007ffffffffffc"},
+    {"prime239v2", 239, 10, 8,
+     "7fffffffffffffffffffffff7fffffffffff8000000000007fffffffffff",
+     "7fffffffffffffffffffffff800000cfa7e8594377d414c03821bc582063",
+     "617fab6832576cbbfed50d99f0249c3fee58b94ba0038c7ae84c8c832f2c",
+     "38af09d98727705120c921bb5e9e26296a3cdcf2f35757a0eafd87b830e7",
+     "5b0125e4dbea0ec7206da0fc01d9b081329fb555de6ef460237dff8be4ba",
+     "7fffffffffffffffffffffff7fffffffffff8000000000007ffffffffffc"},
+    {"prime239v3", 239, 10, 8,
+     "7fffffffffffffffffffffff7fffffffffff8000000000007fffffffffff",
+     "7fffffffffffffffffffffff7fffff975deb41b3a6057c3c432146526551",
+     "255705fa2a306654b1f4cb03d6a750a30c250102d4988717d9ba15ab6d3e",
+     "6768ae8e18bb92cfcf005c949aa2c6d94853d0e660bbf854b1c9505fe95a",
+     "1607e6898f390c06bc1d552bad226f3b6fcfe48b6e818499af18e3ed6cf3",
+     "7fffffffffffffffffffffff7fffffffffff8000000000007ffffffffffc"},
+    {"secp192k1", 192, 9, 7,
+     "fffffffffffffffffffffffffffffffffffffffeffffee37",
+     "fffffffffffffffffffffffe26f2fc170f69466a74defd8d",
+     "000000000000000000000000000000000000000000000003",
+     "db4ff10ec057e9ae26b07d0280b7f4341da5d1b1eae06c7d",
+     "9b2f2f6d9c5628a7844163d015be86344082aa88d95e2f9d",
+     "0"},
+    {"secp224k1", 224, 9, 7,
+     "fffffffffffffffffffffffffffffffffffffffffffffffeffffe56d",
+     "010000000000000000000000000001dce8d2ec6184caf0a971769fb1f7",
+     "00000000000000000000000000000000000000000000000000000005",
+     "a1455b334df099df30fc28a169a467e9e47075a90f7e650eb6b7a45c",
+     "7e089fed7fba344282cafbd6f7e319f7c0b0bd59e2ca4bdb556d61a5",
+     "0"},
+    {"secp256k1", 256, 10, 8,
+     "fffffffffffffffffffffffffffffffffffffffffffffffffffffffefffffc2f",
+     "fffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141",
+     "0000000000000000000000000000000000000000000000000000000000000007",
+     "79be667ef9dcbbac55a06295ce870b07029bfcdb2dce28d959f2815b16f81798",
+     "483ada7726a3c4655da4fbfc0e1108a8fd17b448a68554199c47d08ffb10d4b8",
+     "0"},
+};
+// the other spellings of the reference (and OpenSSL's capitalised brainpool names) -> the entry of kCurves
+static const char* const kCurveAliases[][2] = {
+    {"secp192r1", "P-192"}, {"prime192v1", "P-192"}, {"secp224r1", "P-224"}, {"secp256r1", "P-256"}, {"prime256v1", "P-256"},
+    {"secp384r1", "P-384"}, {"secp521r1", "P-521"},
+    {"brainpoolP192r1", "brainpoolp192r1"}, {"brainpoolP224r1", "brainpoolp224r1"}, {"brainpoolP256r1", "brainpoolp256r1"},
+    {"brainpoolP320r1", "brainpoolp320r1"}, {"brainpoolP384r1", "brainpoolp384r1"}, {"brainpoolP512r1", "brainpoolp512r1"},
 };
 
 static std::vector<uint8_t> hex_to_be(const char* h) {
@@ -1046,11 +1176,26 @@ static int curve_create(vmn_ctx* ctx, const CurveParams& cp, vmn_curve** out) {
     c->b_words = hostbig::from_be(bb.data(), bb.size(), NW);
     c->gx_words = hostbig::from_be(gx.data(), gx.size(), NW);
     c->gy_words = hostbig::from_be(gy.data(), gy.size(), NW);
+    c->kind = cp.a ? EC_GENERAL : EC_NIST;
+    if (cp.a) {
+        auto ab = hex_to_be(cp.a);
+        c->a_words = hostbig::from_be(ab.data(), ab.size(), NW);
+    } else {                                              // a = -3: p - 3
+        c->a_words = c->p_words;
+        Big three(NW, 0);
+        three[0] = 3;
+        hostbig::sub_in(c->a_words, three);
+    }
+    c->a_zero = hostbig::bit_length(c->a_words) == 0;
     c->n0inv = hostbig::neg_inv_pow2(c->p_words[0] & LIMB_MASK, 28);
     c->f64 = new num64::Mod(num64::from_be(pb.data(), pb.size(), (pb.size() + 7) / 8));
     c->host.F = c->f64;
     c->host.cb = ((size_t)cp.bits + 7) / 8;
     c->host.fl = c->f64->nl;
+    if (c->kind == EC_GENERAL) {                          // (empty: a = -3, the host's dbl-2001-b)
+        auto ab = hex_to_be(cp.a);
+        c->host.a = c->f64->to_m(num64::from_be(ab.data(), ab.size(), c->f64->nl));
+    }
     {
         const num64::Mod& F = *c->f64;
         num64::Num two28(F.nl, 0), rd(F.nl, 0);
@@ -1061,7 +1206,7 @@ static int curve_create(vmn_ctx* ctx, const CurveParams& cp, vmn_curve** out) {
     }
     const Big& pw = c->p_words;
     c->p1p = limbs_of(pw, S)[1] + 1;
-    {   // the kernels carry the primes of these two sizes as compile-time constants (ec_kernels.h FieldPrime): same prime?
+    if (c->kind == EC_NIST) {   // the kernels carry the primes of these two sizes as compile-time constants (ec_kernels.h FieldPrime): same prime?
         const std::vector<uint32_t> lim = limbs_of(pw, S);
         bool same = c->n0inv == 1;
         if (S == 10) for (int j = 0; j < S; ++j) same = same && lim[j] == FieldPrime<10>::limb[j];
@@ -1076,6 +1221,7 @@ static int curve_create(vmn_ctx* ctx, const CurveParams& cp, vmn_curve** out) {
     Big r1 = shift_mod(one, 28 * S, pw);                 // R mod p
     Big r2 = shift_mod(r1, 28 * S, pw);                  // R^2 mod p
     Big bm = shift_mod(c->b_words, 28 * S, pw);          // b R mod p
+    Big am = shift_mod(c->a_words, 28 * S, pw);          // a R mod p (canonical: shift_mod reduces every step)
     Big pm2 = pw;
     Big two(NW, 0);
     two[0] = 2;
@@ -1090,6 +1236,7 @@ static int curve_create(vmn_ctx* ctx, const CurveParams& cp, vmn_curve** out) {
     };
     size_t o_p = put(limbs_of(pw, S), FW), o_one = put(limbs_of(r1, S), FW), o_rr = put(limbs_of(r2, S), FW);
     size_t o_b = put(limbs_of(bm, S), FW);
+    size_t o_a = put(limbs_of(am, S), FW);
     size_t o_mp = put(limbs_of(times_small(pw, 64, NW + 1), S), FW);
     size_t o_mp2 = put(limbs_of(times_small(pw, 256, NW + 1), S), FW);
     size_t o_pm2 = put(std::vector<uint32_t>(pm2.begin(), pm2.end()), (NW + 3) & ~3);
@@ -1149,6 +1296,7 @@ static int curve_create(vmn_ctx* ctx, const CurveParams& cp, vmn_curve** out) {
     c->d_one = c->d_consts + o_one;
     c->d_rr = c->d_consts + o_rr;
     c->d_b = c->d_consts + o_b;
+    c->d_a = c->d_consts + o_a;
     c->d_mp = c->d_consts + o_mp;
     c->d_mp2 = c->d_consts + o_mp2;
     c->d_pm2 = c->d_consts + o_pm2;
@@ -1160,25 +1308,32 @@ static int curve_create(vmn_ctx* ctx, const CurveParams& cp, vmn_curve** out) {
 extern "C" int vmn_ec_group_create(vmn_ctx* ctx, const char* curve_name, vmn_group** out) {
     ARG_CHECK(ctx && curve_name && out, "null argument");
     VMN_ENTER(ctx);
+    const char* name = curve_name;
+    for (auto& al : kCurveAliases) {
+        if (strcmp(al[0], curve_name) == 0) name = al[1];
+    }
     const CurveParams* cp = nullptr;
     for (auto& k : kCurves) {
-        if (strcmp(k.name, curve_name) == 0) cp = &k;
+        if (strcmp(k.name, name) == 0) cp = &k;
     }
     if (!cp) {
-        set_error("vmn_ec_group_create: unknown curve %s (known: P-224, P-256, P-384, P-521)", curve_name);
+        set_error("vmn_ec_group_create: unknown curve %s (known: the NIST curves P-192 ... P-521, brainpoolp192r1 ... p512r1, "
+                  "prime192v1-3, prime239v1-3, prime256v1, secp192k1 / r1, secp224k1 / r1, secp256k1 / r1, secp384r1, secp521r1)", curve_name);
         return VMN_ERR_UNSUPPORTED;
     }
+    auto nb = hex_to_be(cp->n);
+    // the exponents' width and the ring's size come from bits(n), not bits(p): secp224k1 has a 225-bit order
+    const int nbits = hostbig::bit_length(hostbig::from_be(nb.data(), nb.size(), (nb.size() + 3) / 4));
     std::unique_ptr<vmn_group> g(new vmn_group());
     g->ctx = ctx;
     g->nbytes = ((size_t)cp->bits + 7) / 8;
-    g->xbytes = g->nbytes;
+    g->xbytes = ((size_t)nbits + 7) / 8;
     vmn_curve* curve = nullptr;
     VMN_TRY(curve_create(ctx, *cp, &curve));
     g->curve = curve;
     // scalars: ordinary residues mod the group order
-    auto nb = hex_to_be(cp->n);
     int S, NW, LPE;
-    size_for_bits(cp->bits, &S, &NW, &LPE);
+    size_for_bits(nbits, &S, &NW, &LPE);
     int rc = modulus_init(ctx, g->Q, nb.data(), nb.size(), S, NW, LPE);
     if (rc != VMN_OK) {
         curve_destroy(curve);
@@ -1251,9 +1406,9 @@ static int import_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const ui
     note_work(ctx, m, (m.ec ? 7.0 : 1.0) * (double)n);
     int rc = VMN_ERR_ARG;
     if (m.ec) {
-#define X(S_, NW_)                                                                                                   \
-    if (m.ec->S == S_)                                                                                               \
-        rc = launch_light(ctx, "import", k_ec_import<S_, NW_>, grid_for(n), d_out, (const uint8_t*)raw.as<uint8_t>(), \
+#define X(S_, NW_, K_)                                                                                               \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                           \
+        rc = launch_light(ctx, "import", k_ec_import<S_, NW_, K_>, grid_for(n), d_out, (const uint8_t*)raw.as<uint8_t>(), \
                           nbytes, stride, leaf_hdr, n, ecdev(m.ec), ctx->flags);
         VMN_FOR_CURVES(X)
 #undef X
@@ -1352,9 +1507,9 @@ static int export_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const ui
     else note_work(ctx, m, m.ec ? 8.0 * (double)n : (double)n, m.ec ? (double)m.nbits * (double)n : 0.0);     // curves: one Fermat inversion per point
     int rc = VMN_ERR_ARG;
     if (m.ec) {
-#define X(S_, NW_)                                                                                               \
-    if (m.ec->S == S_)                                                                                           \
-        rc = launch_light(ctx, "export", k_ec_export<S_, NW_>, grid_for(n), raw.as<uint8_t>(), nbytes, stride,   \
+#define X(S_, NW_, K_)                                                                                           \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                       \
+        rc = launch_light(ctx, "export", k_ec_export<S_, NW_, K_>, grid_for(n), raw.as<uint8_t>(), nbytes, stride, \
                           leaf_hdr | ec_rows_affine, d_in, n, ecdev(m.ec));
         VMN_FOR_CURVES(X)
 #undef X
@@ -1436,8 +1591,8 @@ static int mul_arrays(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* x, con
     note_work(ctx, m, (m.ec ? EC_ADD : 1.0) * (double)n);
     int rc = VMN_ERR_ARG;
     if (m.ec) {
-#define X(S_, NW_) \
-    if (m.ec->S == S_) rc = launch_light(ctx, "modmul", k_ec_add<S_>, grid_for(n), out, x, y, ystride, n, ecdev(m.ec));
+#define X(S_, NW_, K_) \
+    if (m.ec->S == S_ && m.ec->kind == K_) rc = launch_light(ctx, "modmul", k_ec_add<S_, K_>, grid_for(n), out, x, y, ystride, n, ecdev(m.ec));
         VMN_FOR_CURVES(X)
 #undef X
         return rc;
@@ -1488,9 +1643,9 @@ static int modpow_words(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, 
         VMN_TRY(ensure_scratch(ctx, tab_bytes));
         note_work(ctx, m, (double)n * (EC_DBL * ebits + EC_ADD * ((ebits + wb - 1) / wb + (1 << wb))));
         int rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                  \
-    if (m.ec->S == S_)                                                                                              \
-        rc = launch_light(ctx, "modpow", k_ec_mulvar<S_>, grid, out, x, e_words, ewords, estride, ebits, wb, n,      \
+#define X(S_, NW_, K_)                                                                                              \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                          \
+        rc = launch_light(ctx, "modpow", k_ec_mulvar<S_, K_>, grid, out, x, e_words, ewords, estride, ebits, wb, n,  \
                           ecdev(m.ec), reinterpret_cast<uint32_t*>(ctx->scratch));
         VMN_FOR_CURVES(X)
 #undef X
@@ -1939,9 +2094,9 @@ extern "C" int vmn_garray_exp2(const vmn_garray* x, const uint8_t* e_be, size_t 
             const int nw1 = (ebits + wbits - 1) / wbits, nw2 = (fbits + wbits - 1) / wbits;
             note_work(ctx, m, (double)n * (EC_DBL * std::max(ebits, fbits) + EC_ADD * (nw1 + nw2 + 2 * ((1 << wbits) - 2))));
             rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                              \
-    if (m.ec->S == S_)                                                                                                          \
-        rc = launch_light(ctx, "modpow", k_ec_mulvar2<S_>, grid, r->d, (const uint32_t*)x->d, (const uint32_t*)ew.as<uint32_t>(), \
+#define X(S_, NW_, K_)                                                                                                          \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                                      \
+        rc = launch_light(ctx, "modpow", k_ec_mulvar2<S_, K_>, grid, r->d, (const uint32_t*)x->d, (const uint32_t*)ew.as<uint32_t>(), \
                           ewords, ebits, (const uint32_t*)y->d, (const uint32_t*)fw.as<uint32_t>(), g->Q.NW, (size_t)g->Q.NW,     \
                           fbits, wbits, n, ecdev(m.ec), reinterpret_cast<uint32_t*>(ctx->scratch));
             VMN_FOR_CURVES(X)
@@ -2114,8 +2269,8 @@ static int compare_arrays(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* x,
     VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
     if (m.ec) {                        // Jacobian rows: equality of group elements, not of bytes
         int rc = VMN_ERR_ARG;
-#define X(S_, NW_) \
-    if (m.ec->S == S_) rc = launch_light(ctx, "compare", k_ec_equal<S_>, grid_for(n), x, y, n, ecdev(m.ec), ctx->flags);
+#define X(S_, NW_, K_) \
+    if (m.ec->S == S_ && m.ec->kind == K_) rc = launch_light(ctx, "compare", k_ec_equal<S_, K_>, grid_for(n), x, y, n, ecdev(m.ec), ctx->flags);
         VMN_FOR_CURVES(X)
 #undef X
         VMN_TRY(rc);
@@ -2323,8 +2478,8 @@ static int reduce_segments(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* x
         if (mul || m.ec) note_work(ctx, m, (m.ec ? EC_ADD : 1.0) * (double)nseg * (double)(cur - L));
         int rc = VMN_ERR_ARG;
         if (m.ec) {
-#define X(S_, NW_) \
-    if (m.ec->S == S_) rc = launch_light(ctx, "reduce", k_ec_reduce<S_>, grid_for(nseg * L), dst, src, cur, L, nseg, ecdev(m.ec));
+#define X(S_, NW_, K_) \
+    if (m.ec->S == S_ && m.ec->kind == K_) rc = launch_light(ctx, "reduce", k_ec_reduce<S_, K_>, grid_for(nseg * L), dst, src, cur, L, nseg, ecdev(m.ec));
             VMN_FOR_CURVES(X)
 #undef X
         } else {
@@ -2515,9 +2670,9 @@ static int scan_affine(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* e, c
         size_t nchunks = (n + Cc - 1) / Cc;
         int rc = VMN_ERR_ARG;
         if (seglen <= Cc) {
-#define X(S_, NW_)                                                                                                 \
-    if (m.ec->S == S_)                                                                                             \
-        rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_apply<S_>, grid_for(nchunks), out, e, (const uint32_t*)nullptr, n, \
+#define X(S_, NW_, K_)                                                                                             \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                         \
+        rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_apply<S_, K_>, grid_for(nchunks), out, e, (const uint32_t*)nullptr, n, \
                           Cc, seglen, rev, ecdev(m.ec));
             VMN_FOR_CURVES(X)
 #undef X
@@ -2527,17 +2682,17 @@ static int scan_affine(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* e, c
         VMN_TRY(tot.alloc(2 * nchunks * Wd * sizeof(uint32_t)));
         uint32_t* Etot = tot.as<uint32_t>();
         uint32_t* inc = Etot + nchunks * Wd;
-#define X(S_, NW_) \
-    if (m.ec->S == S_) rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_totals<S_>, grid_for(nchunks), Etot, e, n, Cc, seglen, rev, ecdev(m.ec));
+#define X(S_, NW_, K_) \
+    if (m.ec->S == S_ && m.ec->kind == K_) rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_totals<S_, K_>, grid_for(nchunks), Etot, e, n, Cc, seglen, rev, ecdev(m.ec));
         VMN_FOR_CURVES(X)
 #undef X
         VMN_TRY(rc);
         size_t seg_chunks = seglen == n ? nchunks : seglen / Cc;
         VMN_TRY(scan_affine(ctx, m, Etot, nullptr, nchunks, seg_chunks, 0, inc));
         rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                       \
-    if (m.ec->S == S_)                                                                                                   \
-        rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_apply<S_>, grid_for(nchunks), out, e, (const uint32_t*)inc, n, Cc, seglen, \
+#define X(S_, NW_, K_)                                                                                                   \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                               \
+        rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_apply<S_, K_>, grid_for(nchunks), out, e, (const uint32_t*)inc, n, Cc, seglen, \
                           rev, ecdev(m.ec));
         VMN_FOR_CURVES(X)
 #undef X
@@ -2661,8 +2816,8 @@ extern "C" int vmn_garray_inv(const vmn_garray* x, vmn_garray** out) {
     }
     if (m.ec) {
         int rce = VMN_ERR_ARG;
-#define X(S_, NW_) \
-    if (m.ec->S == S_) rce = launch_light(ctx, "modmul", k_ec_neg<S_>, grid_for(n), r->d, (const uint32_t*)x->d, n, ecdev(m.ec));
+#define X(S_, NW_, K_) \
+    if (m.ec->S == S_ && m.ec->kind == K_) rce = launch_light(ctx, "modmul", k_ec_neg<S_, K_>, grid_for(n), r->d, (const uint32_t*)x->d, n, ecdev(m.ec));
         VMN_FOR_CURVES(X)
 #undef X
         if (rce != VMN_OK) {
@@ -2781,11 +2936,11 @@ __global__ void __launch_bounds__(256) k_prg_rows(uint8_t* __restrict__ out, siz
 // ECqPGroup.randomElementArray(n, prg, rbitlen), candidate by candidate (the reference derives its independent generators
 // with it, P/distr/IndependentGeneratorsRO.java:117-130; the procedure itself is VCR's and is restated from the published
 // verifier specification [NOT-IN-REF]): candidate j = the j-th ceil((bits(p) + rbitlen) / 8) bytes of the PRG stream with
-// the leading bits cleared, reduced mod p, taken as an x coordinate; it is KEPT when x^3 - 3x + b is a square, and then
+// the leading bits cleared, reduced mod p, taken as an x coordinate; it is KEPT when x^3 + a x + b is a square, and then
 // the point is (x, y) with y the SMALLER of the two roots; the i-th element of the array is the i-th kept candidate.
-// One lane per candidate: x from the PRG, z = (x^3 - 3x + b)^((p+1)/4) (p = 3 mod 4), kept iff z^2 is that value; the
+// One lane per candidate: x from the PRG, z = sqrt(x^3 + a x + b) (f_sqrt), kept iff z^2 is that value; the
 // caller compacts the kept rows in order.  c_m = 2^(8 cb) mod p in Montgomery form (the value is hi * 2^(8 cb) + lo).
-template <int S, int NW, int HASH>
+template <int S, int NW, int HASH, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW)
 k_ec_random_points(u32* __restrict__ rows, u32* __restrict__ keep, const uint32_t* __restrict__ seed_words, size_t first, size_t m,
                    size_t vb, uint32_t top_mask, size_t cb, const u32* __restrict__ c_m, ECDev E) {
@@ -2824,21 +2979,30 @@ k_ec_random_points(u32* __restrict__ rows, u32* __restrict__ keep, const uint32_
         cm[k] = c_m[k];
         bb[k] = E.b[k];
     }
-    f_mul<S>(lo, lo, rr, E);                           // Montgomery form (any value below R is reduced on the way)
-    f_mul<S>(hi, hi, rr, E);
-    f_mul<S>(t, hi, cm, E);
+    f_mul<S, false, KIND>(lo, lo, rr, E);              // Montgomery form (any value below R is reduced on the way)
+    f_mul<S, false, KIND>(hi, hi, rr, E);
+    f_mul<S, false, KIND>(t, hi, cm, E);
     f_add<S>(x, t, lo);                                // x = hi * 2^(8 cb) + lo  mod p
-    f_canon<S>(x, x, E);
-    f_sqr<S>(t, x, E);
-    f_mul<S>(t2, t, x, E);                             // x^3
-    f_small<S, 3>(t, x);
-    f_add<S>(rhs, t2, bb);
-    f_sub<S>(rhs, rhs, t, E);                          // x^3 - 3x + b
-    f_canon<S>(rhs, rhs, E);
-    f_sqrt<S>(z, rhs, E);
-    f_sqr<S>(t, z, E);
+    f_canon<S, KIND>(x, x, E);
+    f_sqr<S, false, KIND>(t, x, E);
+    f_mul<S, false, KIND>(t2, t, x, E);                // x^3
+    if constexpr (KIND == EC_GENERAL) {
+        u32 aa[S];
+#pragma unroll
+        for (int k = 0; k < S; ++k) aa[k] = E.a[k];
+        f_mul<S, false, KIND>(t, aa, x, E);
+        f_add<S>(rhs, t2, bb);
+        f_add<S>(rhs, rhs, t);                         // x^3 + a x + b
+    } else {
+        f_small<S, 3>(t, x);
+        f_add<S>(rhs, t2, bb);
+        f_sub<S>(rhs, rhs, t, E);                      // x^3 - 3x + b
+    }
+    f_canon<S, KIND>(rhs, rhs, E);
+    f_sqrt<S, KIND>(z, rhs, E);
+    f_sqr<S, false, KIND>(t, z, E);
     f_sub<S, true>(t2, t, rhs, E);
-    const bool ok = f_is_zero<S>(t2, E);
+    const bool ok = f_is_zero<S, KIND>(t2, E);
     // the smaller root: compare the standard representatives of z and p - z
     u32 one1[S], zs[S], zn[S], pp[S];
 #pragma unroll
@@ -2846,7 +3010,7 @@ k_ec_random_points(u32* __restrict__ rows, u32* __restrict__ keep, const uint32_
         one1[k] = k == 0 ? 1u : 0u;
         pp[k] = E.p[k];
     }
-    f_mul<S>(zs, z, one1, E);                          // z / R: standard representative, < 2p
+    f_mul<S, false, KIND>(zs, z, one1, E);             // z / R: standard representative, < 2p
     {
         u32 d[S];
         if (borrow_sweep<S>(d, zs, pp, 0) == 0) {
@@ -2874,8 +3038,8 @@ k_ec_random_points(u32* __restrict__ rows, u32* __restrict__ keep, const uint32_
     u32 ysel[S];
 #pragma unroll
     for (int k = 0; k < S; ++k) ysel[k] = (neg_smaller && znz) ? zn[k] : zs[k];
-    f_mul<S>(P.Y, ysel, rr, E);                        // back to Montgomery form
-    f_canon<S>(P.Y, P.Y, E);
+    f_mul<S, false, KIND>(P.Y, ysel, rr, E);           // back to Montgomery form
+    f_canon<S, KIND>(P.Y, P.Y, E);
     P.inf = 0;
     pt_store<S>(rows + j * ROW, P);
     keep[j] = ok ? 1u : 0u;
@@ -3138,16 +3302,16 @@ static int ec_random_points(vmn_group* grp, const uint8_t* seed, size_t seedlen,
         uint32_t* bsum = idx + (mcand + 1);
         uint32_t* total = bsum + scan_blocks;
         rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                            \
-    if (cv->S == S_) {                                                                                                        \
+#define X(S_, NW_, K_)                                                                                                        \
+    if (cv->S == S_ && cv->kind == K_) {                                                                                      \
         if (ps.hash == 256)                                                                                                   \
-            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 256>, grid_for(mcand), cand.as<uint32_t>(), keep,       \
+            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 256, K_>, grid_for(mcand), cand.as<uint32_t>(), keep,   \
                               (const uint32_t*)dseed.as<uint32_t>(), first, mcand, vb, top_mask, cb, (const uint32_t*)dc.as<uint32_t>(), ecdev(cv)); \
         else if (ps.hash == 384)                                                                                              \
-            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 384>, grid_for(mcand), cand.as<uint32_t>(), keep,       \
+            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 384, K_>, grid_for(mcand), cand.as<uint32_t>(), keep,   \
                               (const uint32_t*)dseed.as<uint32_t>(), first, mcand, vb, top_mask, cb, (const uint32_t*)dc.as<uint32_t>(), ecdev(cv)); \
         else                                                                                                                  \
-            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 512>, grid_for(mcand), cand.as<uint32_t>(), keep,       \
+            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 512, K_>, grid_for(mcand), cand.as<uint32_t>(), keep,   \
                               (const uint32_t*)dseed.as<uint32_t>(), first, mcand, vb, top_mask, cb, (const uint32_t*)dc.as<uint32_t>(), ecdev(cv)); \
     }
         VMN_FOR_CURVES(X)
@@ -3418,9 +3582,9 @@ static int fixed_table(vmn_group* g, const uint8_t* base_be, int ebits, size_t n
         if (rc == VMN_OK) rc = fixed_alloc(g, ft.bytes, &ft.d_tab);
         if (rc == VMN_OK) {
             rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                \
-    if (m.ec->S == S_) {                                                                                          \
-        hipLaunchKernelGGL(k_ec_chain<S_>, dim3(1), dim3(64), 0, ctx->stream, sq.as<uint32_t>(),                  \
+#define X(S_, NW_, K_)                                                                                            \
+    if (m.ec->S == S_ && m.ec->kind == K_) {                                                                      \
+        hipLaunchKernelGGL((k_ec_chain<S_, K_>), dim3(1), dim3(64), 0, ctx->stream, sq.as<uint32_t>(),            \
                            (const uint32_t*)d_base, (int)chain, ecdev(m.ec));                                     \
         rc = hipGetLastError() == hipSuccess ? VMN_OK : VMN_ERR_DEVICE;                                           \
     }
@@ -3432,8 +3596,8 @@ static int fixed_table(vmn_group* g, const uint8_t* base_be, int ebits, size_t n
                               (const uint32_t*)sq.as<uint32_t>(), w, nwin, (const uint32_t*)m.d_one, (int)Wd);
         for (int l = 1; l < w && rc == VMN_OK; ++l) {
             size_t lanes = (((size_t)1 << l) - 1) * nwin;
-#define X(S_, NW_) \
-    if (m.ec->S == S_) rc = note_work(ctx, m, EC_ADD * (double)lanes) ? 0 : launch_light(ctx, "fixed_table", k_ec_fixed_level<S_>, grid_for(lanes), ft.d_tab, w, nwin, l, ecdev(m.ec));
+#define X(S_, NW_, K_) \
+    if (m.ec->S == S_ && m.ec->kind == K_) rc = note_work(ctx, m, EC_ADD * (double)lanes) ? 0 : launch_light(ctx, "fixed_table", k_ec_fixed_level<S_, K_>, grid_for(lanes), ft.d_tab, w, nwin, l, ecdev(m.ec));
             VMN_FOR_CURVES(X)
 #undef X
         }
@@ -3564,9 +3728,9 @@ extern "C" int vmn_group_exp_fixed(vmn_group* grp, const uint8_t* base_be, const
     if (rc == VMN_OK && grp->P.ec) {
         const vmn_modulus& m = grp->P;
         rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                   \
-    if (m.ec->S == S_)                                                                                               \
-        rc = note_work(ctx, m, EC_MADD_RUN * (double)n * (ft->nwin - 1), 0, EC_MADD * (double)n * (ft->nwin - 1)) ? 0 : launch_light(ctx, "fixed", k_ec_fixed_exp<S_>, grid_for(n), r->d, (const uint32_t*)ft->d_tab, ft->wbits, \
+#define X(S_, NW_, K_)                                                                                               \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                           \
+        rc = note_work(ctx, m, EC_MADD_RUN * (double)n * (ft->nwin - 1), 0, EC_MADD * (double)n * (ft->nwin - 1)) ? 0 : launch_light(ctx, "fixed", k_ec_fixed_exp<S_, K_>, grid_for(n), r->d, (const uint32_t*)ft->d_tab, ft->wbits, \
                           ft->nwin, (const uint32_t*)ew.as<uint32_t>(), grp->Q.NW, n, ecdev(m.ec));
         VMN_FOR_CURVES(X)
 #undef X
@@ -3589,7 +3753,7 @@ extern "C" int vmn_group_exp_fixed(vmn_group* grp, const uint8_t* base_be, const
     if (m.S == S_)                                                                                                 \
         rc = note_work(ctx, m, (double)n * (ft->nwin - parts)) ? 0 : launch(ctx, "fixed", k_fixed_exp<Cfg<S_, LPE_>>, grid, lds_bytes(m), dst, (const uint32_t*)ft->d_tab, ft->wbits, \
                     ft->nwin, (const uint32_t*)ew.as<uint32_t>(), grp->Q.NW, n, parts, m.d_n, m.n0inv);
-        if (rc == VMN_OK) {                          // (a failed allocation of the pieces must not reach the launch: dst would be null)
+        if (rc == VMN_OK) {                              // (a failed allocation of the pieces must not reach the launch: dst would be null)
             rc = VMN_ERR_ARG;
             VMN_FOR_SIZES(X)
         }
@@ -3640,8 +3804,8 @@ static int ec_normalize(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* cons
     double products = 7.0 * (double)(k * n) + EC_INV * (double)sizes[L - 1];
     for (size_t l = 1; l + 1 < L; ++l) products += 3.0 * (double)sizes[l];
     int rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                                   \
-    if (m.ec->S == S_) {                                                                                                             \
+#define X(S_, NW_, K_)                                                                                                               \
+    if (m.ec->S == S_ && m.ec->kind == K_) {                                                                                         \
         note_work(ctx, m, products);                                                                                                 \
         rc = VMN_OK;                                                                                                                 \
         const unsigned bpa = (unsigned)((n1 + BLOCK - 1) / BLOCK);                       /* blocks per array of the two row-level launches */ \
@@ -3649,27 +3813,27 @@ static int ec_normalize(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* cons
             const size_t ga = std::min<size_t>(LEVEL_ARRAYS, k - a0);                                                                \
             LevelInputs li{};                                                                                                        \
             for (size_t a = 0; a < ga; ++a) li.p[a] = ins[a0 + a];                                                                   \
-            rc = launch_light(ctx, "normalize", k_finv_up<S_, true>, (unsigned)(bpa * ga), B + off_pref[0] + a0 * n * FWd,     \
+            rc = launch_light(ctx, "normalize", k_finv_up<S_, true, K_>, (unsigned)(bpa * ga), B + off_pref[0] + a0 * n * FWd, \
                               B + off_val[1] + a0 * n1 * FWd, li, bpa, n, K, ecdev(m.ec));                                           \
         }                                                                                                                            \
         for (size_t l = 1; l + 1 < L && rc == VMN_OK; ++l) {                                                                         \
             LevelInputs li{};                                                                                                        \
             li.p[0] = B + off_val[l];                                                                                                \
             const unsigned bl = (unsigned)((sizes[l + 1] + BLOCK - 1) / BLOCK);                                                      \
-            rc = launch_light(ctx, "normalize", k_finv_up<S_, false>, bl, B + off_pref[l], B + off_val[l + 1], li, bl,         \
+            rc = launch_light(ctx, "normalize", k_finv_up<S_, false, K_>, bl, B + off_pref[l], B + off_val[l + 1], li, bl,     \
                               sizes[l], K, ecdev(m.ec));                                                                             \
         }                                                                                                                            \
         if (rc == VMN_OK)                                                                                                            \
-            rc = launch_light(ctx, "normalize", k_finv_top<S_>, grid_for(sizes[L - 1]), B + off_inv[L - 1],                          \
+            rc = launch_light(ctx, "normalize", k_finv_top<S_, K_>, grid_for(sizes[L - 1]), B + off_inv[L - 1],                      \
                               (const uint32_t*)(B + off_val[L - 1]), sizes[L - 1], ecdev(m.ec));                                     \
         for (size_t l = L - 2; l >= 1 && rc == VMN_OK; --l)                                                                          \
-            rc = launch_light(ctx, "normalize", k_finv_down<S_>, grid_for(sizes[l + 1]), B + off_inv[l], (const uint32_t*)(B + off_inv[l + 1]), \
+            rc = launch_light(ctx, "normalize", k_finv_down<S_, K_>, grid_for(sizes[l + 1]), B + off_inv[l], (const uint32_t*)(B + off_inv[l + 1]), \
                               (const uint32_t*)(B + off_pref[l]), (const uint32_t*)(B + off_val[l]), sizes[l], K, ecdev(m.ec));      \
         for (size_t a0 = 0; a0 < k && rc == VMN_OK; a0 += LEVEL_ARRAYS) {                                                            \
             const size_t ga = std::min<size_t>(LEVEL_ARRAYS, k - a0);                                                                \
             LevelInputs li{};                                                                                                        \
             for (size_t a = 0; a < ga; ++a) li.p[a] = ins[a0 + a];                                                                   \
-            rc = launch_light(ctx, "normalize", k_ec_normalize_down<S_>, (unsigned)(bpa * ga), out + a0 * n * Wd, li, bpa,     \
+            rc = launch_light(ctx, "normalize", k_ec_normalize_down<S_, K_>, (unsigned)(bpa * ga), out + a0 * n * Wd, li, bpa, \
                               (const uint32_t*)(B + off_inv[1] + a0 * n1 * FWd), (const uint32_t*)(B + off_pref[0] + a0 * n * FWd),  \
                               n, K, ecdev(m.ec));                                                                                    \
         }                                                                                                                            \
@@ -4013,17 +4177,17 @@ static int expprod_words(vmn_group* g, const uint32_t* const* xs, size_t k, cons
             if (total_out > 0 && m.ec) {
                 rc = VMN_ERR_ARG;
                 const unsigned bpa = grid_for(total_out);
-#define X(S_, NW_)                                                                                                     \
-    if (m.ec->S == S_) {                                                                                               \
+#define X(S_, NW_, K_)                                                                                                 \
+    if (m.ec->S == S_ && m.ec->kind == K_) {                                                                           \
         rc = note_work(ctx, m, (first && ec_rows_normalised ? EC_MADD_RUN : EC_ADD) * level_products, 0,                        \
                        (first && ec_rows_normalised ? EC_MADD : EC_ADD) * level_products) ? 0                                  \
-             : first && !ec_rows_normalised ? launch_light(ctx, "expprod", k_ec_bucket_first_jacobian<S_>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa, \
+             : first && !ec_rows_normalised ? launch_light(ctx, "expprod", k_ec_bucket_first_jacobian<S_, K_>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa, \
                                   (const uint32_t*)sorted.as<uint32_t>(), off_in, cnt_in, (const uint32_t*)off_of((int)level),    \
                                   nbuckets, total_out, F, ecdev(m.ec))                                                 \
-             : first ? launch_light(ctx, "expprod", k_ec_bucket_level<S_, true>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa, \
+             : first ? launch_light(ctx, "expprod", k_ec_bucket_level<S_, true, K_>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa, \
                                   (const uint32_t*)sorted.as<uint32_t>(), off_in, cnt_in, (const uint32_t*)off_of((int)level),    \
                                   nbuckets, total_out, F, ecdev(m.ec))                                                 \
-                   : launch_light(ctx, "expprod", k_ec_bucket_level<S_, false>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa,        \
+                   : launch_light(ctx, "expprod", k_ec_bucket_level<S_, false, K_>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa,    \
                                   (const uint32_t*)nullptr, off_in, cnt_in, (const uint32_t*)off_of((int)level),        \
                                   nbuckets, total_out, F, ecdev(m.ec));                                                \
     }
@@ -4087,9 +4251,9 @@ static int expprod_words(vmn_group* g, const uint32_t* const* xs, size_t k, cons
         DevTmp res(ctx);
         VMN_TRY(res.alloc(k * Wd * sizeof(uint32_t)));
         int rc = VMN_ERR_ARG;
-#define X(S_, NW_)                                                                                                        \
-    if (m.ec->S == S_)                                                                                                    \
-        rc = launch_light(ctx, "expprod_agg", k_ec_horner<S_>, grid_for(k), res.as<uint32_t>(), (const uint32_t*)wres.as<uint32_t>(), \
+#define X(S_, NW_, K_)                                                                                                    \
+    if (m.ec->S == S_ && m.ec->kind == K_)                                                                                \
+        rc = launch_light(ctx, "expprod_agg", k_ec_horner<S_, K_>, grid_for(k), res.as<uint32_t>(), (const uint32_t*)wres.as<uint32_t>(), \
                           nwin, c, (int)k, ecdev(m.ec));
         VMN_FOR_CURVES(X)
 #undef X

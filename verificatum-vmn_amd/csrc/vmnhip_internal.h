@@ -124,12 +124,15 @@ struct vmn_ctx {
 struct vmn_curve {
     std::string name;
     int S = 0, NW = 0;             // field limbs / packed words
-    vmn::hostbig::Big p_words, b_words, gx_words, gy_words;
-    uint32_t* d_consts = nullptr;  // one allocation holding p | one | rr | b | mp | mp2 | pm2
+    int kind = 0;                  // ec_kernels.h EC_NIST (a = -3) / EC_GENERAL (any a): which instances run this curve
+    vmn::hostbig::Big p_words, b_words, gx_words, gy_words, a_words;
+    uint32_t* d_consts = nullptr;  // one allocation holding p | one | rr | b | a | mp | mp2 | pm2
     const uint32_t* d_p = nullptr;
     const uint32_t* d_one = nullptr;
     const uint32_t* d_rr = nullptr;
     const uint32_t* d_b = nullptr;
+    const uint32_t* d_a = nullptr;  // a R mod p (ECDev::a)
+    int a_zero = 0;
     const uint32_t* d_mp = nullptr;
     const uint32_t* d_mp2 = nullptr;
     const uint32_t* d_pm2 = nullptr;

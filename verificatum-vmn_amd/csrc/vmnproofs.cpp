@@ -240,6 +240,14 @@ struct HostGroup {
         curve.F = &Zp;                 // (HostGroup objects are not copied after init)
         curve.cb = cw;
         curve.fl = pl;
+        if (ec) {                      // a general a (brainpool, secp*k1 ...); a = -3 stays on the host's dbl-2001-b
+            Bytes ab(cw);
+            TRY(vmn_group_get_curve_a(grp, ab.data()));
+            Num a = vmn::num64::from_be(ab.data(), cw, pl), pm3 = Zp.n, three(pl, 0);
+            three[0] = 3;
+            vmn::num64::sub_in(pm3, three);
+            if (vmn::num64::cmp(a, pm3) != 0) curve.a = Zp.to_m(a);
+        }
         g.resize(eb);
         TRY(vmn_group_get_generator(grp, g.data()));
         return VMN_OK;
