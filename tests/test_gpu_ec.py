@@ -210,7 +210,10 @@ def test_multi_exponentiation_and_movement(ecg, first_level_rows):
 def test_signed_window_recoding_of_the_multi_exponentiation(ecg, first_level_rows):
     """Curves sort the exponents by SIGNED window digits (light_kernels.h signed_digit): exponents whose digits sit on the
     recoding's edges for every window width the library may pick -- every digit exactly 2^(c-1) (a carry arrives or not), one
-    above and one below, all ones (a carry through every window), the top bits of the order -- against the oracle."""
+    above and one below, all ones (a carry through every window), the top bits of the order -- against the oracle.
+    The width that RUNS is picked from the size of the array, not from the exponents: the two arrays below are recoded at the
+    two or three widths of their sizes (3 and 6 bits over P-256).  Every width 2 ... 17 at its own edges:
+    test_gpu_schedules.py::test_multi_exponentiation_at_every_window_width_curves."""
     G, c = ecg
     rnd = random.Random(77)
     nbits = c.n.bit_length()

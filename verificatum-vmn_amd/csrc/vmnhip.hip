@@ -129,11 +129,8 @@ static size_t default_wide8_max() {
 // 786 432 (47.4 / 110.7 with 196 608): more waves than the two per SIMD that fill the chip still pay, because the kernel waits
 // on its random 296-byte table rows.
 static size_t fixed_split_fill() {
-    static const size_t v = [] {
-        const char* env = getenv("VMN_FIXED_SPLIT_FILL");
-        return env ? (size_t)strtoull(env, nullptr, 10) : (size_t)786432;
-    }();
-    return v;
+    const char* env = getenv("VMN_FIXED_SPLIT_FILL");           // (read per call: the tests run a table's exponentiation cut and uncut)
+    return env ? (size_t)strtoull(env, nullptr, 10) : (size_t)786432;
 }
 static const vmn_modulus& geom(const vmn_ctx* ctx, const vmn_modulus& m, size_t items, bool always = false) {
     const vmn_ctx* root = ctx->parent ? ctx->parent : ctx;
@@ -242,6 +239,16 @@ static int launch_light(vmn_ctx* ctx, const char* family, void (*kernel)(KArgs..
         ctx->recs.push_back(rec);
     }
     return VMN_OK;
+}
+
+// A mark in the timing report: family `name` counts one launch of no duration -- which of two kernels of ONE family a call took
+// (the mixed form of vmn_garray_exp_pair).  Only recorded while timing is on.
+static void note_path(vmn_ctx* ctx, const char* name) {
+    if (!ctx->timing) return;
+    TimingRec rec;
+    rec.family = name;
+    rec.start = rec.stop = nullptr;
+    ctx->recs.push_back(rec);
 }
 
 // Device -> host on the lane's stream, complete on return.  Up to STAGE_BYTES through the lane's pinned buffer (a copy into
@@ -536,6 +543,7 @@ extern "C" void vmn_ctx_destroy(vmn_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& r : ctx->recs) {
+        if (!r.start) continue;                            // (a mark: note_path)
         (void)hipEventDestroy(r.start);
         (void)hipEventDestroy(r.stop);
     }
@@ -685,14 +693,16 @@ static int timing_collect_lane(vmn_ctx* into, vmn_ctx* lane) {
     VMN_HIP(hipStreamSynchronize(lane->stream));
     for (auto& r : lane->recs) {
         float ms = 0;
-        VMN_HIP(hipEventElapsedTime(&ms, r.start, r.stop));
+        if (r.start) VMN_HIP(hipEventElapsedTime(&ms, r.start, r.stop));          // (no events: a mark, note_path)
         auto& acc = into->timing_acc[r.family];
         acc.first += 1;
         acc.second += ms;
         into->work_acc[r.family] += r.mads;
         into->canon_acc[r.family] += r.canon;
-        (void)hipEventDestroy(r.start);
-        (void)hipEventDestroy(r.stop);
+        if (r.start) {
+            (void)hipEventDestroy(r.start);
+            (void)hipEventDestroy(r.stop);
+        }
     }
     lane->recs.clear();
     return VMN_OK;
@@ -2187,10 +2197,8 @@ extern "C" int vmn_garray_exp_pair(const vmn_garray* x, const uint8_t* e_be, siz
         // Mixed form (2048-bit rows): when four lanes per element were chosen and the LONGER job's tiles at eight lanes still fit
         // beside the shorter job's at four, the longer chain -- which sets the time of the launch -- gets the eight
         // (k_modpow_jobs_mixed; VMN_PAIR_MIXED=0 turns it off).
-        static const bool mixed_off = [] {
-            const char* e = getenv("VMN_PAIR_MIXED");
-            return e && *e == '0';
-        }();
+        const char* mixed_env = getenv("VMN_PAIR_MIXED");        // (read per call: the tests run the pair both ways)
+        const bool mixed_off = mixed_env && *mixed_env == '0';
         const bool mixed_fits = !mixed_off && !g->P.ec && mp == g->P.wide && g->P.wide8 && g->P.S == 74 && nx > 0 && ny > 0;
         if (!g->P.ec && nx > 0 && ny > 0 && tiles <= (size_t)ctx->num_cus * 2 * blocks_per_cu(m)) {
             int ewords = (int)((ebytes + 3) / 4);
@@ -2227,6 +2235,7 @@ extern "C" int vmn_garray_exp_pair(const vmn_garray* x, const uint8_t* e_be, siz
                         rc = launch(ctx, "modpow", k_modpow_jobs_mixed<Cfg<80, 8>, Cfg<76, 4>>, (unsigned)tiles_mixed,
                                     std::max(lds_bytes(m8), lds_bytes(m)), j0, j1, egrid(m8, j0.n), wbits, m.d_n, m.n0inv, m.d_one,
                                     reinterpret_cast<uint32_t*>(ctx->scratch));
+                    if (rc == VMN_OK) note_path(ctx, "pair_mixed");
                 } else {
                 rc = VMN_ERR_ARG;
 #define X(S_, NW_, LPE_)                                                                                                     \
@@ -2664,9 +2673,13 @@ static int scan_affine(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* e, c
         if (b) return VMN_ERR_ARG;
         size_t Cc = scan_chunk(n, (size_t)ctx->num_cus * 4 * 64 * 4);          // light kernels: 4 waves per SIMD
         if (seglen != n) {
-            while (Cc > 1 && seglen % Cc) Cc >>= 1;
+            while (Cc > 1 && seglen % Cc) --Cc;      // the largest divisor of a segment not above the chunk (halving a chunk of 3 ended at 1)
         }
         if (seglen <= Cc) Cc = seglen;
+        if (Cc < 2 && seglen > 1) {                     // chunks of one value: the scan over the chunk totals would be this scan again
+            set_error("scan: segments of %zu values cannot be cut into chunks of 2 ... %zu", seglen, scan_chunk(n, (size_t)ctx->num_cus * 4 * 64 * 4));
+            return VMN_ERR_UNSUPPORTED;
+        }
         size_t nchunks = (n + Cc - 1) / Cc;
         int rc = VMN_ERR_ARG;
         if (seglen <= Cc) {
@@ -2701,7 +2714,12 @@ static int scan_affine(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* e, c
     // chunk length: divides seglen when there are several segments
     size_t C = scan_chunk(n, (size_t)ctx->num_cus * blocks_per_cu(m) * (BLOCK / m.LPE));   // one tile per resident workgroup
     if (seglen != n) {
-        while (C > 1 && seglen % C) C >>= 1;
+        while (C > 1 && seglen % C) --C;             // (as above)
+    }
+    if (C < 2 && seglen > 1) {
+        set_error("scan: segments of %zu values cannot be cut into chunks of 2 ... %zu", seglen,
+                  scan_chunk(n, (size_t)ctx->num_cus * blocks_per_cu(m) * (BLOCK / m.LPE)));
+        return VMN_ERR_UNSUPPORTED;
     }
     if (seglen <= C) {
         // every segment fits one chunk: a single apply pass with fresh starts
@@ -3526,7 +3544,8 @@ static int fixed_window_for(vmn_group* g, size_t n, int ebits, int reuse_hint) {
     size_t lanes = m.ec ? (size_t)ctx->num_cus * 4 * 64 * 2 : (size_t)ctx->num_cus * blocks_per_cu(m) * (BLOCK / m.LPE);
     if (!m.ec) {
         size_t parts = 1;
-        while (parts < 16 && 2 * parts * n <= fixed_split_fill()) parts *= 2;
+        const size_t fill = fixed_split_fill();
+        while (parts < 16 && 2 * parts * n <= fill) parts *= 2;
         lanes /= parts;
     }
     return pick_fixed_window(std::max(n, lanes), ebits, elem_words(m) * sizeof(uint32_t), reuse_hint);
@@ -3779,10 +3798,8 @@ static int ec_normalize(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* cons
     if (n == 0 || k == 0) return VMN_OK;
     // K values per lane and level: a launch holds n / K lanes, each a chain of K load + product steps (VMN_EC_NORMALISE_CHUNK,
     // profiles/r04_ec_normalise_chunk_sweep.txt)
-    static const size_t K_env = [] {
-        const char* e = getenv("VMN_EC_NORMALISE_CHUNK");
-        return e && *e ? (size_t)std::max(2, atoi(e)) : (size_t)0;
-    }();
+    const char* K_str = getenv("VMN_EC_NORMALISE_CHUNK");      // (read per call: the tests run two, three and four levels at their sizes)
+    const size_t K_env = K_str && *K_str ? (size_t)std::max(2, atoi(K_str)) : (size_t)0;
     const size_t FWd = (size_t)stride_for_limbs(m.ec->S), Wd = (size_t)m.W, K = K_env ? K_env : 8, TOP = 2048;
     const size_t n1 = (n + K - 1) / K;                       // chunks (= level-1 values) per array
     std::vector<size_t> sizes{k * n, k * n1};                // values per level (level 0: the Z's of the rows, k arrays of n)
@@ -3854,16 +3871,13 @@ static double bucket_agg_weight() {
 // curves recode the windows to signed digits (light_kernels.h: signed_digit): 2^(c-1) buckets per c-bit window, one more
 // bit of the exponent to hold the last carry.  VMN_SIGNED_WINDOWS=0 turns that off (measurement).
 static bool signed_windows(const vmn_modulus& m) {
-    static const bool off = [] {
-        const char* e = getenv("VMN_SIGNED_WINDOWS");
-        return e && *e == '0';
-    }();
-    return m.ec != nullptr && !off;
+    const char* e = getenv("VMN_SIGNED_WINDOWS");               // (read per call: the tests run both recodings over curves)
+    return m.ec != nullptr && !(e && *e == '0');
 }
 static int pick_bucket_bits(size_t n, int ebits, bool ec = false, bool sgn = false) {
     if (const char* env = getenv("VMN_WINDOW_BITS")) {           // measurement knob: the window width itself
         const int c = atoi(env);
-        if (c >= 2 && c <= 16) return c;
+        if (c >= 2 && c <= (sgn ? 17 : 16)) return c;           // (the picker's own range below)
     }
     int best = 1;
     double best_cost = 1e300;
@@ -4046,10 +4060,8 @@ static int expprod_words(vmn_group* g, const uint32_t* const* xs, size_t k, cons
     // fan-in of the per-bucket product tree.  A lane sums one chunk of at most F items; the lanes of a wave wait for the longest
     // chunk, so F is best a little above the typical bucket size n / 2^c (most buckets are then ONE chunk, the wave's longest
     // chunk is close to its average, and hardly anything is left for the upper levels -- which run full additions on few lanes).
-    static const uint32_t F_env = [] {
-        const char* e = getenv("VMN_TREE_FANIN");
-        return e && *e ? (uint32_t)std::max(4, atoi(e)) : 0u;
-    }();
+    const char* F_str = getenv("VMN_TREE_FANIN");              // (read per call: the tests grow deep trees out of small arrays)
+    const uint32_t F_env = F_str && *F_str ? (uint32_t)std::max(4, atoi(F_str)) : 0u;
     // Curves: 16 -- the sum of a chunk runs in XYZZ registers and is turned into a Jacobian row once per chunk (2 products),
     // and the upper levels add Jacobian rows at 11M + 5S: both favour longer chunks (profiles/r04_ec_fanin_sweep_xyzz.txt).
     const uint32_t F = F_env ? F_env : (m.ec ? 16 : 8);
@@ -4242,10 +4254,9 @@ static int expprod_words(vmn_group* g, const uint32_t* const* xs, size_t k, cons
         pend->nwin = nwin;
         pend->c = c;
     }
-    static const bool horner_on_device = [] {          // measurement knob: the one-lane-per-array kernel of round 2
-        const char* e = getenv("VMN_EC_HORNER_DEVICE");
-        return e && *e == '1';
-    }();
+    // measurement knob: the one-lane-per-array kernel of round 2 (read per call: the tests run both chains)
+    const char* horner_env = getenv("VMN_EC_HORNER_DEVICE");
+    const bool horner_on_device = horner_env && *horner_env == '1';
     if (m.ec && horner_on_device) {
         VMN_TRACE("expprod:horner_device");
         DevTmp res(ctx);
