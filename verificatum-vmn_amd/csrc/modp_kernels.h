@@ -619,6 +619,160 @@ __device__ __forceinline__ u32 exp_digit(const u32* __restrict__ ep, int ewords,
     return (u32)(both >> sh) & ((1u << wbits) - 1);
 }
 
+// The pieces every power kernel is made of (k_modpow, k_modpow2, k_modpow_shared of modp_shared_exp.h, their phased forms and
+// modpow_job_tile): each table build and each window loop is written here once, the kernels differ in where a tile's table
+// lives and in which windows of the power one pass over a tile runs.
+// a = a^(2^count)
+template <class C>
+__device__ __forceinline__ void sqr_times(u32 (&a)[C::L], int count, const Lane<C>& ln, const u32 (&nn)[C::L], u32 n0inv) {
+#pragma unroll 1
+    for (int s = 0; s < count; ++s) {
+        regs_to_lds<C>(ln, a);
+        mont_sqr<C>(a, a, ln, nn, n0inv);
+    }
+}
+// a = a * (the table row at `row`)
+template <class C>
+__device__ __forceinline__ void mul_by_row(u32 (&a)[C::L], const u32* __restrict__ row, const Lane<C>& ln, const u32 (&nn)[C::L],
+                                           u32 n0inv) {
+    load_elem_to_lds<C>(ln, row);
+    mont_mul<C>(a, a, ln, nn, n0inv);
+}
+// fixed-window table of the element at `base`: tb[0] = 1, tb[1] = base, tb[k] = tb[k-1] * base (a: work registers, = base after)
+template <class C>
+__device__ __forceinline__ void window_table(u32 (&a)[C::L], u32* __restrict__ tb, int tsize, const u32* __restrict__ base,
+                                             const u32* __restrict__ one_m, const Lane<C>& ln, const u32 (&nn)[C::L], u32 n0inv) {
+    constexpr int W = C::W;
+    load_elem<C>(a, base, ln);
+    {
+        u32 o[C::L];
+        load_modulus<C>(o, one_m, ln);
+        store_elem<C>(tb, o, ln);
+    }
+    store_elem<C>(tb + W, a, ln);
+    regs_to_lds<C>(ln, a);
+#pragma unroll 1
+    for (int k = 2; k < tsize; ++k) {
+        u32 r[C::L];
+        mont_mul<C>(r, a, ln, nn, n0inv);              // base * tb[k-1]
+        store_elem<C>(tb + (size_t)k * W, r, ln);
+        regs_to_lds<C>(ln, r);
+    }
+}
+// sliding-window table of the element at `base`, the odd powers only: tb[0] = x, tb[k] = tb[k-1] * x^2 (a: work registers)
+template <class C>
+__device__ __forceinline__ void odd_power_table(u32 (&a)[C::L], u32* __restrict__ tb, int tsize, const u32* __restrict__ base,
+                                                const Lane<C>& ln, const u32 (&nn)[C::L], u32 n0inv) {
+    constexpr int W = C::W;
+    u32 x2[C::L];
+    load_elem<C>(a, base, ln);
+    store_elem<C>(tb, a, ln);
+    regs_to_lds<C>(ln, a);
+    mont_sqr<C>(x2, a, ln, nn, n0inv);
+#pragma unroll 1
+    for (int k = 1; k < tsize; ++k) {
+        regs_to_lds<C>(ln, a);
+        u32 r[C::L];
+        mont_mul<C>(r, x2, ln, nn, n0inv);             // x^2 * tb[k-1]
+        store_elem<C>(tb + (size_t)k * W, r, ln);
+#pragma unroll
+        for (int j = 0; j < C::L; ++j) a[j] = r[j];
+    }
+}
+// windows hi .. lo (downwards) of a fixed-window power: wbits squarings, then the product by the window's table row
+// (counted by k = wi - lo, here and in straus_windows: with `wi` itself as the counter the compiler lays the loop out differently once
+// two kernels share this function, and k_modpow<Cfg<80, 8>> loses a wave per SIMD to the copies at the loop's edges)
+template <class C>
+__device__ __forceinline__ void fixed_windows(u32 (&a)[C::L], const u32* __restrict__ ep, int ewords, int wbits, int hi, int lo,
+                                              const u32* __restrict__ tb, const Lane<C>& ln, const u32 (&nn)[C::L], u32 n0inv) {
+#pragma unroll 1
+    for (int k = hi - lo; k >= 0; --k) {
+        const int wi = lo + k;
+        sqr_times<C>(a, wbits, ln, nn, n0inv);
+        const u32 d = exp_digit(ep, ewords, wi * wbits, wbits);
+        mul_by_row<C>(a, tb + (size_t)d * C::W, ln, nn, n0inv);
+    }
+}
+// windows hi .. lo of the simultaneous power of two bases (Straus): the squarings shared, none in front of the top window, and
+// a product for each exponent that reaches the window (uniform over the launch: window counts, not digits, decide)
+template <class C>
+__device__ __forceinline__ void straus_windows(u32 (&a)[C::L], const u32* __restrict__ ep1, int ewords1, int nwin1,
+                                               const u32* __restrict__ ep2, int ewords2, int nwin2, int wbits, int hi, int lo,
+                                               const u32* __restrict__ tab1, const u32* __restrict__ tab2, const Lane<C>& ln,
+                                               const u32 (&nn)[C::L], u32 n0inv) {
+    const int nwin = nwin1 > nwin2 ? nwin1 : nwin2;
+#pragma unroll 1
+    for (int k = hi - lo; k >= 0; --k) {
+        const int wi = lo + k;
+        if (wi != nwin - 1) sqr_times<C>(a, wbits, ln, nn, n0inv);
+        if (wi < nwin1) mul_by_row<C>(a, tab1 + (size_t)exp_digit(ep1, ewords1, wi * wbits, wbits) * C::W, ln, nn, n0inv);
+        if (wi < nwin2) mul_by_row<C>(a, tab2 + (size_t)exp_digit(ep2, ewords2, wi * wbits, wbits) * C::W, ln, nn, n0inv);
+    }
+}
+
+// The queue of a phased kernel.  Every tile of k_modpow takes the same time T, so an array of r = ntiles / slots rounds finishes
+// after ceil(r) T: 10^6 elements are 7.63 rounds of the 512 workgroup slots and cost 8 -- 4.6 % of the launch is the idle tail of
+// its last round (measured: 0.632 of the roof at exactly 2 rounds, 0.603 at 7.63).  A phased kernel cuts a tile's power into
+// `phases` runs of windows and its workgroups take (phase, tile) units from this queue in phase-major order: P x 7.63 rounds of
+// units of T / P each, the tail is at most one UNIT.  Between its phases a tile's running value lives in out[], its table in a
+// table of its OWN (per element, not per lane slot: another workgroup continues it).  Unit u = (phase, tile) needs
+// (phase - 1, tile), which is unit u - ntiles: handed out earlier, to a workgroup that is therefore running and waits for
+// nothing later than itself -- the spin in take() always ends, whatever part of the grid is resident.
+//     UnitQueue q(queue, done, &s_unit, ntiles, phases);          (s_unit: a __shared__ word of the kernel)
+//     while (q.take()) { ... unit (q.ph, q.t) ...; q.hand_over(); }
+// ONE thread-0 region per turn -- the hand-over of the finished unit and the fetch of the next, between the two barriers of
+// hand_over().  (With the fetch at the top of the loop and the hand-over at its bottom, two thread-0 regions sit around the back
+// edge: the compiler lets the other lanes of wave 0 run ahead into the next turn's barrier while lane 0 is still signalling, the
+// barrier counts go out of step and the kernel hangs -- tools/micro/queue_handoff.hip reproduces both forms.)
+struct UnitQueue {
+    u32* queue;       // units handed out so far
+    u32* done;        // done[t]: phases of tile t that are finished and visible
+    u32* s_unit;      // the workgroup's current unit
+    u32 ntiles, nunits;
+    int phases;
+    int ph;           // the unit take() returned: phase ...
+    u32 t;            // ... and tile
+    __device__ __forceinline__ UnitQueue(u32* queue_, u32* done_, u32* s_unit_, u32 ntiles_, int phases_)
+        : queue(queue_), done(done_), s_unit(s_unit_), ntiles(ntiles_), nunits(ntiles_ * (u32)phases_), phases(phases_), ph(0), t(0) {
+        if (threadIdx.x == 0) fetch();
+        __syncthreads();
+    }
+    // the next unit of this workgroup, once its tile's previous phase is finished; false: the queue is empty
+    __device__ __forceinline__ bool take() {
+        const u32 u = (u32)__builtin_amdgcn_readfirstlane((int)*s_unit);
+        ph = (int)(u / ntiles);                          // (split before the test: no path leaves ph and t undefined -- with
+        t = u - (u32)ph * ntiles;                        // them set after it the compiler keeps both in vector registers)
+        if (u >= nunits) return false;
+        if (ph > 0) {                                    // the tile's previous phase, run by another workgroup
+            if (threadIdx.x == 0) {
+                long spins = 0;                          // (a unit lasts milliseconds: 2^28 polls are minutes -- a bug, and then a trap, not a hang)
+                while (__hip_atomic_load(done + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < (u32)ph) {
+                    if (++spins > (1L << 28)) __builtin_trap();
+                    __builtin_amdgcn_s_sleep(16);
+                }
+            }
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+        return true;
+    }
+    __device__ __forceinline__ bool last() const { return ph == phases - 1; }
+    // the unit's stores are issued: publish them to the workgroup that continues the tile, and fetch the next unit
+    __device__ __forceinline__ void hand_over() {
+        const bool hand_on = !last();                    // another workgroup continues this tile
+        if (hand_on) __threadfence();
+        __syncthreads();                                 // every store of the unit is out; everybody has read s_unit
+        if (threadIdx.x == 0) {
+            if (hand_on) (void)__hip_atomic_exchange(done + t, (u32)(ph + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            fetch();
+        }
+        __syncthreads();
+    }
+
+private:
+    __device__ __forceinline__ void fetch() { *s_unit = atomicAdd(queue, 1u); }     // (thread 0 only)
+};
+
 template <class C>
 __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e, int ewords, size_t estride,
@@ -640,52 +794,16 @@ k_modpow(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict
         size_t ec = live ? el : n - 1;
         const u32* ep = e + ec * estride;
         u32 a[C::L];
-        // table: tab[0] = 1, tab[1] = x, tab[k] = tab[k-1] * x
-        load_elem<C>(a, x + ec * W, ln);
-        {
-            u32 o[C::L];
-            load_modulus<C>(o, one_m, ln);
-            store_elem<C>(mytab, o, ln);
-        }
-        store_elem<C>(mytab + W, a, ln);
-        regs_to_lds<C>(ln, a);
-#pragma unroll 1
-        for (int k = 2; k < tsize; ++k) {
-            u32 r[C::L];
-            mont_mul<C>(r, a, ln, nn, n0inv);          // x * tab[k-1]
-            store_elem<C>(mytab + (size_t)k * W, r, ln);
-            regs_to_lds<C>(ln, r);
-        }
-        // main loop
-        u32 d = exp_digit(ep, ewords, (nwin - 1) * wbits, wbits);
-        load_elem<C>(a, mytab + (size_t)d * W, ln);
-#pragma unroll 1
-        for (int wi = nwin - 2; wi >= 0; --wi) {
-#pragma unroll 1
-            for (int s = 0; s < wbits; ++s) {
-                regs_to_lds<C>(ln, a);
-                mont_sqr<C>(a, a, ln, nn, n0inv);
-            }
-            d = exp_digit(ep, ewords, wi * wbits, wbits);
-            load_elem_to_lds<C>(ln, mytab + (size_t)d * W);
-            mont_mul<C>(a, a, ln, nn, n0inv);
-        }
+        window_table<C>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
+        load_elem<C>(a, mytab + (size_t)exp_digit(ep, ewords, (nwin - 1) * wbits, wbits) * W, ln);     // the top window
+        fixed_windows<C>(a, ep, ewords, wbits, nwin - 2, 0, mytab, ln, nn, n0inv);
         canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_modpow for arrays of MORE than one round of tiles, in phases.  Every tile of k_modpow takes the same time T, so an
-// array of r = ntiles / slots rounds finishes after ceil(r) T: 10^6 elements are 7.63 rounds of the 512 workgroup slots and
-// cost 8 -- 4.6 % of the launch is the idle tail of its last round (measured: 0.632 of the roof at exactly 2 rounds,
-// 0.603 at 7.63).  Here a tile's power is cut into `phases` runs of windows and the workgroups take (phase, tile) units
-// from a queue in phase-major order: P x 7.63 rounds of units of T / P each, the tail is at most one UNIT.  Between its
-// phases a tile's running value lives in out[], its window table in a table of its OWN (per element, not per lane slot:
-// another workgroup continues it).  Unit u = (phase, tile) needs (phase - 1, tile), which is unit u - ntiles: handed out
-// earlier, to a workgroup that is therefore running and waits for nothing later than itself -- the spin below always ends,
-// whatever part of the grid is resident.  Same products in the same order as k_modpow: bit-identical results.
-// ---------------------------------------------------------------------------------------------
+// k_modpow for arrays of MORE than one round of tiles, in phases from a queue of (phase, tile) units (UnitQueue has the
+// reasons).  Same products in the same order as k_modpow: bit-identical results.
 template <class C>
 __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow_phased(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e, int ewords, size_t estride,
@@ -697,84 +815,30 @@ k_modpow_phased(u32* __restrict__ out, const u32* __restrict__ x, const u32* __r
     Lane<C> ln(lds);
     u32 nn[C::L];
     load_modulus<C>(nn, nmod, ln);
-    const u32 ntiles = (u32)((n + C::EPB - 1) / C::EPB);
-    const u32 nunits = ntiles * (u32)phases;
     const int tsize = 1 << wbits;
     const int nwin = (ebits + wbits - 1) / wbits;
     const int M = nwin - 1;                              // windows of the main loop (the top one is the first table read)
-    // ONE thread-0 region per turn -- the hand-over of the finished unit and the fetch of the next, between two barriers.  (With
-    // the fetch at the top of the loop and the hand-over at its bottom, two thread-0 regions sit around the back edge: the
-    // compiler lets the other lanes of wave 0 run ahead into the next turn's barrier while lane 0 is still signalling, the
-    // barrier counts go out of step and the kernel hangs -- tools/micro/queue_handoff.hip reproduces both forms.)
-    if (threadIdx.x == 0) s_unit = atomicAdd(queue, 1u);
-    __syncthreads();
-    for (;;) {
-        const u32 u = (u32)__builtin_amdgcn_readfirstlane((int)s_unit);
-        if (u >= nunits) break;
-        const int ph = (int)(u / ntiles);
-        const u32 t = u - (u32)ph * ntiles;
-        if (ph > 0) {                                    // the tile's previous phase, run by another workgroup
-            if (threadIdx.x == 0) {
-                long spins = 0;                          // (a unit lasts milliseconds: 2^28 polls are minutes -- a bug, and then a trap, not a hang)
-                while (__hip_atomic_load(done + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < (u32)ph) {
-                    if (++spins > (1L << 28)) __builtin_trap();
-                    __builtin_amdgcn_s_sleep(16);
-                }
-            }
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        size_t el = (size_t)t * C::EPB + ln.eslot;
+    UnitQueue q(queue, done, &s_unit, (u32)((n + C::EPB - 1) / C::EPB), phases);
+    while (q.take()) {
+        const int ph = q.ph;
+        size_t el = (size_t)q.t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
         const u32* ep = e + ec * estride;
-        u32* mytab = tab + ((size_t)t * C::EPB + ln.eslot) * (size_t)tsize * W;
+        u32* mytab = tab + el * (size_t)tsize * W;
         u32 a[C::L];
         if (ph == 0) {
-            // table: tab[0] = 1, tab[1] = x, tab[k] = tab[k-1] * x
-            load_elem<C>(a, x + ec * W, ln);
-            {
-                u32 o[C::L];
-                load_modulus<C>(o, one_m, ln);
-                store_elem<C>(mytab, o, ln);
-            }
-            store_elem<C>(mytab + W, a, ln);
-            regs_to_lds<C>(ln, a);
-#pragma unroll 1
-            for (int k = 2; k < tsize; ++k) {
-                u32 r[C::L];
-                mont_mul<C>(r, a, ln, nn, n0inv);          // x * tab[k-1]
-                store_elem<C>(mytab + (size_t)k * W, r, ln);
-                regs_to_lds<C>(ln, r);
-            }
-            u32 d = exp_digit(ep, ewords, (nwin - 1) * wbits, wbits);
-            load_elem<C>(a, mytab + (size_t)d * W, ln);
+            window_table<C>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
+            load_elem<C>(a, mytab + (size_t)exp_digit(ep, ewords, (nwin - 1) * wbits, wbits) * W, ln);
         } else {
             load_elem<C>(a, out + ec * W, ln);
         }
         // the windows of this phase: M - 1 - M ph / P  down to  M - M (ph + 1) / P
         const int hi = M - 1 - (int)((long)M * ph / phases), lo = M - (int)((long)M * (ph + 1) / phases);
-#pragma unroll 1
-        for (int wi = hi; wi >= lo; --wi) {
-#pragma unroll 1
-            for (int s = 0; s < wbits; ++s) {
-                regs_to_lds<C>(ln, a);
-                mont_sqr<C>(a, a, ln, nn, n0inv);
-            }
-            u32 d = exp_digit(ep, ewords, wi * wbits, wbits);
-            load_elem_to_lds<C>(ln, mytab + (size_t)d * W);
-            mont_mul<C>(a, a, ln, nn, n0inv);
-        }
-        if (ph == phases - 1) canonicalize<C>(a, nn, ln);
+        fixed_windows<C>(a, ep, ewords, wbits, hi, lo, mytab, ln, nn, n0inv);
+        if (q.last()) canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
-        const bool hand_on = ph < phases - 1;            // another workgroup continues this tile
-        if (hand_on) __threadfence();
-        __syncthreads();                                 // every store of the unit is out; everybody has read s_unit
-        if (threadIdx.x == 0) {
-            if (hand_on) (void)__hip_atomic_exchange(done + t, (u32)(ph + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            s_unit = atomicAdd(queue, 1u);
-        }
-        __syncthreads();
+        q.hand_over();
     }
 }
 
@@ -804,58 +868,20 @@ k_modpow2(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restric
         size_t el = t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
-        const u32* ep1 = e1 + ec * estride1;
-        const u32* ep2 = e2 + ec * estride2;
         u32 a[C::L];
-        // tables: tab[0] = 1, tab[1] = base, tab[k] = tab[k-1] * base
 #pragma unroll 1
-        for (int which = 0; which < 2; ++which) {
-            u32* tb = which ? tab2 : tab1;
-            {
-                u32 o[C::L];
-                load_modulus<C>(o, one_m, ln);
-                store_elem<C>(tb, o, ln);
-            }
-            load_elem<C>(a, (which ? y : x) + ec * W, ln);
-            store_elem<C>(tb + W, a, ln);
-            regs_to_lds<C>(ln, a);
-#pragma unroll 1
-            for (int k = 2; k < tsize; ++k) {
-                u32 r[C::L];
-                mont_mul<C>(r, a, ln, nn, n0inv);          // base * tab[k-1]
-                store_elem<C>(tb + (size_t)k * W, r, ln);
-                regs_to_lds<C>(ln, r);
-            }
-        }
+        for (int which = 0; which < 2; ++which)
+            window_table<C>(a, which ? tab2 : tab1, tsize, (which ? y : x) + ec * W, one_m, ln, nn, n0inv);
         load_modulus<C>(a, one_m, ln);
-#pragma unroll 1
-        for (int wi = nwin - 1; wi >= 0; --wi) {
-            if (wi != nwin - 1) {
-#pragma unroll 1
-                for (int s = 0; s < wbits; ++s) {
-                    regs_to_lds<C>(ln, a);
-                    mont_sqr<C>(a, a, ln, nn, n0inv);
-                }
-            }
-            if (wi < nwin1) {                              // (uniform over the launch: window counts, not digits, decide)
-                u32 d = exp_digit(ep1, ewords1, wi * wbits, wbits);
-                load_elem_to_lds<C>(ln, tab1 + (size_t)d * W);
-                mont_mul<C>(a, a, ln, nn, n0inv);
-            }
-            if (wi < nwin2) {
-                u32 d = exp_digit(ep2, ewords2, wi * wbits, wbits);
-                load_elem_to_lds<C>(ln, tab2 + (size_t)d * W);
-                mont_mul<C>(a, a, ln, nn, n0inv);
-            }
-        }
+        straus_windows<C>(a, e1 + ec * estride1, ewords1, nwin1, e2 + ec * estride2, ewords2, nwin2, wbits, nwin - 1, 0, tab1, tab2,
+                          ln, nn, n0inv);
         canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
     }
 }
 
 // k_modpow2 for arrays of more than one round of tiles: the same simultaneous power in phases from a queue of (phase, tile)
-// units (see k_modpow_phased -- the queue, the hand-over and the ONE thread-0 region per turn are the same); both tables
-// of a tile live in a table of its own (2 * 2^w rows per element).
+// units (UnitQueue); both tables of a tile live in a table of its own (2 * 2^w rows per element).
 template <class C>
 __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow2_phased(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e1, int ewords1, size_t estride1, int ebits1,
@@ -868,94 +894,33 @@ k_modpow2_phased(u32* __restrict__ out, const u32* __restrict__ x, const u32* __
     Lane<C> ln(lds);
     u32 nn[C::L];
     load_modulus<C>(nn, nmod, ln);
-    const u32 ntiles = (u32)((n + C::EPB - 1) / C::EPB);
-    const u32 nunits = ntiles * (u32)phases;
     const int tsize = 1 << wbits;
     const int nwin1 = (ebits1 + wbits - 1) / wbits, nwin2 = (ebits2 + wbits - 1) / wbits;
     const int nwin = nwin1 > nwin2 ? nwin1 : nwin2;
-    if (threadIdx.x == 0) s_unit = atomicAdd(queue, 1u);
-    __syncthreads();
-    for (;;) {
-        const u32 u = (u32)__builtin_amdgcn_readfirstlane((int)s_unit);
-        if (u >= nunits) break;
-        const int ph = (int)(u / ntiles);
-        const u32 t = u - (u32)ph * ntiles;
-        if (ph > 0) {
-            if (threadIdx.x == 0) {
-                long spins = 0;
-                while (__hip_atomic_load(done + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < (u32)ph) {
-                    if (++spins > (1L << 28)) __builtin_trap();
-                    __builtin_amdgcn_s_sleep(16);
-                }
-            }
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        size_t el = (size_t)t * C::EPB + ln.eslot;
+    UnitQueue q(queue, done, &s_unit, (u32)((n + C::EPB - 1) / C::EPB), phases);
+    while (q.take()) {
+        const int ph = q.ph;
+        size_t el = (size_t)q.t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
-        const u32* ep1 = e1 + ec * estride1;
-        const u32* ep2 = e2 + ec * estride2;
-        u32* tab1 = tab + ((size_t)t * C::EPB + ln.eslot) * (size_t)(2 * tsize) * W;
+        u32* tab1 = tab + el * (size_t)(2 * tsize) * W;
         u32* tab2 = tab1 + (size_t)tsize * W;
         u32 a[C::L];
         if (ph == 0) {
-            // tables: tab[0] = 1, tab[1] = base, tab[k] = tab[k-1] * base
 #pragma unroll 1
-            for (int which = 0; which < 2; ++which) {
-                u32* tb = which ? tab2 : tab1;
-                {
-                    u32 o[C::L];
-                    load_modulus<C>(o, one_m, ln);
-                    store_elem<C>(tb, o, ln);
-                }
-                load_elem<C>(a, (which ? y : x) + ec * W, ln);
-                store_elem<C>(tb + W, a, ln);
-                regs_to_lds<C>(ln, a);
-#pragma unroll 1
-                for (int k = 2; k < tsize; ++k) {
-                    u32 r[C::L];
-                    mont_mul<C>(r, a, ln, nn, n0inv);          // base * tab[k-1]
-                    store_elem<C>(tb + (size_t)k * W, r, ln);
-                    regs_to_lds<C>(ln, r);
-                }
-            }
+            for (int which = 0; which < 2; ++which)
+                window_table<C>(a, which ? tab2 : tab1, tsize, (which ? y : x) + ec * W, one_m, ln, nn, n0inv);
             load_modulus<C>(a, one_m, ln);
         } else {
             load_elem<C>(a, out + ec * W, ln);
         }
         // the windows of this phase: nwin - 1 - nwin ph / P  down to  nwin - nwin (ph + 1) / P
         const int hi = nwin - 1 - (int)((long)nwin * ph / phases), lo = nwin - (int)((long)nwin * (ph + 1) / phases);
-#pragma unroll 1
-        for (int wi = hi; wi >= lo; --wi) {
-            if (wi != nwin - 1) {
-#pragma unroll 1
-                for (int s = 0; s < wbits; ++s) {
-                    regs_to_lds<C>(ln, a);
-                    mont_sqr<C>(a, a, ln, nn, n0inv);
-                }
-            }
-            if (wi < nwin1) {
-                u32 d = exp_digit(ep1, ewords1, wi * wbits, wbits);
-                load_elem_to_lds<C>(ln, tab1 + (size_t)d * W);
-                mont_mul<C>(a, a, ln, nn, n0inv);
-            }
-            if (wi < nwin2) {
-                u32 d = exp_digit(ep2, ewords2, wi * wbits, wbits);
-                load_elem_to_lds<C>(ln, tab2 + (size_t)d * W);
-                mont_mul<C>(a, a, ln, nn, n0inv);
-            }
-        }
-        if (ph == phases - 1) canonicalize<C>(a, nn, ln);
+        straus_windows<C>(a, e1 + ec * estride1, ewords1, nwin1, e2 + ec * estride2, ewords2, nwin2, wbits, hi, lo, tab1, tab2, ln,
+                          nn, n0inv);
+        if (q.last()) canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
-        const bool hand_on = ph < phases - 1;
-        if (hand_on) __threadfence();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (hand_on) (void)__hip_atomic_exchange(done + t, (u32)(ph + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            s_unit = atomicAdd(queue, 1u);
-        }
-        __syncthreads();
+        q.hand_over();
     }
 }
 

@@ -21,6 +21,19 @@ struct SlideStep {
     int idx;
 };
 
+// steps s_lo .. s_hi - 1 of the schedule (wave-uniform: every lane walks the same steps).  (A half-open range: with `s <= s_hi`
+// the compiler lays the loop of k_modpow_shared<Cfg<19, 1>> out with register copies at its edges, 115 registers instead of 76.)
+template <class C>
+__device__ __forceinline__ void slide_steps(u32 (&a)[C::L], const SlideStep* __restrict__ steps, int s_lo, int s_hi,
+                                            const u32* __restrict__ tb, const Lane<C>& ln, const u32 (&nn)[C::L], u32 n0inv) {
+#pragma unroll 1
+    for (int s = s_lo; s < s_hi; ++s) {
+        const int sq = steps[s].sq, idx = steps[s].idx;
+        sqr_times<C>(a, sq, ln, nn, n0inv);
+        if (idx >= 0) mul_by_row<C>(a, tb + (size_t)idx * C::W, ln, nn, n0inv);
+    }
+}
+
 template <class C>
 __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow_shared(u32* __restrict__ out, const u32* __restrict__ x, const SlideStep* __restrict__ steps, int nsteps, int tsize, size_t n,
@@ -36,45 +49,18 @@ k_modpow_shared(u32* __restrict__ out, const u32* __restrict__ x, const SlideSte
         size_t el = t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
-        u32 a[C::L], x2[C::L];
-        // table of odd powers: tab[0] = x, tab[k] = tab[k-1] * x^2
-        load_elem<C>(a, x + ec * W, ln);
-        store_elem<C>(mytab, a, ln);
-        regs_to_lds<C>(ln, a);
-        mont_sqr<C>(x2, a, ln, nn, n0inv);
-#pragma unroll 1
-        for (int k = 1; k < tsize; ++k) {
-            regs_to_lds<C>(ln, a);
-            u32 r[C::L];
-            mont_mul<C>(r, x2, ln, nn, n0inv);         // x^2 * tab[k-1]
-            store_elem<C>(mytab + (size_t)k * W, r, ln);
-#pragma unroll
-            for (int j = 0; j < C::L; ++j) a[j] = r[j];
-        }
-        // the schedule (wave-uniform: every lane walks the same steps)
+        u32 a[C::L];
+        odd_power_table<C>(a, mytab, tsize, x + ec * W, ln, nn, n0inv);
         load_elem<C>(a, mytab + (size_t)steps[0].idx * W, ln);
-#pragma unroll 1
-        for (int s = 1; s < nsteps; ++s) {
-            const int sq = steps[s].sq, idx = steps[s].idx;
-#pragma unroll 1
-            for (int q = 0; q < sq; ++q) {
-                regs_to_lds<C>(ln, a);
-                mont_sqr<C>(a, a, ln, nn, n0inv);
-            }
-            if (idx >= 0) {
-                load_elem_to_lds<C>(ln, mytab + (size_t)idx * W);
-                mont_mul<C>(a, a, ln, nn, n0inv);
-            }
-        }
+        slide_steps<C>(a, steps, 1, nsteps, mytab, ln, nn, n0inv);
         canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
     }
 }
 
 // k_modpow_shared for arrays of more than one round of tiles: the schedule's steps in phases from a queue of (phase, tile) units
-// (see k_modpow_phased, modp_kernels.h: the queue, the hand-over between workgroups and the ONE thread-0 region per turn are the
-// same); a tile's table of odd powers lives in a table of its own.  The decryption factors of a party -- one full-length secret
-// exponent over every ciphertext -- are this kernel's large case.
+// (UnitQueue, modp_kernels.h); a tile's table of odd powers lives in a table of its own.  The decryption factors of a party -- one
+// full-length secret exponent over every ciphertext -- are this kernel's large case.
 template <class C>
 __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow_shared_phased(u32* __restrict__ out, const u32* __restrict__ x, const SlideStep* __restrict__ steps, int nsteps, int tsize,
@@ -86,77 +72,27 @@ k_modpow_shared_phased(u32* __restrict__ out, const u32* __restrict__ x, const S
     Lane<C> ln(lds);
     u32 nn[C::L];
     load_modulus<C>(nn, nmod, ln);
-    const u32 ntiles = (u32)((n + C::EPB - 1) / C::EPB);
-    const u32 nunits = ntiles * (u32)phases;
     const int M = nsteps - 1;                            // steps of the main loop (step 0 is the first table read)
-    if (threadIdx.x == 0) s_unit = atomicAdd(queue, 1u);
-    __syncthreads();
-    for (;;) {
-        const u32 u = (u32)__builtin_amdgcn_readfirstlane((int)s_unit);
-        if (u >= nunits) break;
-        const int ph = (int)(u / ntiles);
-        const u32 t = u - (u32)ph * ntiles;
-        if (ph > 0) {
-            if (threadIdx.x == 0) {
-                long spins = 0;
-                while (__hip_atomic_load(done + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < (u32)ph) {
-                    if (++spins > (1L << 28)) __builtin_trap();
-                    __builtin_amdgcn_s_sleep(16);
-                }
-            }
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        size_t el = (size_t)t * C::EPB + ln.eslot;
+    UnitQueue q(queue, done, &s_unit, (u32)((n + C::EPB - 1) / C::EPB), phases);
+    while (q.take()) {
+        const int ph = q.ph;
+        size_t el = (size_t)q.t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
-        u32* mytab = tab + ((size_t)t * C::EPB + ln.eslot) * (size_t)tsize * W;
+        u32* mytab = tab + el * (size_t)tsize * W;
         u32 a[C::L];
         if (ph == 0) {
-            u32 x2[C::L];
-            // table of odd powers: tab[0] = x, tab[k] = tab[k-1] * x^2
-            load_elem<C>(a, x + ec * W, ln);
-            store_elem<C>(mytab, a, ln);
-            regs_to_lds<C>(ln, a);
-            mont_sqr<C>(x2, a, ln, nn, n0inv);
-#pragma unroll 1
-            for (int k = 1; k < tsize; ++k) {
-                regs_to_lds<C>(ln, a);
-                u32 r[C::L];
-                mont_mul<C>(r, x2, ln, nn, n0inv);         // x^2 * tab[k-1]
-                store_elem<C>(mytab + (size_t)k * W, r, ln);
-#pragma unroll
-                for (int j = 0; j < C::L; ++j) a[j] = r[j];
-            }
+            odd_power_table<C>(a, mytab, tsize, x + ec * W, ln, nn, n0inv);
             load_elem<C>(a, mytab + (size_t)steps[0].idx * W, ln);
         } else {
             load_elem<C>(a, out + ec * W, ln);
         }
-        // the steps of this phase: 1 + M ph / P  up to  M (ph + 1) / P
-        const int s_lo = 1 + (int)((long)M * ph / phases), s_hi = (int)((long)M * (ph + 1) / phases);
-#pragma unroll 1
-        for (int s = s_lo; s <= s_hi; ++s) {
-            const int sq = steps[s].sq, idx = steps[s].idx;
-#pragma unroll 1
-            for (int q = 0; q < sq; ++q) {
-                regs_to_lds<C>(ln, a);
-                mont_sqr<C>(a, a, ln, nn, n0inv);
-            }
-            if (idx >= 0) {
-                load_elem_to_lds<C>(ln, mytab + (size_t)idx * W);
-                mont_mul<C>(a, a, ln, nn, n0inv);
-            }
-        }
-        if (ph == phases - 1) canonicalize<C>(a, nn, ln);
+        // the steps of this phase: 1 + M ph / P  up to  M (ph + 1) / P (s_hi: one past it)
+        const int s_lo = 1 + (int)((long)M * ph / phases), s_hi = 1 + (int)((long)M * (ph + 1) / phases);
+        slide_steps<C>(a, steps, s_lo, s_hi, mytab, ln, nn, n0inv);
+        if (q.last()) canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
-        const bool hand_on = ph < phases - 1;
-        if (hand_on) __threadfence();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (hand_on) (void)__hip_atomic_exchange(done + t, (u32)(ph + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            s_unit = atomicAdd(queue, 1u);
-        }
-        __syncthreads();
+        q.hand_over();
     }
 }
 
@@ -190,34 +126,9 @@ __device__ __forceinline__ void modpow_job_tile(const ModpowJob& J, size_t t, in
     size_t ec = live ? el : J.n - 1;
     const u32* ep = J.e + ec * J.estride;
     u32 a[C::L];
-    load_elem<C>(a, J.x + ec * W, ln);
-    {
-        u32 o[C::L];
-        load_modulus<C>(o, one_m, ln);
-        store_elem<C>(mytab, o, ln);
-    }
-    store_elem<C>(mytab + W, a, ln);
-    regs_to_lds<C>(ln, a);
-#pragma unroll 1
-    for (int k = 2; k < tsize; ++k) {
-        u32 r[C::L];
-        mont_mul<C>(r, a, ln, nn, n0inv);                            // x * tab[k-1]
-        store_elem<C>(mytab + (size_t)k * W, r, ln);
-        regs_to_lds<C>(ln, r);
-    }
-    u32 d = exp_digit(ep, J.ewords, (nwin - 1) * wbits, wbits);
-    load_elem<C>(a, mytab + (size_t)d * W, ln);
-#pragma unroll 1
-    for (int wi = nwin - 2; wi >= 0; --wi) {
-#pragma unroll 1
-        for (int s = 0; s < wbits; ++s) {
-            regs_to_lds<C>(ln, a);
-            mont_sqr<C>(a, a, ln, nn, n0inv);
-        }
-        d = exp_digit(ep, J.ewords, wi * wbits, wbits);
-        load_elem_to_lds<C>(ln, mytab + (size_t)d * W);
-        mont_mul<C>(a, a, ln, nn, n0inv);
-    }
+    window_table<C>(a, mytab, tsize, J.x + ec * W, one_m, ln, nn, n0inv);
+    load_elem<C>(a, mytab + (size_t)exp_digit(ep, J.ewords, (nwin - 1) * wbits, wbits) * W, ln);      // the top window
+    fixed_windows<C>(a, ep, J.ewords, wbits, nwin - 2, 0, mytab, ln, nn, n0inv);
     canonicalize<C>(a, nn, ln);
     if (live) store_elem<C>(J.out + el * W, a, ln);
 }

@@ -1640,6 +1640,50 @@ static int pick_window(int ebits) {
     return best;
 }
 
+// How a power kernel over n elements of geometry m is launched: tile by tile on `grid` workgroups with a table per lane slot in
+// ctx->scratch (the plain kernel), or -- more than one round of tiles -- in phases from a queue of (phase, tile) units (the phased
+// kernel), so that the launch ends with a tail of one unit instead of one whole tile: 10^6 elements are 7.63 rounds and cost 8
+// otherwise.  The three powers (modpow_words, modpow_shared, modpow2) plan here.
+struct PhasePlan {
+    unsigned max_blocks;       // workgroup slots of the device: the grid of the phased kernel
+    unsigned grid;             // the grid of the plain kernel
+    size_t epb, ntiles;
+    int phases = 1;            // > 1 after split(): launch the phased kernel with table(), queue() and done()
+    DevTmp tab, sync_words;
+    PhasePlan(vmn_ctx* ctx, const vmn_modulus& m, size_t n)
+        : max_blocks((unsigned)(ctx->num_cus * blocks_per_cu(m))), epb((size_t)(BLOCK / m.LPE)), ntiles((n + epb - 1) / epb), tab(ctx),
+          sync_words(ctx) {
+        if (const char* mb = getenv("VMN_MODPOW_MAX_BLOCKS")) {       // test hook: a "device" of few workgroup slots, so that small arrays take the phased kernel
+            const int v = atoi(mb);
+            if (v >= 1) max_blocks = std::min<unsigned>(max_blocks, (unsigned)v);
+        }
+        grid = std::min<unsigned>(egrid(m, n), max_blocks);
+    }
+    // bytes of the plain kernel's tables: `rows` rows per lane slot
+    size_t slot_tables_bytes(const vmn_modulus& m, size_t rows) const { return (size_t)grid * epb * rows * elem_words(m) * sizeof(uint32_t); }
+    // Cut the power into phases: at most the environment's count (default 16; 1 = always the plain kernel) and at most
+    // `cuttable_steps`, the windows or steps of its main loop.  A phased launch needs a table per ELEMENT, `rows` rows each
+    // (9.5 GB for 10^6 x 2048 bits, w = 5): where that does not fit -- more than 64 GB, or the allocation fails -- phases stays 1
+    // and the power runs tile by tile with a table per lane slot, as it always did.
+    int split(vmn_ctx* ctx, const vmn_modulus& m, int cuttable_steps, size_t rows) {
+        static const int phases_env = [] {
+            const char* e = getenv("VMN_MODPOW_PHASES");
+            return e && *e ? std::max(1, atoi(e)) : 16;
+        }();
+        if (ntiles <= (size_t)max_blocks || ntiles >= ((size_t)1 << 26)) return VMN_OK;      // (unit indices are 32-bit)
+        const int want = std::min(phases_env, std::max(1, cuttable_steps));
+        const size_t tab_bytes = ntiles * epb * rows * elem_words(m) * sizeof(uint32_t);
+        if (want == 1 || tab_bytes > ((size_t)64 << 30) || tab.alloc(tab_bytes) != VMN_OK) return VMN_OK;
+        VMN_TRY(sync_words.alloc((ntiles + 1) * sizeof(uint32_t)));     // the queue's counter, then a word per tile
+        VMN_TRY(dev_zero(ctx, sync_words.p, (ntiles + 1) * sizeof(uint32_t)));
+        phases = want;
+        return VMN_OK;
+    }
+    uint32_t* table() { return tab.as<uint32_t>(); }
+    uint32_t* queue() { return sync_words.as<uint32_t>(); }
+    uint32_t* done() { return queue() + 1; }
+};
+
 // out[i] = x[i]^e[i] with packed-word exponents already on the device
 static int modpow_words(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, const uint32_t* e_words, int ewords,
                         size_t estride, int ebits, size_t n, uint32_t* out) {
@@ -1663,51 +1707,24 @@ static int modpow_words(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, 
     }
     int wbits = pick_window(ebits);
     const vmn_modulus& m = geom(ctx, m0, n);
-    unsigned max_blocks = (unsigned)(ctx->num_cus * blocks_per_cu(m));
-    unsigned grid = std::min<unsigned>(egrid(m, n), max_blocks);
-    size_t tab_bytes = (size_t)grid * (BLOCK / m.LPE) * ((size_t)1 << wbits) * elem_words(m) * sizeof(uint32_t);
-    VMN_TRY(ensure_scratch(ctx, tab_bytes));
-    {
-        const int nwin = (ebits + wbits - 1) / wbits;
-        note_work(ctx, m, (double)n * (nwin - 1 + (1 << wbits) - 2), (double)n * (nwin - 1) * wbits);
-    }
+    const int nwin = (ebits + wbits - 1) / wbits;
+    PhasePlan pl(ctx, m, n);
+    VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)1 << wbits)));
+    note_work(ctx, m, (double)n * (nwin - 1 + (1 << wbits) - 2), (double)n * (nwin - 1) * wbits);
+    VMN_TRY(pl.split(ctx, m, nwin - 1, (size_t)1 << wbits));
     int rc = VMN_ERR_ARG;
-    // More than one round of tiles: the power in phases from a queue of (phase, tile) units (k_modpow_phased), so that the
-    // launch ends with a tail of one unit instead of one whole tile -- 10^6 elements are 7.63 rounds and cost 8 otherwise.
-    // VMN_MODPOW_PHASES: 1 = one phase (k_modpow); default 16.
-    static const int phases_env = [] {
-        const char* e = getenv("VMN_MODPOW_PHASES");
-        return e && *e ? std::max(1, atoi(e)) : 16;
-    }();
-    if (const char* mb = getenv("VMN_MODPOW_MAX_BLOCKS")) {       // test hook: a "device" of few workgroup slots, so that small arrays take the phased kernel
-        const int v = atoi(mb);
-        if (v >= 1) max_blocks = std::min<unsigned>(max_blocks, (unsigned)v);
-    }
-    const size_t epb = (size_t)(BLOCK / m.LPE);
-    const size_t ntiles = (n + epb - 1) / epb;
-    const int main_windows = (ebits + wbits - 1) / wbits - 1;
-    const int phases = ntiles > (size_t)max_blocks && ntiles < ((size_t)1 << 26) ? std::min(phases_env, std::max(1, main_windows)) : 1;
-    // a window table per ELEMENT (9.5 GB for 10^6 x 2048 bits, w = 5): where that does not fit -- more than 64 GB, or the
-    // allocation fails -- the power runs tile by tile with a table per lane slot, as it always did
-    const size_t ptab_bytes = ntiles * epb * ((size_t)1 << wbits) * elem_words(m) * sizeof(uint32_t);
-    DevTmp ptab(ctx), sync_words(ctx);
-    bool phased = phases > 1 && ptab_bytes <= ((size_t)64 << 30);
-    if (phased && ptab.alloc(ptab_bytes) != VMN_OK) phased = false;
-    if (phased) {
-        VMN_TRY(sync_words.alloc((ntiles + 1) * sizeof(uint32_t)));
-        VMN_TRY(dev_zero(ctx, sync_words.p, (ntiles + 1) * sizeof(uint32_t)));
-        uint32_t* queue = sync_words.as<uint32_t>();
+    if (pl.phases > 1) {
 #define X(S_, NW_, LPE_)                                                                                                 \
     if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow_phased<Cfg<S_, LPE_>>, max_blocks, lds_bytes(m), out, x, e_words, ewords, estride, ebits, \
-                    wbits, n, m.d_n, m.n0inv, m.d_one, ptab.as<uint32_t>(), phases, queue, queue + 1);
+        rc = launch(ctx, "modpow", k_modpow_phased<Cfg<S_, LPE_>>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, estride, ebits, \
+                    wbits, n, m.d_n, m.n0inv, m.d_one, pl.table(), pl.phases, pl.queue(), pl.done());
         VMN_FOR_SIZES(X)
 #undef X
         return rc;
     }
 #define X(S_, NW_, LPE_)                                                                                                 \
     if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow<Cfg<S_, LPE_>>, grid, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, \
+        rc = launch(ctx, "modpow", k_modpow<Cfg<S_, LPE_>>, pl.grid, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, \
                     n, m.d_n, m.n0inv, m.d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
     VMN_FOR_SIZES(X)
 #undef X
@@ -1758,48 +1775,27 @@ static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x,
     }
     const int tsize = 1 << (w - 1);
     const vmn_modulus& m = geom(ctx, m0, n);
-    unsigned max_blocks = (unsigned)(ctx->num_cus * blocks_per_cu(m));
-    if (const char* mb = getenv("VMN_MODPOW_MAX_BLOCKS")) {       // (test hook, see modpow_words)
-        const int v = atoi(mb);
-        if (v >= 1) max_blocks = std::min<unsigned>(max_blocks, (unsigned)v);
-    }
-    const unsigned grid = std::min<unsigned>(egrid(m, n), max_blocks);
-    const size_t tab_bytes = (size_t)grid * (BLOCK / m.LPE) * (size_t)tsize * elem_words(m) * sizeof(uint32_t);
-    VMN_TRY(ensure_scratch(ctx, tab_bytes));
+    PhasePlan pl(ctx, m, n);
+    VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)tsize)));
     DevTmp dsteps(ctx);
     VMN_TRY(dsteps.alloc(steps.size() * sizeof(SlideStep)));
     VMN_TRY(h2d(ctx, dsteps.p, steps.data(), steps.size() * sizeof(SlideStep)));
     note_work(ctx, m, (double)n * (double)(mults + tsize - 1), (double)n * (double)(squarings + 1));
+    VMN_TRY(pl.split(ctx, m, (int)steps.size() - 1, (size_t)tsize));
     int rc = VMN_ERR_ARG;
-    // more than one round of tiles: in phases from a queue of units (k_modpow_shared_phased; modpow_words has the reasons)
-    {
-        const size_t epb = (size_t)(BLOCK / m.LPE), ntiles = (n + epb - 1) / epb;
-        static const int phases_env3 = [] {
-            const char* e = getenv("VMN_MODPOW_PHASES");
-            return e && *e ? std::max(1, atoi(e)) : 16;
-        }();
-        const int phases = ntiles > (size_t)max_blocks && ntiles < ((size_t)1 << 26) ? std::min(phases_env3, std::max(1, (int)steps.size() - 1)) : 1;
-        const size_t ptab_bytes = ntiles * epb * (size_t)tsize * elem_words(m) * sizeof(uint32_t);
-        DevTmp ptab(ctx), sync_words(ctx);
-        bool phased = phases > 1 && ptab_bytes <= ((size_t)64 << 30);
-        if (phased && ptab.alloc(ptab_bytes) != VMN_OK) phased = false;
-        if (phased) {
-            VMN_TRY(sync_words.alloc((ntiles + 1) * sizeof(uint32_t)));
-            VMN_TRY(dev_zero(ctx, sync_words.p, (ntiles + 1) * sizeof(uint32_t)));
-            uint32_t* queue = sync_words.as<uint32_t>();
+    if (pl.phases > 1) {
 #define X(S_, NW_, LPE_)                                                                                                 \
     if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow_shared_phased<Cfg<S_, LPE_>>, max_blocks, lds_bytes(m), out, x,                  \
-                    (const SlideStep*)dsteps.as<SlideStep>(), (int)steps.size(), tsize, n, m.d_n, m.n0inv, ptab.as<uint32_t>(), \
-                    phases, queue, queue + 1);
-            VMN_FOR_SIZES(X)
+        rc = launch(ctx, "modpow", k_modpow_shared_phased<Cfg<S_, LPE_>>, pl.max_blocks, lds_bytes(m), out, x,               \
+                    (const SlideStep*)dsteps.as<SlideStep>(), (int)steps.size(), tsize, n, m.d_n, m.n0inv, pl.table(), pl.phases,  \
+                    pl.queue(), pl.done());
+        VMN_FOR_SIZES(X)
 #undef X
-            return rc;
-        }
+        return rc;
     }
 #define X(S_, NW_, LPE_)                                                                                                 \
     if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow_shared<Cfg<S_, LPE_>>, grid, lds_bytes(m), out, x, (const SlideStep*)dsteps.as<SlideStep>(), \
+        rc = launch(ctx, "modpow", k_modpow_shared<Cfg<S_, LPE_>>, pl.grid, lds_bytes(m), out, x, (const SlideStep*)dsteps.as<SlideStep>(), \
                     (int)steps.size(), tsize, n, m.d_n, m.n0inv, reinterpret_cast<uint32_t*>(ctx->scratch));
     VMN_FOR_SIZES(X)
 #undef X
@@ -2061,6 +2057,38 @@ extern "C" int vmn_garray_exp_scalar(const vmn_garray* x, const uint8_t* e_be, s
     return VMN_OK;
 }
 
+// out[i] = x[i]^e * y[i]^f[i] over a modular group, exponents in packed words on the device: e one exponent of ewords words,
+// f[i] fwords words each
+static int modpow2(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, const uint32_t* e_words, int ewords, int ebits,
+                   const uint32_t* y, const uint32_t* f_words, int fwords, int fbits, size_t n, uint32_t* out) {
+    const vmn_modulus& m = geom(ctx, m0, n);
+    const int wbits = std::min(pick_window(std::max(ebits, fbits)), 5);       // two tables per lane
+    const int nw1 = (ebits + wbits - 1) / wbits, nw2 = (fbits + wbits - 1) / wbits;
+    PhasePlan pl(ctx, m, n);
+    VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)2 << wbits)));
+    VMN_TRY(pl.split(ctx, m, std::max(nw1, nw2), (size_t)2 << wbits));
+    note_work(ctx, m, (double)n * (nw1 + nw2 + 2 * ((1 << wbits) - 2)), (double)n * (std::max(nw1, nw2) - 1) * wbits);
+    int rc = VMN_ERR_ARG;
+    if (pl.phases > 1) {
+#define X(S_, NW_, LPE_)                                                                                                       \
+    if (m.S == S_)                                                                                                             \
+        rc = launch(ctx, "modpow", k_modpow2_phased<Cfg<S_, LPE_>>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, (size_t)0,  \
+                    ebits, y, f_words, fwords, (size_t)fwords, fbits, wbits, n, m.d_n, m.n0inv, m.d_one, pl.table(), pl.phases,    \
+                    pl.queue(), pl.done());
+        VMN_FOR_SIZES(X)
+#undef X
+        return rc;
+    }
+#define X(S_, NW_, LPE_)                                                                                                       \
+    if (m.S == S_)                                                                                                             \
+        rc = launch(ctx, "modpow", k_modpow2<Cfg<S_, LPE_>>, pl.grid, lds_bytes(m), out, x, e_words, ewords, (size_t)0, ebits, y,    \
+                    f_words, fwords, (size_t)fwords, fbits, wbits, n, m.d_n, m.n0inv, m.d_one,                                \
+                    reinterpret_cast<uint32_t*>(ctx->scratch));
+    VMN_FOR_SIZES(X)
+#undef X
+    return rc;
+}
+
 // out[i] = x[i]^e * y[i]^f[i]: one simultaneous power (k_modpow2), the squarings shared between the two exponents.
 // The verifiers' check (B): B_i^v (B_{i-1}^{-1})^{k_E,i}.  Modular groups only.
 extern "C" int vmn_garray_exp2(const vmn_garray* x, const uint8_t* e_be, size_t ebytes, const vmn_garray* y, const vmn_rarray* f,
@@ -2113,56 +2141,7 @@ extern "C" int vmn_garray_exp2(const vmn_garray* x, const uint8_t* e_be, size_t 
 #undef X
         }
     } else if (rc == VMN_OK) {
-        const vmn_modulus& m = geom(ctx, g->P, n);
-        const int wbits = std::min(pick_window(std::max(ebits, fbits)), 5);       // two tables per lane
-        unsigned max_blocks = (unsigned)(ctx->num_cus * blocks_per_cu(m));
-        if (const char* mb = getenv("VMN_MODPOW_MAX_BLOCKS")) {       // (test hook, see modpow_words)
-            const int v = atoi(mb);
-            if (v >= 1) max_blocks = std::min<unsigned>(max_blocks, (unsigned)v);
-        }
-        const unsigned grid = std::min<unsigned>(egrid(m, n), max_blocks);
-        const size_t tab_bytes = (size_t)grid * (BLOCK / m.LPE) * ((size_t)2 << wbits) * elem_words(m) * sizeof(uint32_t);
-        rc = ensure_scratch(ctx, tab_bytes);
-        // more than one round of tiles: in phases from a queue of units (k_modpow2_phased; modpow_words has the reasons)
-        const size_t epb = (size_t)(BLOCK / m.LPE), ntiles = (n + epb - 1) / epb;
-        const int nwin_all = (std::max(ebits, fbits) + wbits - 1) / wbits;
-        static const int phases_env2 = [] {
-            const char* e = getenv("VMN_MODPOW_PHASES");
-            return e && *e ? std::max(1, atoi(e)) : 16;
-        }();
-        const int phases = ntiles > (size_t)max_blocks && ntiles < ((size_t)1 << 26) ? std::min(phases_env2, std::max(1, nwin_all)) : 1;
-        const size_t ptab_bytes = ntiles * epb * ((size_t)2 << wbits) * elem_words(m) * sizeof(uint32_t);
-        DevTmp ptab(ctx), sync_words(ctx);
-        bool phased = rc == VMN_OK && phases > 1 && ptab_bytes <= ((size_t)64 << 30);
-        if (phased && ptab.alloc(ptab_bytes) != VMN_OK) phased = false;
-        if (phased) rc = sync_words.alloc((ntiles + 1) * sizeof(uint32_t));
-        if (phased && rc == VMN_OK) rc = dev_zero(ctx, sync_words.p, (ntiles + 1) * sizeof(uint32_t));
-        if (phased && rc == VMN_OK) {
-            const int nw1 = (ebits + wbits - 1) / wbits, nw2 = (fbits + wbits - 1) / wbits;
-            note_work(ctx, m, (double)n * (nw1 + nw2 + 2 * ((1 << wbits) - 2)), (double)n * (std::max(nw1, nw2) - 1) * wbits);
-            uint32_t* queue = sync_words.as<uint32_t>();
-            rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                                       \
-    if (m.S == S_)                                                                                                             \
-        rc = launch(ctx, "modpow", k_modpow2_phased<Cfg<S_, LPE_>>, max_blocks, lds_bytes(m), r->d, (const uint32_t*)x->d,        \
-                    (const uint32_t*)ew.as<uint32_t>(), ewords, (size_t)0, ebits, (const uint32_t*)y->d,                         \
-                    (const uint32_t*)fw.as<uint32_t>(), g->Q.NW, (size_t)g->Q.NW, fbits, wbits, n, m.d_n, m.n0inv, m.d_one,    \
-                    ptab.as<uint32_t>(), phases, queue, queue + 1);
-            VMN_FOR_SIZES(X)
-#undef X
-        } else if (rc == VMN_OK) {
-            const int nw1 = (ebits + wbits - 1) / wbits, nw2 = (fbits + wbits - 1) / wbits;
-            note_work(ctx, m, (double)n * (nw1 + nw2 + 2 * ((1 << wbits) - 2)), (double)n * (std::max(nw1, nw2) - 1) * wbits);
-            rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                                       \
-    if (m.S == S_)                                                                                                             \
-        rc = launch(ctx, "modpow", k_modpow2<Cfg<S_, LPE_>>, grid, lds_bytes(m), r->d, (const uint32_t*)x->d,                      \
-                    (const uint32_t*)ew.as<uint32_t>(), ewords, (size_t)0, ebits, (const uint32_t*)y->d,                         \
-                    (const uint32_t*)fw.as<uint32_t>(), g->Q.NW, (size_t)g->Q.NW, fbits, wbits, n, m.d_n, m.n0inv, m.d_one,    \
-                    reinterpret_cast<uint32_t*>(ctx->scratch));
-            VMN_FOR_SIZES(X)
-#undef X
-        }
+        rc = modpow2(ctx, g->P, x->d, ew.as<uint32_t>(), ewords, ebits, y->d, fw.as<uint32_t>(), g->Q.NW, fbits, n, r->d);
     }
     if (rc != VMN_OK) {
         vmn_garray_free(r);
