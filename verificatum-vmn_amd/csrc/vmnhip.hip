@@ -84,6 +84,35 @@ extern "C" const char* vmn_version(void) { return "vmnhip 0.1 (gfx950, radix-2^2
 #define VMN_FOR_CURVES(X) X(9, 7, EC_NIST) X(10, 8, EC_NIST) X(15, 12, EC_NIST) X(21, 17, EC_NIST) \
     X(9, 7, EC_GENERAL) X(10, 8, EC_GENERAL) X(13, 10, EC_GENERAL) X(15, 12, EC_GENERAL) X(21, 17, EC_GENERAL)
 
+// The two lists above are expanded here and nowhere else: a launch site passes a generic lambda and receives the geometry
+// as types, so it names its kernel as k<C> or k<C, W::NW> and leaves out with `if constexpr` what does not exist for C.
+template <int NW_>
+struct Words {
+    static constexpr int NW = NW_;
+};
+template <int S_, int NW_, int KIND_>
+struct CurveCfg {
+    static constexpr int S = S_, NW = NW_, KIND = KIND_;
+};
+// f(Cfg<S, LPE>{}, Words<NW>{}) for the geometry m is in, as it stands (no choice by size); VMN_ERR_ARG if none was built
+template <class F>
+static int with_cfg(const vmn_modulus& m, F&& f) {
+#define X(S_, NW_, LPE_) \
+    if (m.S == S_) return f(Cfg<S_, LPE_>{}, Words<NW_>{});
+    VMN_FOR_SIZES(X)
+#undef X
+    return VMN_ERR_ARG;
+}
+// f(CurveCfg<S, NW, KIND>{}) for the limb count and the kind of m's curve; VMN_ERR_ARG if none was built
+template <class F>
+static int with_curve(const vmn_modulus& m, F&& f) {
+#define X(S_, NW_, K_) \
+    if (m.ec->S == S_ && m.ec->kind == K_) return f(CurveCfg<S_, NW_, K_>{});
+    VMN_FOR_CURVES(X)
+#undef X
+    return VMN_ERR_ARG;
+}
+
 static bool size_for_bits(int nbits, int* S, int* NW, int* LPE) {
     const int sizes[][4] = {{256, 10, 8, 1}, {384, 14, 12, 1}, {512, 19, 16, 1}, {1024, 37, 32, 1}, {2048, 74, 64, 1},
                             {3072, 110, 96, 2}, {4096, 148, 128, 4}, {8192, 296, 256, 8}, {16384, 592, 512, 16}};
@@ -138,27 +167,21 @@ static const vmn_modulus& geom(const vmn_ctx* ctx, const vmn_modulus& m, size_t 
     if (!m.wide || root->wide_max == 0) return m;
     return (always || items <= root->wide_max) ? *m.wide : m;
 }
-// the non-curve launch sites: X sees `m` = the geometry chosen for `items`
-#define VMN_DISPATCH(items, X)                              \
-    {                                                       \
-        const vmn_modulus& m_base__ = m;                    \
-        const vmn_modulus& m = geom(ctx, m_base__, (items)); \
-        VMN_FOR_SIZES(X)                                    \
-    }
-
+// the non-curve launch sites: f(cfg, words, m) with m = the geometry chosen for `items`
+template <class F>
+static int with_geom(const vmn_ctx* ctx, const vmn_modulus& m0, size_t items, F&& f, bool always = false) {
+    const vmn_modulus& m = geom(ctx, m0, items, always);
+    return with_cfg(m, [&](auto c, auto w) { return f(c, w, m); });
+}
 static size_t lds_bytes(const vmn_modulus& m) { return (size_t)m.S * (BLOCK / m.LPE) * sizeof(u32); }
 static int blocks_per_cu(const vmn_modulus&) { return 2; }
 
 // ------------------------------------------------------------------------------------------------
 // launch helper: dynamic LDS attribute, stream, optional event timing per kernel family
 // ------------------------------------------------------------------------------------------------
+// the launch itself with its timing record and error check; launch() and launch_light() below differ in the LDS alone
 template <typename... KArgs, typename... Args>
-static int launch(vmn_ctx* ctx, const char* family, void (*kernel)(KArgs...), unsigned grid, size_t lds, Args... args) {
-    const void* kp = reinterpret_cast<const void*>(kernel);
-    if (!ctx->lds_attr_set.count(kp)) {
-        VMN_HIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->lds_attr_set.insert(kp);
-    }
+static int launch_timed(vmn_ctx* ctx, const char* family, void (*kernel)(KArgs...), unsigned grid, size_t lds, Args... args) {
     TimingRec rec;
     if (ctx->timing) {
         rec.family = family;
@@ -177,14 +200,23 @@ static int launch(vmn_ctx* ctx, const char* family, void (*kernel)(KArgs...), un
     }
     return VMN_OK;
 }
+template <typename... KArgs, typename... Args>
+static int launch(vmn_ctx* ctx, const char* family, void (*kernel)(KArgs...), unsigned grid, size_t lds, Args... args) {
+    const void* kp = reinterpret_cast<const void*>(kernel);
+    if (!ctx->lds_attr_set.count(kp)) {
+        VMN_HIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ctx->lds_attr_set.insert(kp);
+    }
+    return launch_timed(ctx, family, kernel, grid, lds, args...);
+}
 
 // Work accounting for the roofline of the proof legs (bench.py): the number of v_mad_u64_u32 multiply-adds the NEXT
 // launch executes, from the number of Montgomery products / squarings its lanes perform.  A product of S limbs is 2 S^2
 // multiply-adds (multiplication + reduction half); a squaring S^2 (reduction) + S (S + LPE SQR_BLK) / 2 (block-symmetric
 // multiplication half, summed over the LPE lanes of the element).  Curve points: field products
 // (S = 10 / 15), 16 per addition (11M + 5S), 8 per doubling (3M + 5S).  Only recorded while timing is on.
-static int note_work(vmn_ctx* ctx, const vmn_modulus& m, double products, double squarings = 0, double canon_products = -1) {
-    if (!ctx->timing) return 0;
+static void note_work(vmn_ctx* ctx, const vmn_modulus& m, double products, double squarings = 0, double canon_products = -1) {
+    if (!ctx->timing) return;
     const double S = m.ec ? (double)m.ec->S : (double)m.S;              // columns
     const double Rw = m.ec ? S : (double)m.rows;                         // rows (< S in a wide geometry)
     // the same products priced in SURVEY.md §8d's unit: 32 x 32-bit multiply-accumulates of a product / squaring on
@@ -201,11 +233,10 @@ static int note_work(vmn_ctx* ctx, const vmn_modulus& m, double products, double
         const bool known = m.ec->kind == EC_NIST;
         const double nz = known && m.ec->S == 10 ? 7 : known && m.ec->S == 15 ? 12 : S;   // (P-256: 6 limbs + the carry product of the wide-digit rows)
         ctx->next_mads = (products + squarings) * (S * S + S * nz);
-        return 0;
+        return;
     }
     const double sq = Rw * S + Rw * (S + SQR_BLK * m.LPE) / 2;           // block-symmetric in every geometry
     ctx->next_mads = products * 2 * Rw * S + squarings * sq;
-    return 0;                                   // (an int so that a launch inside a macro can be written  note_work(..) ? 0 : launch(..))
 }
 // in field products (S^2 + S nz multiply-adds, see note_work): a product 1, a squaring ~0.775 (symmetric), a zero test 0.5 (reduction only)
 // add = 11M + 5S + zero test, mixed add = 7M + 4S + zero test, doubling = 3M + 5S, normalising one point ~7 + inversion / K
@@ -222,23 +253,7 @@ static unsigned light_grid(vmn_ctx* ctx, size_t work_items) {
 // plain (non-LDS) kernel launch with timing
 template <typename... KArgs, typename... Args>
 static int launch_light(vmn_ctx* ctx, const char* family, void (*kernel)(KArgs...), unsigned grid, Args... args) {
-    TimingRec rec;
-    if (ctx->timing) {
-        rec.family = family;
-        rec.mads = ctx->next_mads;
-        rec.canon = ctx->next_canon;
-        VMN_HIP(hipEventCreate(&rec.start));
-        VMN_HIP(hipEventCreate(&rec.stop));
-        VMN_HIP(hipEventRecord(rec.start, ctx->stream));
-    }
-    ctx->next_mads = ctx->next_canon = 0;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, static_cast<KArgs>(args)...);
-    VMN_HIP(hipGetLastError());
-    if (ctx->timing) {
-        VMN_HIP(hipEventRecord(rec.stop, ctx->stream));
-        ctx->recs.push_back(rec);
-    }
-    return VMN_OK;
+    return launch_timed(ctx, family, kernel, grid, (size_t)0, args...);
 }
 
 // A mark in the timing report: family `name` counts one launch of no duration -- which of two kernels of ONE family a call took
@@ -1414,21 +1429,17 @@ static int import_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const ui
     else VMN_HIP(hipMemcpyAsync(raw.p, be, n * stride, hipMemcpyHostToDevice, ctx->stream));
     VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
     note_work(ctx, m, (m.ec ? 7.0 : 1.0) * (double)n);
-    int rc = VMN_ERR_ARG;
+    int rc;
     if (m.ec) {
-#define X(S_, NW_, K_)                                                                                               \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                           \
-        rc = launch_light(ctx, "import", k_ec_import<S_, NW_, K_>, grid_for(n), d_out, (const uint8_t*)raw.as<uint8_t>(), \
-                          nbytes, stride, leaf_hdr, n, ecdev(m.ec), ctx->flags);
-        VMN_FOR_CURVES(X)
-#undef X
+        rc = with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "import", k_ec_import<E::S, E::NW, E::KIND>, grid_for(n), d_out, (const uint8_t*)raw.as<uint8_t>(),
+                                nbytes, stride, leaf_hdr, n, ecdev(m.ec), ctx->flags);
+        });
     } else {
-#define X(S_, NW_, LPE_)                                                                                              \
-    if (m.S == S_)                                                                                              \
-        rc = launch(ctx, "import", k_import_be<Cfg<S_, LPE_>, NW_>, egrid(m, n), lds_bytes(m), d_out, raw.as<uint8_t>(), \
-                    nbytes, stride, leaf_hdr, n, m.d_n, m.n0inv, m.d_rr, ctx->flags);
-    VMN_DISPATCH(n, X)
-#undef X
+        rc = with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+            return launch(ctx, "import", k_import_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), d_out, raw.as<uint8_t>(), nbytes, stride,
+                          leaf_hdr, n, mg.d_n, mg.n0inv, mg.d_rr, ctx->flags);
+        });
     }
     VMN_TRY(rc);
     if (checked_on_host) return VMN_OK;
@@ -1515,21 +1526,17 @@ static int export_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const ui
     }
     if (ec_rows_affine) note_work(ctx, m, 2.0 * (double)n);
     else note_work(ctx, m, m.ec ? 8.0 * (double)n : (double)n, m.ec ? (double)m.nbits * (double)n : 0.0);     // curves: one Fermat inversion per point
-    int rc = VMN_ERR_ARG;
+    int rc;
     if (m.ec) {
-#define X(S_, NW_, K_)                                                                                           \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                       \
-        rc = launch_light(ctx, "export", k_ec_export<S_, NW_, K_>, grid_for(n), raw.as<uint8_t>(), nbytes, stride, \
-                          leaf_hdr | ec_rows_affine, d_in, n, ecdev(m.ec));
-        VMN_FOR_CURVES(X)
-#undef X
+        rc = with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "export", k_ec_export<E::S, E::NW, E::KIND>, grid_for(n), raw.as<uint8_t>(), nbytes, stride,
+                                leaf_hdr | ec_rows_affine, d_in, n, ecdev(m.ec));
+        });
     } else {
-#define X(S_, NW_, LPE_)                                                                                          \
-    if (m.S == S_)                                                                                          \
-        rc = launch(ctx, "export", k_export_be<Cfg<S_, LPE_>, NW_>, egrid(m, n), lds_bytes(m), raw.as<uint8_t>(),    \
-                    nbytes, stride, leaf_hdr, d_in, n, m.d_n, m.n0inv);
-    VMN_DISPATCH(n, X)
-#undef X
+        rc = with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+            return launch(ctx, "export", k_export_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), raw.as<uint8_t>(), nbytes, stride, leaf_hdr,
+                          d_in, n, mg.d_n, mg.n0inv);
+        });
     }
     VMN_TRY(rc);
     if (pinned_async) {
@@ -1599,31 +1606,23 @@ static int mul_arrays(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* x, con
                       uint32_t* out) {
     if (n == 0) return VMN_OK;
     note_work(ctx, m, (m.ec ? EC_ADD : 1.0) * (double)n);
-    int rc = VMN_ERR_ARG;
     if (m.ec) {
-#define X(S_, NW_, K_) \
-    if (m.ec->S == S_ && m.ec->kind == K_) rc = launch_light(ctx, "modmul", k_ec_add<S_, K_>, grid_for(n), out, x, y, ystride, n, ecdev(m.ec));
-        VMN_FOR_CURVES(X)
-#undef X
-        return rc;
+        return with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "modmul", k_ec_add<E::S, E::KIND>, grid_for(n), out, x, y, ystride, n, ecdev(m.ec));
+        });
     }
-#define X(S_, NW_, LPE_) \
-    if (m.S == S_) rc = launch(ctx, "modmul", k_mul<Cfg<S_, LPE_>>, egrid(m, n), lds_bytes(m), out, x, y, ystride, n, m.d_n, m.n0inv);
-    VMN_DISPATCH(n, X)
-#undef X
-    return rc;
+    return with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+        return launch(ctx, "modmul", k_mul<C>, egrid(mg, n), lds_bytes(mg), out, x, y, ystride, n, mg.d_n, mg.n0inv);
+    });
 }
 
 // M28 residues -> packed words (n * NW words)
 static int to_words(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* in, size_t n, uint32_t* out_words) {
     if (n == 0) return VMN_OK;
     note_work(ctx, m, (double)n);
-    int rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_) \
-    if (m.S == S_) rc = launch(ctx, "to_words", k_to_words<Cfg<S_, LPE_>, NW_>, egrid(m, n), lds_bytes(m), out_words, in, n, m.d_n, m.n0inv);
-    VMN_DISPATCH(n, X)
-#undef X
-    return rc;
+    return with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+        return launch(ctx, "to_words", k_to_words<C, W::NW>, egrid(mg, n), lds_bytes(mg), out_words, in, n, mg.d_n, mg.n0inv);
+    });
 }
 
 // window size minimising (table build) + (window multiplications)
@@ -1696,14 +1695,10 @@ static int modpow_words(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, 
         size_t tab_bytes = (size_t)grid * BLOCK * ((size_t)1 << wb) * elem_words(m) * sizeof(uint32_t);
         VMN_TRY(ensure_scratch(ctx, tab_bytes));
         note_work(ctx, m, (double)n * (EC_DBL * ebits + EC_ADD * ((ebits + wb - 1) / wb + (1 << wb))));
-        int rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                              \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                          \
-        rc = launch_light(ctx, "modpow", k_ec_mulvar<S_, K_>, grid, out, x, e_words, ewords, estride, ebits, wb, n,  \
-                          ecdev(m.ec), reinterpret_cast<uint32_t*>(ctx->scratch));
-        VMN_FOR_CURVES(X)
-#undef X
-        return rc;
+        return with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "modpow", k_ec_mulvar<E::S, E::KIND>, grid, out, x, e_words, ewords, estride, ebits, wb, n, ecdev(m.ec),
+                                reinterpret_cast<uint32_t*>(ctx->scratch));
+        });
     }
     int wbits = pick_window(ebits);
     const vmn_modulus& m = geom(ctx, m0, n);
@@ -1712,23 +1707,13 @@ static int modpow_words(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, 
     VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)1 << wbits)));
     note_work(ctx, m, (double)n * (nwin - 1 + (1 << wbits) - 2), (double)n * (nwin - 1) * wbits);
     VMN_TRY(pl.split(ctx, m, nwin - 1, (size_t)1 << wbits));
-    int rc = VMN_ERR_ARG;
-    if (pl.phases > 1) {
-#define X(S_, NW_, LPE_)                                                                                                 \
-    if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow_phased<Cfg<S_, LPE_>>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, estride, ebits, \
-                    wbits, n, m.d_n, m.n0inv, m.d_one, pl.table(), pl.phases, pl.queue(), pl.done());
-        VMN_FOR_SIZES(X)
-#undef X
-        return rc;
-    }
-#define X(S_, NW_, LPE_)                                                                                                 \
-    if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow<Cfg<S_, LPE_>>, pl.grid, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, \
-                    n, m.d_n, m.n0inv, m.d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
-    VMN_FOR_SIZES(X)
-#undef X
-    return rc;
+    return with_cfg(m, [&]<class C, class W>(C, W) {
+        if (pl.phases > 1)
+            return launch(ctx, "modpow", k_modpow_phased<C>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, n,
+                          m.d_n, m.n0inv, m.d_one, pl.table(), pl.phases, pl.queue(), pl.done());
+        return launch(ctx, "modpow", k_modpow<C>, pl.grid, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, n, m.d_n, m.n0inv,
+                      m.d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
+    });
 }
 
 // out[i] = x[i]^e for ONE exponent: left-to-right sliding window (csrc/modp_shared_exp.h).  Modular groups, exponents of
@@ -1782,24 +1767,14 @@ static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x,
     VMN_TRY(h2d(ctx, dsteps.p, steps.data(), steps.size() * sizeof(SlideStep)));
     note_work(ctx, m, (double)n * (double)(mults + tsize - 1), (double)n * (double)(squarings + 1));
     VMN_TRY(pl.split(ctx, m, (int)steps.size() - 1, (size_t)tsize));
-    int rc = VMN_ERR_ARG;
-    if (pl.phases > 1) {
-#define X(S_, NW_, LPE_)                                                                                                 \
-    if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow_shared_phased<Cfg<S_, LPE_>>, pl.max_blocks, lds_bytes(m), out, x,               \
-                    (const SlideStep*)dsteps.as<SlideStep>(), (int)steps.size(), tsize, n, m.d_n, m.n0inv, pl.table(), pl.phases,  \
-                    pl.queue(), pl.done());
-        VMN_FOR_SIZES(X)
-#undef X
-        return rc;
-    }
-#define X(S_, NW_, LPE_)                                                                                                 \
-    if (m.S == S_)                                                                                                 \
-        rc = launch(ctx, "modpow", k_modpow_shared<Cfg<S_, LPE_>>, pl.grid, lds_bytes(m), out, x, (const SlideStep*)dsteps.as<SlideStep>(), \
-                    (int)steps.size(), tsize, n, m.d_n, m.n0inv, reinterpret_cast<uint32_t*>(ctx->scratch));
-    VMN_FOR_SIZES(X)
-#undef X
-    return rc;
+    const SlideStep* d_steps = dsteps.as<SlideStep>();
+    return with_cfg(m, [&]<class C, class W>(C, W) {
+        if (pl.phases > 1)
+            return launch(ctx, "modpow", k_modpow_shared_phased<C>, pl.max_blocks, lds_bytes(m), out, x, d_steps, (int)steps.size(), tsize, n,
+                          m.d_n, m.n0inv, pl.table(), pl.phases, pl.queue(), pl.done());
+        return launch(ctx, "modpow", k_modpow_shared<C>, pl.grid, lds_bytes(m), out, x, d_steps, (int)steps.size(), tsize, n, m.d_n, m.n0inv,
+                      reinterpret_cast<uint32_t*>(ctx->scratch));
+    });
 }
 
 // big-endian integers (ebytes each) -> packed little-endian words on the host
@@ -2068,25 +2043,14 @@ static int modpow2(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, const
     VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)2 << wbits)));
     VMN_TRY(pl.split(ctx, m, std::max(nw1, nw2), (size_t)2 << wbits));
     note_work(ctx, m, (double)n * (nw1 + nw2 + 2 * ((1 << wbits) - 2)), (double)n * (std::max(nw1, nw2) - 1) * wbits);
-    int rc = VMN_ERR_ARG;
-    if (pl.phases > 1) {
-#define X(S_, NW_, LPE_)                                                                                                       \
-    if (m.S == S_)                                                                                                             \
-        rc = launch(ctx, "modpow", k_modpow2_phased<Cfg<S_, LPE_>>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, (size_t)0,  \
-                    ebits, y, f_words, fwords, (size_t)fwords, fbits, wbits, n, m.d_n, m.n0inv, m.d_one, pl.table(), pl.phases,    \
-                    pl.queue(), pl.done());
-        VMN_FOR_SIZES(X)
-#undef X
-        return rc;
-    }
-#define X(S_, NW_, LPE_)                                                                                                       \
-    if (m.S == S_)                                                                                                             \
-        rc = launch(ctx, "modpow", k_modpow2<Cfg<S_, LPE_>>, pl.grid, lds_bytes(m), out, x, e_words, ewords, (size_t)0, ebits, y,    \
-                    f_words, fwords, (size_t)fwords, fbits, wbits, n, m.d_n, m.n0inv, m.d_one,                                \
-                    reinterpret_cast<uint32_t*>(ctx->scratch));
-    VMN_FOR_SIZES(X)
-#undef X
-    return rc;
+    return with_cfg(m, [&]<class C, class W>(C, W) {
+        if (pl.phases > 1)
+            return launch(ctx, "modpow", k_modpow2_phased<C>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, (size_t)0, ebits, y,
+                          f_words, fwords, (size_t)fwords, fbits, wbits, n, m.d_n, m.n0inv, m.d_one, pl.table(), pl.phases, pl.queue(),
+                          pl.done());
+        return launch(ctx, "modpow", k_modpow2<C>, pl.grid, lds_bytes(m), out, x, e_words, ewords, (size_t)0, ebits, y, f_words, fwords,
+                      (size_t)fwords, fbits, wbits, n, m.d_n, m.n0inv, m.d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
+    });
 }
 
 // out[i] = x[i]^e * y[i]^f[i]: one simultaneous power (k_modpow2), the squarings shared between the two exponents.
@@ -2131,14 +2095,12 @@ extern "C" int vmn_garray_exp2(const vmn_garray* x, const uint8_t* e_be, size_t 
         if (rc == VMN_OK) {
             const int nw1 = (ebits + wbits - 1) / wbits, nw2 = (fbits + wbits - 1) / wbits;
             note_work(ctx, m, (double)n * (EC_DBL * std::max(ebits, fbits) + EC_ADD * (nw1 + nw2 + 2 * ((1 << wbits) - 2))));
-            rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                                          \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                                      \
-        rc = launch_light(ctx, "modpow", k_ec_mulvar2<S_, K_>, grid, r->d, (const uint32_t*)x->d, (const uint32_t*)ew.as<uint32_t>(), \
-                          ewords, ebits, (const uint32_t*)y->d, (const uint32_t*)fw.as<uint32_t>(), g->Q.NW, (size_t)g->Q.NW,     \
-                          fbits, wbits, n, ecdev(m.ec), reinterpret_cast<uint32_t*>(ctx->scratch));
-            VMN_FOR_CURVES(X)
-#undef X
+            rc = with_curve(m, [&]<class E>(E) {
+                return launch_light(ctx, "modpow", k_ec_mulvar2<E::S, E::KIND>, grid, r->d, (const uint32_t*)x->d,
+                                    (const uint32_t*)ew.as<uint32_t>(), ewords, ebits, (const uint32_t*)y->d,
+                                    (const uint32_t*)fw.as<uint32_t>(), g->Q.NW, (size_t)g->Q.NW, fbits, wbits, n, ecdev(m.ec),
+                                    reinterpret_cast<uint32_t*>(ctx->scratch));
+            });
         }
     } else if (rc == VMN_OK) {
         rc = modpow2(ctx, g->P, x->d, ew.as<uint32_t>(), ewords, ebits, y->d, fw.as<uint32_t>(), g->Q.NW, fbits, n, r->d);
@@ -2216,13 +2178,10 @@ extern "C" int vmn_garray_exp_pair(const vmn_garray* x, const uint8_t* e_be, siz
                                     reinterpret_cast<uint32_t*>(ctx->scratch));
                     if (rc == VMN_OK) note_path(ctx, "pair_mixed");
                 } else {
-                rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                                     \
-    if (m.S == S_)                                                                                                           \
-        rc = launch(ctx, "modpow", k_modpow_jobs<Cfg<S_, LPE_>>, (unsigned)tiles, lds_bytes(m), j0, j1, egrid(m, j0.n), wbits, m.d_n, \
-                    m.n0inv, m.d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
-                VMN_FOR_SIZES(X)
-#undef X
+                    rc = with_cfg(m, [&]<class C, class W>(C, W) {
+                        return launch(ctx, "modpow", k_modpow_jobs<C>, (unsigned)tiles, lds_bytes(m), j0, j1, egrid(m, j0.n), wbits, m.d_n,
+                                      m.n0inv, m.d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
+                    });
                 }
             }
             if (rc != VMN_OK) {
@@ -2256,12 +2215,9 @@ static int compare_arrays(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* x,
     if (n == 0) return VMN_OK;
     VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
     if (m.ec) {                        // Jacobian rows: equality of group elements, not of bytes
-        int rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_) \
-    if (m.ec->S == S_ && m.ec->kind == K_) rc = launch_light(ctx, "compare", k_ec_equal<S_, K_>, grid_for(n), x, y, n, ecdev(m.ec), ctx->flags);
-        VMN_FOR_CURVES(X)
-#undef X
-        VMN_TRY(rc);
+        VMN_TRY(with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "compare", k_ec_equal<E::S, E::KIND>, grid_for(n), x, y, n, ecdev(m.ec), ctx->flags);
+        }));
         uint32_t fl = 0;
         VMN_TRY(read_flag(ctx, &fl));
         *equal = fl ? 0 : 1;
@@ -2464,22 +2420,19 @@ static int reduce_segments(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* x
     while (true) {
         uint32_t* dst = (L == 1) ? d_out : ping;
         if (mul || m.ec) note_work(ctx, m, (m.ec ? EC_ADD : 1.0) * (double)nseg * (double)(cur - L));
-        int rc = VMN_ERR_ARG;
+        int rc;
         if (m.ec) {
-#define X(S_, NW_, K_) \
-    if (m.ec->S == S_ && m.ec->kind == K_) rc = launch_light(ctx, "reduce", k_ec_reduce<S_, K_>, grid_for(nseg * L), dst, src, cur, L, nseg, ecdev(m.ec));
-            VMN_FOR_CURVES(X)
-#undef X
+            rc = with_curve(m, [&]<class E>(E) {
+                return launch_light(ctx, "reduce", k_ec_reduce<E::S, E::KIND>, grid_for(nseg * L), dst, src, cur, L, nseg, ecdev(m.ec));
+            });
         } else {
-#define X(S_, NW_, LPE_)                                                                                                      \
-    if (m.S == S_) {                                                                                                    \
-        rc = mul ? launch(ctx, "reduce", k_reduce_strided<Cfg<S_, LPE_>, true>, egrid(m, nseg * L), lds_bytes(m), dst, src, cur, L, \
-                          nseg, m.d_n, m.n0inv)                                                                         \
-                 : launch(ctx, "reduce", k_reduce_strided<Cfg<S_, LPE_>, false>, egrid(m, nseg * L), lds_bytes(m), dst, src, cur, \
-                          L, nseg, m.d_n, m.n0inv);                                                                     \
-    }
-        VMN_DISPATCH((nseg * L) / 8, X)        /* the tail levels of a reduction are latency-bound: wide up to 8 x the threshold */
-#undef X
+            // the tail levels of a reduction are latency-bound: wide up to 8 x the threshold
+            rc = with_geom(ctx, m, (nseg * L) / 8, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+                auto go = [&](auto kernel) {
+                    return launch(ctx, "reduce", kernel, egrid(mg, nseg * L), lds_bytes(mg), dst, src, cur, L, nseg, mg.d_n, mg.n0inv);
+                };
+                return mul ? go(k_reduce_strided<C, true>) : go(k_reduce_strided<C, false>);
+            });
         }
         VMN_TRY(rc);
         if (L == 1) break;
@@ -2555,12 +2508,9 @@ static int ring_elementwise(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* 
                             int op, size_t n, uint32_t* out) {
     if (n == 0) return VMN_OK;
     if (op >= 2) note_work(ctx, m, (double)n);
-    int rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_) \
-    if (m.S == S_) rc = launch(ctx, "ring", k_ring_elementwise<Cfg<S_, LPE_>>, egrid(m, n), lds_bytes(m), out, x, y, v, op, n, m.d_n, m.n0inv);
-    VMN_DISPATCH(n, X)
-#undef X
-    return rc;
+    return with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+        return launch(ctx, "ring", k_ring_elementwise<C>, egrid(mg, n), lds_bytes(mg), out, x, y, v, op, n, mg.d_n, mg.n0inv);
+    });
 }
 
 extern "C" int vmn_rarray_mul(const vmn_rarray* x, const vmn_rarray* y, vmn_rarray** out) {
@@ -2660,35 +2610,24 @@ static int scan_affine(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* e, c
             return VMN_ERR_UNSUPPORTED;
         }
         size_t nchunks = (n + Cc - 1) / Cc;
-        int rc = VMN_ERR_ARG;
-        if (seglen <= Cc) {
-#define X(S_, NW_, K_)                                                                                             \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                         \
-        rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_apply<S_, K_>, grid_for(nchunks), out, e, (const uint32_t*)nullptr, n, \
-                          Cc, seglen, rev, ecdev(m.ec));
-            VMN_FOR_CURVES(X)
-#undef X
-            return rc;
-        }
-        DevTmp tot(ctx);
-        VMN_TRY(tot.alloc(2 * nchunks * Wd * sizeof(uint32_t)));
-        uint32_t* Etot = tot.as<uint32_t>();
-        uint32_t* inc = Etot + nchunks * Wd;
-#define X(S_, NW_, K_) \
-    if (m.ec->S == S_ && m.ec->kind == K_) rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_totals<S_, K_>, grid_for(nchunks), Etot, e, n, Cc, seglen, rev, ecdev(m.ec));
-        VMN_FOR_CURVES(X)
-#undef X
-        VMN_TRY(rc);
-        size_t seg_chunks = seglen == n ? nchunks : seglen / Cc;
-        VMN_TRY(scan_affine(ctx, m, Etot, nullptr, nchunks, seg_chunks, 0, inc));
-        rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                                   \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                               \
-        rc = note_work(ctx, m, EC_ADD * (double)n) ? 0 : launch_light(ctx, "scan", k_ec_scan_apply<S_, K_>, grid_for(nchunks), out, e, (const uint32_t*)inc, n, Cc, seglen, \
-                          rev, ecdev(m.ec));
-        VMN_FOR_CURVES(X)
-#undef X
-        return rc;
+        return with_curve(m, [&]<class E>(E) -> int {
+            if (seglen <= Cc) {
+                note_work(ctx, m, EC_ADD * (double)n);
+                return launch_light(ctx, "scan", k_ec_scan_apply<E::S, E::KIND>, grid_for(nchunks), out, e, (const uint32_t*)nullptr, n, Cc,
+                                    seglen, rev, ecdev(m.ec));
+            }
+            DevTmp tot(ctx);
+            VMN_TRY(tot.alloc(2 * nchunks * Wd * sizeof(uint32_t)));
+            uint32_t* Etot = tot.as<uint32_t>();
+            uint32_t* inc = Etot + nchunks * Wd;
+            note_work(ctx, m, EC_ADD * (double)n);
+            VMN_TRY(launch_light(ctx, "scan", k_ec_scan_totals<E::S, E::KIND>, grid_for(nchunks), Etot, e, n, Cc, seglen, rev, ecdev(m.ec)));
+            size_t seg_chunks = seglen == n ? nchunks : seglen / Cc;
+            VMN_TRY(scan_affine(ctx, m, Etot, nullptr, nchunks, seg_chunks, 0, inc));
+            note_work(ctx, m, EC_ADD * (double)n);
+            return launch_light(ctx, "scan", k_ec_scan_apply<E::S, E::KIND>, grid_for(nchunks), out, e, (const uint32_t*)inc, n, Cc, seglen,
+                                rev, ecdev(m.ec));
+        });
     }
     // chunk length: divides seglen when there are several segments
     size_t C = scan_chunk(n, (size_t)ctx->num_cus * blocks_per_cu(m) * (BLOCK / m.LPE));   // one tile per resident workgroup
@@ -2703,15 +2642,12 @@ static int scan_affine(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* e, c
     if (seglen <= C) {
         // every segment fits one chunk: a single apply pass with fresh starts
         size_t Cs = seglen;
-        int rc = VMN_ERR_ARG;
         size_t nchunks = (n + Cs - 1) / Cs;
-#define X(S_, NW_, LPE_)                                                                                                        \
-    if (m.S == S_)                                                                                                        \
-        rc = note_work(ctx, m, (double)n) ? 0 : launch(ctx, "scan", k_scan_apply<Cfg<S_, LPE_>>, egrid(m, nchunks), lds_bytes(m), out, e, b, (const uint32_t*)nullptr, \
-                    n, Cs, seglen, rev, m.d_n, m.n0inv, m.d_one);
-        VMN_DISPATCH(nchunks, X)
-#undef X
-        return rc;
+        return with_geom(ctx, m, nchunks, [&]<class C_, class W>(C_, W, const vmn_modulus& mg) {
+            note_work(ctx, mg, (double)n);
+            return launch(ctx, "scan", k_scan_apply<C_>, egrid(mg, nchunks), lds_bytes(mg), out, e, b, (const uint32_t*)nullptr, n, Cs, seglen,
+                          rev, mg.d_n, mg.n0inv, mg.d_one);
+        });
     }
     size_t nchunks = (n + C - 1) / C;
     DevTmp tot(ctx);
@@ -2719,29 +2655,23 @@ static int scan_affine(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* e, c
     uint32_t* Etot = tot.as<uint32_t>();
     uint32_t* Xtot = Etot + nchunks * Wd;
     uint32_t* inc = Xtot + nchunks * Wd;
-    int rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                                      \
-    if (m.S == S_) {                                                                                                    \
-        rc = note_work(ctx, m, (double)n) ? 0 : launch(ctx, "scan", k_scan_totals<Cfg<S_, LPE_>, false>, egrid(m, nchunks), lds_bytes(m), Etot, e, b, n, C, seglen,  \
-                    rev, m.d_n, m.n0inv, m.d_one);                                                                      \
-        if (rc == VMN_OK && b)                                                                                          \
-            rc = note_work(ctx, m, (double)n) ? 0 : launch(ctx, "scan", k_scan_totals<Cfg<S_, LPE_>, true>, egrid(m, nchunks), lds_bytes(m), Xtot, e, b, n, C,       \
-                        seglen, rev, m.d_n, m.n0inv, m.d_one);                                                          \
-    }
-    VMN_DISPATCH(nchunks, X)
-#undef X
-    VMN_TRY(rc);
+    // (a pass over nchunks lanes chooses once more, from m: where the wide geometries are off for n, eight lanes may still serve nchunks)
+    VMN_TRY(with_geom(ctx, m, nchunks, [&]<class C_, class W>(C_, W, const vmn_modulus& mg) -> int {
+        auto totals = [&](auto kernel, uint32_t* dst) {
+            note_work(ctx, mg, (double)n);
+            return launch(ctx, "scan", kernel, egrid(mg, nchunks), lds_bytes(mg), dst, e, b, n, C, seglen, rev, mg.d_n, mg.n0inv, mg.d_one);
+        };
+        VMN_TRY(totals(k_scan_totals<C_, false>, Etot));
+        return b ? totals(k_scan_totals<C_, true>, Xtot) : VMN_OK;
+    }));
     // inclusive scan over the chunk totals with the same recurrence (segments shrink by C)
     size_t seg_chunks = seglen == n ? nchunks : seglen / C;
     VMN_TRY(scan_affine(ctx, m0, Etot, b ? Xtot : nullptr, nchunks, seg_chunks, 0, inc));
-    rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                                  \
-    if (m.S == S_)                                                                                                  \
-        rc = note_work(ctx, m, (double)n) ? 0 : launch(ctx, "scan", k_scan_apply<Cfg<S_, LPE_>>, egrid(m, nchunks), lds_bytes(m), out, e, b, (const uint32_t*)inc, n, \
-                    C, seglen, rev, m.d_n, m.n0inv, m.d_one);
-    VMN_DISPATCH(nchunks, X)
-#undef X
-    return rc;
+    return with_geom(ctx, m, nchunks, [&]<class C_, class W>(C_, W, const vmn_modulus& mg) {
+        note_work(ctx, mg, (double)n);
+        return launch(ctx, "scan", k_scan_apply<C_>, egrid(mg, nchunks), lds_bytes(mg), out, e, b, (const uint32_t*)inc, n, C, seglen, rev,
+                      mg.d_n, mg.n0inv, mg.d_one);
+    });
 }
 
 extern "C" int vmn_rarray_max_bits(const vmn_rarray* x, int* bits) {
@@ -2812,11 +2742,9 @@ extern "C" int vmn_garray_inv(const vmn_garray* x, vmn_garray** out) {
         return VMN_OK;
     }
     if (m.ec) {
-        int rce = VMN_ERR_ARG;
-#define X(S_, NW_, K_) \
-    if (m.ec->S == S_ && m.ec->kind == K_) rce = launch_light(ctx, "modmul", k_ec_neg<S_, K_>, grid_for(n), r->d, (const uint32_t*)x->d, n, ecdev(m.ec));
-        VMN_FOR_CURVES(X)
-#undef X
+        const int rce = with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "modmul", k_ec_neg<E::S, E::KIND>, grid_for(n), r->d, (const uint32_t*)x->d, n, ecdev(m.ec));
+        });
         if (rce != VMN_OK) {
             vmn_garray_free(r);
             return rce;
@@ -3086,14 +3014,10 @@ static int import_dev(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const u
     if (all_in_range) *all_in_range = 1;
     if (n == 0) return VMN_OK;
     VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
-    int rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                               \
-    if (m.S == S_)                                                                                                     \
-        rc = launch(ctx, "import", k_import_be<Cfg<S_, LPE_>, NW_>, egrid(m, n), lds_bytes(m), d_out, d_rows, nbytes, nbytes, mode, n, \
-                    m.d_n, m.n0inv, m.d_rr, ctx->flags);
-    VMN_DISPATCH(n, X)
-#undef X
-    VMN_TRY(rc);
+    VMN_TRY(with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+        return launch(ctx, "import", k_import_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), d_out, d_rows, nbytes, nbytes, mode, n, mg.d_n,
+                      mg.n0inv, mg.d_rr, ctx->flags);
+    }));
     if (all_in_range) {
         uint32_t fl = 0;
         VMN_TRY(d2h(ctx, &fl, ctx->flags, sizeof(fl)));
@@ -3139,14 +3063,11 @@ static int prg_residues(vmn_ctx* ctx, const vmn_modulus& m, const PrgSeed& w, si
         VMN_TRY(prg_rows(ctx, w, n, vb, vbits, top_len + (pidx - 1) * mb, mb, mb, rows, sel));
         VMN_TRY(import_dev(ctx, m, mb, rows.as<uint8_t>(), 2, n, part.as<uint32_t>(), nullptr));
         uint32_t* dst = pidx + 1 == nparts ? d_out : cur;          // element-wise: a lane reads its operands before it writes
-        int rc = VMN_ERR_ARG;                                       // dst = cur * c + part   (ring op 2 with this modulus)
-#define X(S_, NW_, LPE_)                                                                                                      \
-    if (m.S == S_)                                                                                                            \
-        rc = launch(ctx, "ring", k_ring_elementwise<Cfg<S_, LPE_>>, egrid(m, n), lds_bytes(m), dst, (const uint32_t*)cur,          \
-                    (const uint32_t*)part.as<uint32_t>(), (const uint32_t*)cdev.as<uint32_t>(), 2, n, m.d_n, m.n0inv);
-        VMN_DISPATCH(n, X)
-#undef X
-        VMN_TRY(rc);
+        // dst = cur * c + part   (ring op 2 with this modulus)
+        VMN_TRY(with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+            return launch(ctx, "ring", k_ring_elementwise<C>, egrid(mg, n), lds_bytes(mg), dst, (const uint32_t*)cur,
+                          (const uint32_t*)part.as<uint32_t>(), (const uint32_t*)cdev.as<uint32_t>(), 2, n, mg.d_n, mg.n0inv);
+        }));
         cur = dst;
     }
     return VMN_OK;
@@ -3298,21 +3219,15 @@ static int ec_random_points(vmn_group* grp, const uint8_t* seed, size_t seedlen,
         uint32_t* idx = pos + (mcand + 1);
         uint32_t* bsum = idx + (mcand + 1);
         uint32_t* total = bsum + scan_blocks;
-        rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                                        \
-    if (cv->S == S_ && cv->kind == K_) {                                                                                      \
-        if (ps.hash == 256)                                                                                                   \
-            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 256, K_>, grid_for(mcand), cand.as<uint32_t>(), keep,   \
-                              (const uint32_t*)dseed.as<uint32_t>(), first, mcand, vb, top_mask, cb, (const uint32_t*)dc.as<uint32_t>(), ecdev(cv)); \
-        else if (ps.hash == 384)                                                                                              \
-            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 384, K_>, grid_for(mcand), cand.as<uint32_t>(), keep,   \
-                              (const uint32_t*)dseed.as<uint32_t>(), first, mcand, vb, top_mask, cb, (const uint32_t*)dc.as<uint32_t>(), ecdev(cv)); \
-        else                                                                                                                  \
-            rc = launch_light(ctx, "prg", k_ec_random_points<S_, NW_, 512, K_>, grid_for(mcand), cand.as<uint32_t>(), keep,   \
-                              (const uint32_t*)dseed.as<uint32_t>(), first, mcand, vb, top_mask, cb, (const uint32_t*)dc.as<uint32_t>(), ecdev(cv)); \
-    }
-        VMN_FOR_CURVES(X)
-#undef X
+        rc = with_curve(m, [&]<class E>(E) {                   // (m.ec is cv)
+            auto go = [&](auto kernel) {
+                return launch_light(ctx, "prg", kernel, grid_for(mcand), cand.as<uint32_t>(), keep, (const uint32_t*)dseed.as<uint32_t>(), first,
+                                    mcand, vb, top_mask, cb, (const uint32_t*)dc.as<uint32_t>(), ecdev(cv));
+            };
+            if (ps.hash == 256) return go(k_ec_random_points<E::S, E::NW, 256, E::KIND>);
+            if (ps.hash == 384) return go(k_ec_random_points<E::S, E::NW, 384, E::KIND>);
+            return go(k_ec_random_points<E::S, E::NW, 512, E::KIND>);
+        });
         if (rc != VMN_OK) break;
         // exclusive prefix sums of the keep flags, then the kept rows in candidate order
         rc = launch_light(ctx, "prg", k_u32_blocksum, (unsigned)scan_blocks, bsum, (const uint32_t*)keep, mcand);
@@ -3579,25 +3494,21 @@ static int fixed_table(vmn_group* g, const uint8_t* base_be, int ebits, size_t n
         ft.bytes = (size_t)nwin * ((size_t)1 << w) * Wd * sizeof(uint32_t);
         if (rc == VMN_OK) rc = fixed_alloc(g, ft.bytes, &ft.d_tab);
         if (rc == VMN_OK) {
-            rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                            \
-    if (m.ec->S == S_ && m.ec->kind == K_) {                                                                      \
-        hipLaunchKernelGGL((k_ec_chain<S_, K_>), dim3(1), dim3(64), 0, ctx->stream, sq.as<uint32_t>(),            \
-                           (const uint32_t*)d_base, (int)chain, ecdev(m.ec));                                     \
-        rc = hipGetLastError() == hipSuccess ? VMN_OK : VMN_ERR_DEVICE;                                           \
-    }
-            VMN_FOR_CURVES(X)
-#undef X
+            rc = with_curve(m, [&]<class E>(E) {               // (one lane, untimed)
+                hipLaunchKernelGGL((k_ec_chain<E::S, E::KIND>), dim3(1), dim3(64), 0, ctx->stream, sq.as<uint32_t>(), (const uint32_t*)d_base,
+                                   (int)chain, ecdev(m.ec));
+                return hipGetLastError() == hipSuccess ? VMN_OK : VMN_ERR_DEVICE;
+            });
         }
         if (rc == VMN_OK)
             rc = launch_light(ctx, "fixed_table", k_fixed_seed, grid_for((size_t)nwin * (w + 1)), ft.d_tab,
                               (const uint32_t*)sq.as<uint32_t>(), w, nwin, (const uint32_t*)m.d_one, (int)Wd);
         for (int l = 1; l < w && rc == VMN_OK; ++l) {
             size_t lanes = (((size_t)1 << l) - 1) * nwin;
-#define X(S_, NW_, K_) \
-    if (m.ec->S == S_ && m.ec->kind == K_) rc = note_work(ctx, m, EC_ADD * (double)lanes) ? 0 : launch_light(ctx, "fixed_table", k_ec_fixed_level<S_, K_>, grid_for(lanes), ft.d_tab, w, nwin, l, ecdev(m.ec));
-            VMN_FOR_CURVES(X)
-#undef X
+            rc = with_curve(m, [&]<class E>(E) {
+                note_work(ctx, m, EC_ADD * (double)lanes);
+                return launch_light(ctx, "fixed_table", k_ec_fixed_level<E::S, E::KIND>, grid_for(lanes), ft.d_tab, w, nwin, l, ecdev(m.ec));
+            });
         }
         free_one(ctx, m, d_base);
         if (rc == VMN_OK) {                              // Z := 1 in every entry: k_ec_fixed_exp adds them with the mixed addition
@@ -3642,15 +3553,14 @@ static int fixed_table(vmn_group* g, const uint8_t* base_be, int ebits, size_t n
     ft.nwin = nwin;
     ft.bytes = (size_t)nwin * ((size_t)1 << w) * Wd * sizeof(uint32_t);
     VMN_TRY(fixed_alloc(g, ft.bytes, &ft.d_tab));
-    int rc = VMN_ERR_ARG;
-    rc = launch_light(ctx, "fixed_table", k_fixed_seed, grid_for((size_t)nwin * (w + 1)), ft.d_tab,
-                      (const uint32_t*)sq.as<uint32_t>(), w, nwin, (const uint32_t*)m.d_one, (int)Wd);
+    int rc = launch_light(ctx, "fixed_table", k_fixed_seed, grid_for((size_t)nwin * (w + 1)), ft.d_tab, (const uint32_t*)sq.as<uint32_t>(), w,
+                          nwin, (const uint32_t*)m.d_one, (int)Wd);
     for (int l = 1; l < w && rc == VMN_OK; ++l) {
         size_t lanes = (((size_t)1 << l) - 1) * nwin;
-#define X(S_, NW_, LPE_) \
-    if (m.S == S_) rc = note_work(ctx, m, (double)lanes) ? 0 : launch(ctx, "fixed_table", k_fixed_level<Cfg<S_, LPE_>>, egrid(m, lanes), lds_bytes(m), ft.d_tab, w, nwin, l, m.d_n, m.n0inv);
-        VMN_DISPATCH(lanes, X)
-#undef X
+        rc = with_geom(ctx, m, lanes, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+            note_work(ctx, mg, (double)lanes);
+            return launch(ctx, "fixed_table", k_fixed_level<C>, egrid(mg, lanes), lds_bytes(mg), ft.d_tab, w, nwin, l, mg.d_n, mg.n0inv);
+        });
     }
     if (rc != VMN_OK) {
         (void)hipFree(ft.d_tab);
@@ -3725,13 +3635,11 @@ extern "C" int vmn_group_exp_fixed(vmn_group* grp, const uint8_t* base_be, const
     if (rc == VMN_OK) rc = to_words(ctx, grp->Q, e->d, n, ew.as<uint32_t>());
     if (rc == VMN_OK && grp->P.ec) {
         const vmn_modulus& m = grp->P;
-        rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                               \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                           \
-        rc = note_work(ctx, m, EC_MADD_RUN * (double)n * (ft->nwin - 1), 0, EC_MADD * (double)n * (ft->nwin - 1)) ? 0 : launch_light(ctx, "fixed", k_ec_fixed_exp<S_, K_>, grid_for(n), r->d, (const uint32_t*)ft->d_tab, ft->wbits, \
-                          ft->nwin, (const uint32_t*)ew.as<uint32_t>(), grp->Q.NW, n, ecdev(m.ec));
-        VMN_FOR_CURVES(X)
-#undef X
+        rc = with_curve(m, [&]<class E>(E) {
+            note_work(ctx, m, EC_MADD_RUN * (double)n * (ft->nwin - 1), 0, EC_MADD * (double)n * (ft->nwin - 1));
+            return launch_light(ctx, "fixed", k_ec_fixed_exp<E::S, E::KIND>, grid_for(n), r->d, (const uint32_t*)ft->d_tab, ft->wbits, ft->nwin,
+                                (const uint32_t*)ew.as<uint32_t>(), grp->Q.NW, n, ecdev(m.ec));
+        });
     } else if (rc == VMN_OK) {
         // Small arrays: an element's chain of nwin - 1 dependent products is cut into `parts` pieces on `parts` times as many
         // lanes, multiplied together by a tree of element-wise products (k_fixed_exp) -- as many pieces as it takes to give
@@ -3747,15 +3655,13 @@ extern "C" int vmn_group_exp_fixed(vmn_group* grp, const uint8_t* base_be, const
         // one workgroup per tile rather than a persistent grid: a workgroup slot frees up every ~2 ms, so kernels of
         // the other lane (a helper's exports) are scheduled between the tiles instead of behind the whole launch
         unsigned grid = egrid(m, items);
-#define X(S_, NW_, LPE_)                                                                                                 \
-    if (m.S == S_)                                                                                                 \
-        rc = note_work(ctx, m, (double)n * (ft->nwin - parts)) ? 0 : launch(ctx, "fixed", k_fixed_exp<Cfg<S_, LPE_>>, grid, lds_bytes(m), dst, (const uint32_t*)ft->d_tab, ft->wbits, \
-                    ft->nwin, (const uint32_t*)ew.as<uint32_t>(), grp->Q.NW, n, parts, m.d_n, m.n0inv);
         if (rc == VMN_OK) {                              // (a failed allocation of the pieces must not reach the launch: dst would be null)
-            rc = VMN_ERR_ARG;
-            VMN_FOR_SIZES(X)
+            rc = with_cfg(m, [&]<class C, class W>(C, W) {
+                note_work(ctx, m, (double)n * (ft->nwin - parts));
+                return launch(ctx, "fixed", k_fixed_exp<C>, grid, lds_bytes(m), dst, (const uint32_t*)ft->d_tab, ft->wbits, ft->nwin,
+                              (const uint32_t*)ew.as<uint32_t>(), grp->Q.NW, n, parts, m.d_n, m.n0inv);
+            });
         }
-#undef X
         for (int half = parts / 2; half >= 1 && rc == VMN_OK; half /= 2) {          // pieces [0, half) *= pieces [half, 2 half)
             uint32_t* lo = pieces.as<uint32_t>();
             rc = mul_arrays(ctx, grp->P, lo, lo + (size_t)half * n * Wd, Wd, (size_t)half * n, half == 1 ? r->d : lo);
@@ -3799,44 +3705,43 @@ static int ec_normalize(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* cons
     uint32_t* B = buf.as<uint32_t>();
     double products = 7.0 * (double)(k * n) + EC_INV * (double)sizes[L - 1];
     for (size_t l = 1; l + 1 < L; ++l) products += 3.0 * (double)sizes[l];
-    int rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                                               \
-    if (m.ec->S == S_ && m.ec->kind == K_) {                                                                                         \
-        note_work(ctx, m, products);                                                                                                 \
-        rc = VMN_OK;                                                                                                                 \
-        const unsigned bpa = (unsigned)((n1 + BLOCK - 1) / BLOCK);                       /* blocks per array of the two row-level launches */ \
-        for (size_t a0 = 0; a0 < k && rc == VMN_OK; a0 += LEVEL_ARRAYS) {                                                            \
-            const size_t ga = std::min<size_t>(LEVEL_ARRAYS, k - a0);                                                                \
-            LevelInputs li{};                                                                                                        \
-            for (size_t a = 0; a < ga; ++a) li.p[a] = ins[a0 + a];                                                                   \
-            rc = launch_light(ctx, "normalize", k_finv_up<S_, true, K_>, (unsigned)(bpa * ga), B + off_pref[0] + a0 * n * FWd, \
-                              B + off_val[1] + a0 * n1 * FWd, li, bpa, n, K, ecdev(m.ec));                                           \
-        }                                                                                                                            \
-        for (size_t l = 1; l + 1 < L && rc == VMN_OK; ++l) {                                                                         \
-            LevelInputs li{};                                                                                                        \
-            li.p[0] = B + off_val[l];                                                                                                \
-            const unsigned bl = (unsigned)((sizes[l + 1] + BLOCK - 1) / BLOCK);                                                      \
-            rc = launch_light(ctx, "normalize", k_finv_up<S_, false, K_>, bl, B + off_pref[l], B + off_val[l + 1], li, bl,     \
-                              sizes[l], K, ecdev(m.ec));                                                                             \
-        }                                                                                                                            \
-        if (rc == VMN_OK)                                                                                                            \
-            rc = launch_light(ctx, "normalize", k_finv_top<S_, K_>, grid_for(sizes[L - 1]), B + off_inv[L - 1],                      \
-                              (const uint32_t*)(B + off_val[L - 1]), sizes[L - 1], ecdev(m.ec));                                     \
-        for (size_t l = L - 2; l >= 1 && rc == VMN_OK; --l)                                                                          \
-            rc = launch_light(ctx, "normalize", k_finv_down<S_, K_>, grid_for(sizes[l + 1]), B + off_inv[l], (const uint32_t*)(B + off_inv[l + 1]), \
-                              (const uint32_t*)(B + off_pref[l]), (const uint32_t*)(B + off_val[l]), sizes[l], K, ecdev(m.ec));      \
-        for (size_t a0 = 0; a0 < k && rc == VMN_OK; a0 += LEVEL_ARRAYS) {                                                            \
-            const size_t ga = std::min<size_t>(LEVEL_ARRAYS, k - a0);                                                                \
-            LevelInputs li{};                                                                                                        \
-            for (size_t a = 0; a < ga; ++a) li.p[a] = ins[a0 + a];                                                                   \
-            rc = launch_light(ctx, "normalize", k_ec_normalize_down<S_, K_>, (unsigned)(bpa * ga), out + a0 * n * Wd, li, bpa, \
-                              (const uint32_t*)(B + off_inv[1] + a0 * n1 * FWd), (const uint32_t*)(B + off_pref[0] + a0 * n * FWd),  \
-                              n, K, ecdev(m.ec));                                                                                    \
-        }                                                                                                                            \
-    }
-    VMN_FOR_CURVES(X)
-#undef X
-    return rc;
+    return with_curve(m, [&]<class E>(E) -> int {
+        constexpr int S = E::S, KIND = E::KIND;
+        note_work(ctx, m, products);
+        const unsigned bpa = (unsigned)((n1 + BLOCK - 1) / BLOCK);       // blocks per array of the two row-level launches
+        // up: the prefix products of every chunk and the chunk's product, level by level (the rows' Z first, LEVEL_ARRAYS arrays a launch)
+        for (size_t a0 = 0; a0 < k; a0 += LEVEL_ARRAYS) {
+            const size_t ga = std::min<size_t>(LEVEL_ARRAYS, k - a0);
+            LevelInputs li{};
+            for (size_t a = 0; a < ga; ++a) li.p[a] = ins[a0 + a];
+            VMN_TRY(launch_light(ctx, "normalize", k_finv_up<S, true, KIND>, (unsigned)(bpa * ga), B + off_pref[0] + a0 * n * FWd,
+                                 B + off_val[1] + a0 * n1 * FWd, li, bpa, n, K, ecdev(m.ec)));
+        }
+        for (size_t l = 1; l + 1 < L; ++l) {
+            LevelInputs li{};
+            li.p[0] = B + off_val[l];
+            const unsigned bl = (unsigned)((sizes[l + 1] + BLOCK - 1) / BLOCK);
+            VMN_TRY(launch_light(ctx, "normalize", k_finv_up<S, false, KIND>, bl, B + off_pref[l], B + off_val[l + 1], li, bl, sizes[l], K,
+                                 ecdev(m.ec)));
+        }
+        // the top level's values are inverted one by one
+        VMN_TRY(launch_light(ctx, "normalize", k_finv_top<S, KIND>, grid_for(sizes[L - 1]), B + off_inv[L - 1],
+                             (const uint32_t*)(B + off_val[L - 1]), sizes[L - 1], ecdev(m.ec)));
+        // down: the inverses of a level from those of the level above, at last the rows themselves
+        for (size_t l = L - 2; l >= 1; --l)
+            VMN_TRY(launch_light(ctx, "normalize", k_finv_down<S, KIND>, grid_for(sizes[l + 1]), B + off_inv[l],
+                                 (const uint32_t*)(B + off_inv[l + 1]), (const uint32_t*)(B + off_pref[l]), (const uint32_t*)(B + off_val[l]),
+                                 sizes[l], K, ecdev(m.ec)));
+        for (size_t a0 = 0; a0 < k; a0 += LEVEL_ARRAYS) {
+            const size_t ga = std::min<size_t>(LEVEL_ARRAYS, k - a0);
+            LevelInputs li{};
+            for (size_t a = 0; a < ga; ++a) li.p[a] = ins[a0 + a];
+            VMN_TRY(launch_light(ctx, "normalize", k_ec_normalize_down<S, KIND>, (unsigned)(bpa * ga), out + a0 * n * Wd, li, bpa,
+                                 (const uint32_t*)(B + off_inv[1] + a0 * n1 * FWd), (const uint32_t*)(B + off_pref[0] + a0 * n * FWd), n, K,
+                                 ecdev(m.ec)));
+        }
+        return VMN_OK;
+    });
 }
 
 // ---- K3 multi-exponentiation -----------------------------------------------------------------------
@@ -4080,16 +3985,16 @@ static int expprod_words(vmn_group* g, const uint32_t* const* xs, size_t k, cons
     VMN_TRACE("expprod:sort");
     VMN_TRY(dev_zero(ctx, counts, nbuckets * sizeof(uint32_t)));
     const unsigned gx = std::max<unsigned>(1, std::min<unsigned>((unsigned)((n + BLOCK - 1) / BLOCK), (unsigned)(ctx->num_cus * 8 / std::max(nwin, 1) + 1)));
+    auto sort = [&](auto hist, auto scatter) -> int {
+        VMN_TRY(launch_light(ctx, "expprod_sort", hist, gx * (unsigned)nwin, counts, e_words, ewords, n, c, nwin, gx, ebits));
+        VMN_TRY(scan_u32(off0, cursor, counts, misc + 2 * LV));
+        return launch_light(ctx, "expprod_sort", scatter, gx * (unsigned)nwin, sorted.as<uint32_t>(), cursor, e_words, ewords, n, c, nwin, gx,
+                            ebits);
+    };
     if (sgn) {
-        VMN_TRY(launch_light(ctx, "expprod_sort", k_bucket_hist<true>, gx * (unsigned)nwin, counts, e_words, ewords, n, c, nwin, gx, ebits));
-        VMN_TRY(scan_u32(off0, cursor, counts, misc + 2 * LV));
-        VMN_TRY(launch_light(ctx, "expprod_sort", k_bucket_scatter<true>, gx * (unsigned)nwin, sorted.as<uint32_t>(), cursor,
-                             e_words, ewords, n, c, nwin, gx, ebits));           // (zero digits were never inserted)
+        VMN_TRY(sort(k_bucket_hist<true>, k_bucket_scatter<true>));           // (zero digits were never inserted)
     } else {
-        VMN_TRY(launch_light(ctx, "expprod_sort", k_bucket_hist<false>, gx * (unsigned)nwin, counts, e_words, ewords, n, c, nwin, gx, ebits));
-        VMN_TRY(scan_u32(off0, cursor, counts, misc + 2 * LV));
-        VMN_TRY(launch_light(ctx, "expprod_sort", k_bucket_scatter<false>, gx * (unsigned)nwin, sorted.as<uint32_t>(), cursor,
-                             e_words, ewords, n, c, nwin, gx, ebits));
+        VMN_TRY(sort(k_bucket_hist<false>, k_bucket_scatter<false>));
         VMN_TRY(launch_light(ctx, "expprod_sort", k_bucket_drop_zero, grid_for(nwin), counts, c, nwin));
     }
     }
@@ -4159,47 +4064,39 @@ static int expprod_words(vmn_group* g, const uint32_t* const* xs, size_t k, cons
         uint32_t* items_other = itemsB.as<uint32_t>();
         size_t out_cap = cap0, other_cap = cap1;
         bool first = true;
-        int rc = VMN_OK;
         for (size_t level = 0; level < shape.size(); ++level) {
             const size_t total_out = shape[level].first;
             const double level_in = level == 0 ? (double)nwin * (double)n : (double)shape[level - 1].first;
             const double level_products = std::max(0.0, level_in - (double)total_out) * (double)gl;
             const size_t out_stride = out_cap * Wd;
             if (total_out > 0 && m.ec) {
-                rc = VMN_ERR_ARG;
                 const unsigned bpa = grid_for(total_out);
-#define X(S_, NW_, K_)                                                                                                 \
-    if (m.ec->S == S_ && m.ec->kind == K_) {                                                                           \
-        rc = note_work(ctx, m, (first && ec_rows_normalised ? EC_MADD_RUN : EC_ADD) * level_products, 0,                        \
-                       (first && ec_rows_normalised ? EC_MADD : EC_ADD) * level_products) ? 0                                  \
-             : first && !ec_rows_normalised ? launch_light(ctx, "expprod", k_ec_bucket_first_jacobian<S_, K_>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa, \
-                                  (const uint32_t*)sorted.as<uint32_t>(), off_in, cnt_in, (const uint32_t*)off_of((int)level),    \
-                                  nbuckets, total_out, F, ecdev(m.ec))                                                 \
-             : first ? launch_light(ctx, "expprod", k_ec_bucket_level<S_, true, K_>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa, \
-                                  (const uint32_t*)sorted.as<uint32_t>(), off_in, cnt_in, (const uint32_t*)off_of((int)level),    \
-                                  nbuckets, total_out, F, ecdev(m.ec))                                                 \
-                   : launch_light(ctx, "expprod", k_ec_bucket_level<S_, false, K_>, bpa * (unsigned)gl, items_out, out_stride, ins, bpa,    \
-                                  (const uint32_t*)nullptr, off_in, cnt_in, (const uint32_t*)off_of((int)level),        \
-                                  nbuckets, total_out, F, ecdev(m.ec));                                                \
-    }
-                VMN_FOR_CURVES(X)
-#undef X
-                VMN_TRY(rc);
+                VMN_TRY(with_curve(m, [&]<class E>(E) {
+                    const bool mixed = first && ec_rows_normalised;
+                    note_work(ctx, m, (mixed ? EC_MADD_RUN : EC_ADD) * level_products, 0, (mixed ? EC_MADD : EC_ADD) * level_products);
+                    if (first && !ec_rows_normalised)
+                        return launch_light(ctx, "expprod", k_ec_bucket_first_jacobian<E::S, E::KIND>, bpa * (unsigned)gl, items_out, out_stride,
+                                            ins, bpa, (const uint32_t*)sorted.as<uint32_t>(), off_in, cnt_in,
+                                            (const uint32_t*)off_of((int)level), nbuckets, total_out, F, ecdev(m.ec));
+                    if (first)
+                        return launch_light(ctx, "expprod", k_ec_bucket_level<E::S, true, E::KIND>, bpa * (unsigned)gl, items_out, out_stride,
+                                            ins, bpa, (const uint32_t*)sorted.as<uint32_t>(), off_in, cnt_in,
+                                            (const uint32_t*)off_of((int)level), nbuckets, total_out, F, ecdev(m.ec));
+                    return launch_light(ctx, "expprod", k_ec_bucket_level<E::S, false, E::KIND>, bpa * (unsigned)gl, items_out, out_stride, ins,
+                                        bpa, (const uint32_t*)nullptr, off_in, cnt_in, (const uint32_t*)off_of((int)level), nbuckets,
+                                        total_out, F, ecdev(m.ec));
+                }));
             } else if (total_out > 0) {
-                rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                                      \
-    if (m.S == S_) {                                                                                                    \
-        const unsigned bpa = egrid(m, total_out);                                                                       \
-        rc = note_work(ctx, m, level_products) ? 0 : first ? launch(ctx, "expprod", k_bucket_level<Cfg<S_, LPE_>, true>, bpa * (unsigned)gl, lds_bytes(m), items_out, out_stride,    \
-                            ins, bpa, (const uint32_t*)sorted.as<uint32_t>(), off_in, cnt_in, (const uint32_t*)off_of((int)level), \
-                            nbuckets, total_out, F, m.d_n, m.n0inv)                                                     \
-                   : launch(ctx, "expprod", k_bucket_level<Cfg<S_, LPE_>, false>, bpa * (unsigned)gl, lds_bytes(m), items_out, out_stride,   \
-                            ins, bpa, (const uint32_t*)nullptr, off_in, cnt_in, (const uint32_t*)off_of((int)level), nbuckets,     \
-                            total_out, F, m.d_n, m.n0inv);                                                              \
-    }
-                VMN_DISPATCH(total_out * gl, X)
-#undef X
-                VMN_TRY(rc);
+                VMN_TRY(with_geom(ctx, m, total_out * gl, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+                    const unsigned bpa = egrid(mg, total_out);
+                    // the first level reads the arrays through the sorted indices, the others the items of the level below as they lie
+                    auto go = [&](auto kernel, const uint32_t* order) {
+                        note_work(ctx, mg, level_products);
+                        return launch(ctx, "expprod", kernel, bpa * (unsigned)gl, lds_bytes(mg), items_out, out_stride, ins, bpa, order, off_in,
+                                      cnt_in, (const uint32_t*)off_of((int)level), nbuckets, total_out, F, mg.d_n, mg.n0inv);
+                    };
+                    return first ? go(k_bucket_level<C, true>, sorted.as<uint32_t>()) : go(k_bucket_level<C, false>, nullptr);
+                }));
             }
             // the outputs become the next level's inputs
             first = false;
@@ -4240,14 +4137,10 @@ static int expprod_words(vmn_group* g, const uint32_t* const* xs, size_t k, cons
         VMN_TRACE("expprod:horner_device");
         DevTmp res(ctx);
         VMN_TRY(res.alloc(k * Wd * sizeof(uint32_t)));
-        int rc = VMN_ERR_ARG;
-#define X(S_, NW_, K_)                                                                                                    \
-    if (m.ec->S == S_ && m.ec->kind == K_)                                                                                \
-        rc = launch_light(ctx, "expprod_agg", k_ec_horner<S_, K_>, grid_for(k), res.as<uint32_t>(), (const uint32_t*)wres.as<uint32_t>(), \
-                          nwin, c, (int)k, ecdev(m.ec));
-        VMN_FOR_CURVES(X)
-#undef X
-        VMN_TRY(rc);
+        VMN_TRY(with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "expprod_agg", k_ec_horner<E::S, E::KIND>, grid_for(k), res.as<uint32_t>(),
+                                (const uint32_t*)wres.as<uint32_t>(), nwin, c, (int)k, ecdev(m.ec));
+        }));
         if (pend) {
             pend->nwin = 0;                            // (finish: the staged bytes ARE the results)
             pend->staged_bytes = k * ebytes_out;
@@ -4410,16 +4303,16 @@ extern "C" int vmn_garray_is_member(const vmn_garray* x, int* all_members) {
         pm1[0] -= 1;
         if (hostbig::cmp(twoq, pm1) == 0) {
             VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
-            int rc = VMN_ERR_ARG;
-#define X(S_, NW_, LPE_)                                                                                                   \
-    if constexpr (LPE_ == 1) {                                                                                             \
-        if (m.S == S_) rc = launch_light(ctx, "member", k_jacobi_member<Cfg<S_, LPE_>>, grid_for(x->n), (const uint32_t*)x->d, x->n, (const uint32_t*)m.d_n, ctx->flags); \
-    } else if constexpr (!Cfg<S_, LPE_>::WIDE) {                                                                           \
-        if (m.S == S_) rc = launch_light(ctx, "member", k_jacobi_member_lanes<Cfg<S_, LPE_>>, egrid(m, x->n), (const uint32_t*)x->d, x->n, (const uint32_t*)m.d_n, ctx->flags); \
-    }
-            VMN_FOR_SIZES(X)
-#undef X
-            VMN_TRY(rc);
+            VMN_TRY(with_cfg(m, [&]<class C, class W>(C, W) -> int {
+                if constexpr (C::LPE == 1)
+                    return launch_light(ctx, "member", k_jacobi_member<C>, grid_for(x->n), (const uint32_t*)x->d, x->n, (const uint32_t*)m.d_n,
+                                        ctx->flags);
+                else if constexpr (!C::WIDE)
+                    return launch_light(ctx, "member", k_jacobi_member_lanes<C>, egrid(m, x->n), (const uint32_t*)x->d, x->n,
+                                        (const uint32_t*)m.d_n, ctx->flags);
+                else
+                    return VMN_ERR_ARG;
+            }));
             uint32_t fl = 0;
             VMN_TRY(d2h(ctx, &fl, ctx->flags, sizeof(fl)));
             *all_members = fl ? 0 : 1;
