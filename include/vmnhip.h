@@ -185,6 +185,13 @@ int vmn_garray_exp_ints(const vmn_garray* x, const uint8_t* exps_be, size_t ebyt
  * P/mixnet/ShufflerElGamalSession.java:506; P/mixnet/PermutationCommitment.java:357;
  * P/elgamal/DistrElGamalSession.java:384-385. */
 int vmn_garray_exp_scalar(const vmn_garray* x, const uint8_t* e_be, size_t ebytes, vmn_garray** out);
+/* The same for k arrays of one group and one size under ONE exponent: outs[c][i] = xs[c][i]^e, bit for bit what k calls of
+ * vmn_garray_exp_scalar give (the omega component arrays of a width-omega list raised to a party's secret:
+ * P/elgamal/DistrElGamalSession.java:365-389 over a product group).  Over a modular group, for exponents above 32 bits, up to
+ * eight arrays share one launch; VMN_EXP_MULTI_FUSED=0 (read per call) runs them one after the other.  The same array may
+ * appear twice.  k = 0, arrays of two groups or of different sizes: VMN_ERR_ARG.  On failure no output stays allocated
+ * (outs[c] = NULL). */
+int vmn_garray_exp_scalar_multi(const vmn_garray* const* xs, size_t k, const uint8_t* e_be, size_t ebytes, vmn_garray** outs);
 /* K2  g.exp(E): out[i] = base^E[i] for one fixed base.  ref: P/mixnet/ShufflerElGamalSession.java:407,
  * 658; P/hvzk/PoSBasicTW.java:447, 606, 608, 644, 646, 1030; P/mixnet/PermutationCommitment.java:200. */
 int vmn_group_exp_fixed(vmn_group* grp, const uint8_t* base_be, const vmn_rarray* e, vmn_garray** out);

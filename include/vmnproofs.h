@@ -282,6 +282,16 @@ int vmn_decryption_factors(vmn_group* grp, const vmn_garray* u, const uint8_t* s
 int vmn_combine_decryption_factors(vmn_group* grp, const vmn_garray* const* f, const uint8_t* correct, int k, int threshold,
                                    vmn_garray** out);
 /* plaintexts = v.mul(combinedFactors) is vmn_garray_mul. */
+/* The same over the plaintext group G^width (a list of width-omega ciphertexts; DistrElGamalSessionBasic keeps u, A, B' and
+ * B_l in G^omega while g, y, the secret, the randomizer, the reply and the challenge stay in G / Z_q).  A width-omega array is
+ * `width` vmn_garray of equal size, component 0 first; the width-1 entry points above and below are the case width = 1 of
+ * these.  u / f_out / out: `width` arrays.  f: (k + 1) * width arrays, entry l * width + c = component c of party l (party 0
+ * unused, NULL = absent).  One party's components are raised in ONE vmn_garray_exp_scalar_multi; the threshold integers are
+ * computed once. */
+int vmn_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* const* u, const uint8_t* secret_be, int k,
+                                vmn_garray** f_out);
+int vmn_combine_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* const* f, const uint8_t* correct, int k,
+                                        int threshold, vmn_garray** out);
 
 typedef struct vmn_decproof vmn_decproof;          /* DistrElGamalSessionBasic of party j (prover and verifier of all l) */
 int vmn_decproof_create(vmn_group* grp, int j, int k, int threshold, int ebitlen, const vmn_random_source* rs, vmn_decproof** out);
@@ -300,6 +310,16 @@ int vmn_decproof_verify(vmn_decproof* p, int l, const uint8_t* v_be, size_t vbyt
 int vmn_decproof_combine(vmn_decproof* p, const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* combinedf);
 int vmn_decproof_batch_combined(vmn_decproof* p);                                            /* :683-685 */
 int vmn_decproof_verify_combined(vmn_decproof* p, const uint8_t* v_be, size_t vbytes, int* verdict);         /* :693-700 */
+/* Width omega.  After vmn_decproof_set_instance_wide (u: width arrays, f: (k + 1) * width arrays as above) A, B'_l, B_l and the
+ * combined B', B are width elements each: vmn_decproof_commit writes vmn_decproof_width(p) rows of elem_bytes to Bp_out and
+ * vmn_decproof_set_commitment reads as many from Bp_be, component 0 first (one row that is no group element: VMN_ERR_FORMAT);
+ * batch_input, batch(l) and batch_combined are ONE vmn_garray_expprod_multi over the components each; verify(l) and
+ * verify_combined check the y equation once and the B equation in every component.  The batching vector has N entries, and
+ * yp, the reply and the k_x >= q rule are those of width 1. */
+int vmn_decproof_set_instance_wide(vmn_decproof* p, size_t width, const vmn_garray* const* u, const uint8_t* y_be,
+                                   const vmn_garray* const* f);
+size_t vmn_decproof_width(const vmn_decproof* p);
+int vmn_decproof_combine_wide(vmn_decproof* p, const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* const* combinedf);
 
 /* ---- interactive derivation of independent generators -----------------------------------
  * distr/IndependentGeneratorsBasicI.java: setInstance :166-175, setBatchVector :186-193, commit :201-208,

@@ -173,6 +173,10 @@ def need_expr(name, ptype, pname, plist):
     proof = next((pt for pt in PROOF_TYPES if name.startswith(pt + "_")), None)
     pobj = hcast(proof + "*", plist[0][1]) if proof else None
     if k == "handles_out":
+        if name.endswith("_wide") and pname in ("f_out", "out"):
+            return "(size_t)width"
+        if pname == "outs":
+            return "(size_t)k"
         return {"wp_out": "2 * (size_t)width", "factors_out": "2 * (size_t)width", "s_out": "(size_t)width"}.get(pname, "1")
     if k == "handles_in":
         if pname in ("xs", "ys"):
@@ -181,8 +185,11 @@ def need_expr(name, ptype, pname, plist):
             return "2 * (size_t)width"
         if pname in ("s", "s_full"):
             return "(size_t)width"
+        if name.endswith("_wide") and pname in ("u", "combinedf"):
+            return "(size_t)width" if "width" in names else f"vmn_decproof_width({pobj})"
         if pname == "f":
-            return "(size_t)k + 1" if "k" in names else f"(size_t)vmn_decproof_parties({pobj}) + 1"
+            parties = "(size_t)k + 1" if "k" in names else f"(size_t)vmn_decproof_parties({pobj}) + 1"
+            return f"({parties}) * (size_t)width" if name.endswith("_wide") else parties
         if pname == "h" and name == "vmn_igen_set_instance":
             return f"(size_t)vmn_igen_parties({pobj}) + 1"
         return None
@@ -257,7 +264,9 @@ def need_expr(name, ptype, pname, plist):
             return f"2 * (size_t)width * {EB}"
         if pname == "partials_be":
             return f"(size_t)k * {EB}"
-        if pname == "y_be" and name == "vmn_decproof_set_instance":
+        if pname in ("Bp_out", "Bp_be") and proof == "vmn_decproof":          # width rows after a wide instance
+            return f"vmn_decproof_width({pobj}) * {EB}"
+        if pname == "y_be" and name in ("vmn_decproof_set_instance", "vmn_decproof_set_instance_wide"):
             return f"((size_t)vmn_decproof_parties({pobj}) + 1) * {EB}"
         if pname == "abs_be":
             return f"(size_t)threshold * {XB}"

@@ -6,6 +6,8 @@ MixNetElGamalVerifyFiatShamir.java:382-388).
 
     python tools/vmnv_vectors.py <nizkp dir> [-l PARTY] [-t der.rho,PoS] [--arrays]
     python tools/vmnv_vectors.py --demo <new dir> [-n 100]      write a directory with the C++ prover first (synthetic list)
+    python tools/vmnv_vectors.py <nizkp dir> -decrypt [--list FILE]      the decryption branch (:1545-1667): Dec.s, Dec.v
+    python tools/vmnv_vectors.py --demo <new dir> -decrypt [--width 3] [--parties 3] [--threshold 2]
 
 The directory layout is the reference's (verificatum-vmn_amd/proofdir.py); what `vmnv` reads from the protocol-info XML is
 in <dir>/params.json.  THE diff that would pin parity: on a machine with a JDK + VCR, run `vmnv -t der.rho,PoS ...` on a proof
@@ -35,10 +37,11 @@ DESCRIPTIONS = {                      # MixNetElGamalVerifyFiatShamirTool.java:8
     # not registered by the reference (private fields of its classes): printed for diffing two builds of THIS code
     "PoSC.A": "[not in the reference] PoSC. Batched permutation commitment.", "PoSC.C": "[not in the reference] PoSC. Derived intermediate values.",
     "PoSC.D": "[not in the reference] PoSC. Derived intermediate values.", "CCPoS.A": "[not in the reference] CCPoS. Batched permutation commitment.",
-    "CCPoS.B": "[not in the reference] CCPoS. Batched input ciphertexts."}
+    "CCPoS.B": "[not in the reference] CCPoS. Batched input ciphertexts.",
+    "Dec.s": "Dec. Seed to derive batching vector in hexadecimal notation.", "Dec.v": "Dec. Integer challenge in decimal notation."}
 ORDER = ["der.rho", "bas.h", "PoSC.s", "PoSC.v", "PoSC.A", "PoSC.C", "PoSC.D", "CCPoS.s", "CCPoS.A", "CCPoS.B", "CCPoS.v",
          "PoS.s", "PoS.A", "PoS.F", "PoS.B", "PoS.Ap", "PoS.Bp", "PoS.Cp", "PoS.Dp", "PoS.Fp", "PoS.v", "PoS.C",
-         "PoS.D", "PoS.k_A", "PoS.k_B", "PoS.k_C", "PoS.k_D", "PoS.k_E", "PoS.k_F"]
+         "PoS.D", "PoS.k_A", "PoS.k_B", "PoS.k_C", "PoS.k_D", "PoS.k_E", "PoS.k_F", "Dec.s", "Dec.v"]
 
 
 def selected(name, wanted):
@@ -53,6 +56,29 @@ def group_of(vmn, ctx, params):
     return vmn.ECqPGroup(ctx, params["group"]["curve"], java_widths=True)
 
 
+def demo_decryption(args, vmn, ctx, proofdir, randomsource, stdgroups):
+    """A synthetic list of width --width under a key shared among --parties parties (threshold --threshold), decrypted by
+    proofdir.write_decryption with every party played here."""
+    p, q, g = stdgroups.modp_group(args.bits)
+    k, thr, width = args.parties, args.threshold, args.width
+    params = {"version": "3.1.0", "sid": "MyDemo", "auxsid": "default", "rbitlen": 100, "vbitlenro": 256, "ebitlenro": 256,
+              "prg": "SHA-256", "rohash": "SHA-256", "rohash_name": "SHA-256", "width": width, "k": k, "threshold": thr,
+              "pgroup": f"ModPGroup(safe-prime modulus=2*order+1. order bit-length = {args.bits - 1})",
+              "group": {"kind": "modp", "p": format(p, "x"), "q": format(q, "x"), "g": format(g, "x")}}
+    grp = group_of(vmn, ctx, params)
+    rnd = randomsource.InsecureShaRandomSource(b"vmnv-demo-decrypt", q)
+    coeffs = rnd.ring_array(thr)
+    shares = [None] + [sum(c * pow(l, d, q) for d, c in enumerate(coeffs)) % q for l in range(1, k + 1)]
+    poly = [pow(g, c, p) for c in coeffs]
+    pkey = [g] * width + [poly[0]] * width
+    T = [grp.ringArray(rnd.ring_array(args.n)) for _ in range(width)]
+    M = [grp.exp(g, grp.ringArray(rnd.ring_array(args.n))) for _ in range(width)]
+    W = [grp.exp(g, t) for t in T] + [m.mul(grp.exp(poly[0], t)) for m, t in zip(M, T)]
+    proofdir.write_inputs(args.nizkp, grp, params, pkey, W)
+    proofdir.write_decryption(args.nizkp, grp, params, pkey, W, poly, shares, randomsource.SecureRandomSource(q), k, thr)
+    print(f"wrote {args.nizkp}: {args.n} ciphertexts of width {width}, {k} parties, threshold {thr}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("nizkp")
@@ -65,13 +91,21 @@ def main():
                     help="the directory holds a PRECOMPUTED shuffle for N_0 ciphertexts (PoSC + keep list + CCPoS files) instead of a PoS; "
                          "with --demo: write one (N_0 >= n)")
     ap.add_argument("--bits", type=int, default=2048)
+    ap.add_argument("-decrypt", "--decrypt", dest="decrypt", action="store_true",
+                    help="verify the threshold decryption of a list (modular groups) instead of a shuffle; with --demo: write one")
+    ap.add_argument("--list", default=None, help="-decrypt: the decrypted list (default: Ciphertexts.bt of the directory)")
+    ap.add_argument("--width", type=int, default=1, help="--demo -decrypt: width of the ciphertexts")
+    ap.add_argument("--parties", type=int, default=3, help="--demo -decrypt: number of parties k")
+    ap.add_argument("--threshold", type=int, default=2, help="--demo -decrypt: parties needed to decrypt")
     args = ap.parse_args()
     import json
     import __graft_entry__ as entry
     vmn = entry.load_package()
     from verificatum_vmn_amd import proofdir, randomsource, stdgroups
     ctx = vmn.Context(0)
-    if args.demo:
+    if args.demo and args.decrypt:
+        demo_decryption(args, vmn, ctx, proofdir, randomsource, stdgroups)
+    elif args.demo:
         p, q, g = stdgroups.modp_group(args.bits)
         params = {"version": "3.1.0", "sid": "MyDemo", "auxsid": "default", "rbitlen": 100, "vbitlenro": 256, "ebitlenro": 256,
                   "prg": "SHA-256", "rohash": "SHA-256", "rohash_name": "SHA-256", "width": 1,
@@ -103,6 +137,15 @@ def main():
     pkey = [grp.dec_el(b) for b in flat]
     vectors = {}
     n0 = args.precomputed or int(params.get("N_0", 0))
+    if args.decrypt:
+        verdict = proofdir.verify_decryption(args.nizkp, grp, params, pkey, args.list or proofdir.l_file(args.nizkp, 0), vectors)
+        for name in sorted(v for v in vectors if v.startswith("Dec.y_")):
+            print(f"\nTEST VECTOR\n{name} - [not in the reference] Dec. Public key share of a party.\n{vectors[name]}")
+        for name in ("Dec.s", "Dec.v"):
+            if name in vectors:
+                print(f"\nTEST VECTOR\n{name} - {DESCRIPTIONS[name]}\n{vectors[name]}")
+        print(f"\nverdict of the decryption: {'accepted' if verdict else 'REJECTED'}")
+        sys.exit(0 if verdict else 1)
     if n0:
         verdict = proofdir.verify_precomputed_shuffle(args.nizkp, args.l, grp, params, pkey, n0, vectors)
         if args.t == "der,PoS":

@@ -571,6 +571,20 @@ class PGroupElementArray(_ArrayBase):
             _check(lib().vmn_garray_exp_scalar(self._h, int_to_be(e, nb), C.c_size_t(nb), C.byref(h)))
         return self._new(h)
 
+    @staticmethod
+    def expMulti(arrays, e: int) -> list:
+        """``vmn_garray_exp_scalar_multi``: ``[a.exp(e) for a in arrays]`` for arrays of one group and one size (the components
+        of a width-omega list under a party's secret); over a modular group the arrays of a call share one launch."""
+        k = len(arrays)
+        if k == 0:
+            raise ValueError("expMulti needs at least one array")
+        hs = (C.c_void_p * k)(*[a._h for a in arrays])
+        outs = (C.c_void_p * k)()
+        e = int(e)
+        nb = max(1, (e.bit_length() + 7) // 8)
+        _check(lib().vmn_garray_exp_scalar_multi(hs, C.c_size_t(k), int_to_be(e, nb), C.c_size_t(nb), outs))
+        return [PGroupElementArray(arrays[0].group, C.c_void_p(h)) for h in outs]
+
     def expInts(self, exps: Sequence[int], ebits: int) -> "PGroupElementArray":
         """Exponents that are plain integers of ``ebits`` bits (not reduced mod q)."""
         nb = (ebits + 7) // 8

@@ -1,5 +1,6 @@
-// modp_shared_exp.h — variants of K1 beside k_modpow: ONE exponent for the whole array (out[i] = x[i]^e, sliding window),
-// and two independent exponentiations of small arrays in one launch (k_modpow_jobs, at the end).
+// modp_shared_exp.h — variants of K1 beside k_modpow: ONE exponent for the whole array (out[i] = x[i]^e, sliding window), for one
+// array or for several arrays of one size in one launch, and two independent exponentiations of small arrays in one launch
+// (k_modpow_jobs, at the end).
 //
 // The reference raises whole arrays to a single exponent in the decryption half of the mix-net -- the decryption factors
 // f = u^(-x_j / c), a full-length secret exponent per party (elgamal/DistrElGamalSession.java:365-385) -- and in the
@@ -34,18 +35,45 @@ __device__ __forceinline__ void slide_steps(u32 (&a)[C::L], const SlideStep* __r
     }
 }
 
-template <class C>
-__global__ void __launch_bounds__(BLOCK, C::MINW)
-k_modpow_shared(u32* __restrict__ out, const u32* __restrict__ x, const SlideStep* __restrict__ steps, int nsteps, int tsize, size_t n,
-                const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab) {
+// The arrays of one launch.  A party's decryption factors at width w are w arrays raised to ONE exponent
+// (DistrElGamalSession.java:365-389 over a product group): one launch per array would choose its geometry, plan its phases and
+// end in a tail w times, and at the reference's own sizes (10^4 elements) each leaves most of the device without a wave.  The
+// kernels below therefore walk GLOBAL tiles: tile T belongs to array T / ntiles and is that array's tile T % ntiles (block-uniform:
+// the pointers are picked with scalar instructions), and every array keeps its own ragged last tile.  One array is the case k = 1
+// of the same body (OneArray: no table, no division).
+constexpr int SHARED_ARRAYS = 8;
+struct SharedArrays {
+    const u32* x[SHARED_ARRAYS];
+    u32* out[SHARED_ARRAYS];
+    // the array of global tile T, and T's index among that array's tiles (the host keeps k * ntiles below 2^32)
+    __device__ __forceinline__ u32 array_of(size_t T, u32 ntiles) const { return (u32)T / ntiles; }
+    __device__ __forceinline__ size_t tile_of(size_t T, u32 a, u32 ntiles) const { return (u32)T - a * ntiles; }
+    __device__ __forceinline__ const u32* x_of(u32 a) const { return x[a]; }
+    __device__ __forceinline__ u32* out_of(u32 a) const { return out[a]; }
+};
+struct OneArray {
+    const u32* x;
+    u32* out;
+    __device__ __forceinline__ u32 array_of(size_t, u32) const { return 0; }
+    __device__ __forceinline__ size_t tile_of(size_t T, u32, u32) const { return T; }
+    __device__ __forceinline__ const u32* x_of(u32) const { return x; }
+    __device__ __forceinline__ u32* out_of(u32) const { return out; }
+};
+
+// `total` global tiles, `ntiles` of them per array of n elements; a table per lane slot in `tab`
+template <class C, class A>
+__device__ __forceinline__ void modpow_shared_tiles(const A& arrs, u32 ntiles, size_t total, const SlideStep* __restrict__ steps, int nsteps,
+                                                    int tsize, size_t n, const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab, u32* lds) {
     constexpr int W = C::W;
-    extern __shared__ u32 lds[];
     Lane<C> ln(lds);
     u32 nn[C::L];
     load_modulus<C>(nn, nmod, ln);
-    const size_t ntiles = (n + C::EPB - 1) / C::EPB;
     u32* mytab = tab + ((size_t)blockIdx.x * C::EPB + ln.eslot) * (size_t)tsize * W;
-    for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    for (size_t T = blockIdx.x; T < total; T += gridDim.x) {
+        const u32 arr = arrs.array_of(T, ntiles);
+        const size_t t = arrs.tile_of(T, arr, ntiles);
+        const u32* __restrict__ x = arrs.x_of(arr);
+        u32* __restrict__ out = arrs.out_of(arr);
         size_t el = t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
@@ -58,28 +86,30 @@ k_modpow_shared(u32* __restrict__ out, const u32* __restrict__ x, const SlideSte
     }
 }
 
-// k_modpow_shared for arrays of more than one round of tiles: the schedule's steps in phases from a queue of (phase, tile) units
-// (UnitQueue, modp_kernels.h); a tile's table of odd powers lives in a table of its own.  The decryption factors of a party -- one
-// full-length secret exponent over every ciphertext -- are this kernel's large case.
-template <class C>
-__global__ void __launch_bounds__(BLOCK, C::MINW)
-k_modpow_shared_phased(u32* __restrict__ out, const u32* __restrict__ x, const SlideStep* __restrict__ steps, int nsteps, int tsize,
-                       size_t n, const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab, int phases, u32* __restrict__ queue,
-                       u32* __restrict__ done) {
+// The same for more than one round of tiles: the schedule's steps in phases from a queue of (phase, global tile) units
+// (UnitQueue, modp_kernels.h); a tile's table of odd powers lives in a table of its own, indexed by the GLOBAL element
+// T * EPB + slot.  The decryption factors of a party -- one full-length secret exponent over every ciphertext -- are this
+// kernel's large case.
+template <class C, class A>
+__device__ __forceinline__ void modpow_shared_units(const A& arrs, u32 ntiles, u32 total, const SlideStep* __restrict__ steps, int nsteps,
+                                                    int tsize, size_t n, const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab,
+                                                    int phases, u32* __restrict__ queue, u32* __restrict__ done, u32* s_unit, u32* lds) {
     constexpr int W = C::W;
-    extern __shared__ u32 lds[];
-    __shared__ u32 s_unit;
     Lane<C> ln(lds);
     u32 nn[C::L];
     load_modulus<C>(nn, nmod, ln);
     const int M = nsteps - 1;                            // steps of the main loop (step 0 is the first table read)
-    UnitQueue q(queue, done, &s_unit, (u32)((n + C::EPB - 1) / C::EPB), phases);
+    UnitQueue q(queue, done, s_unit, total, phases);
     while (q.take()) {
         const int ph = q.ph;
-        size_t el = (size_t)q.t * C::EPB + ln.eslot;
+        const u32 arr = arrs.array_of(q.t, ntiles);
+        const size_t t = arrs.tile_of(q.t, arr, ntiles);
+        const u32* __restrict__ x = arrs.x_of(arr);
+        u32* __restrict__ out = arrs.out_of(arr);
+        size_t el = t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
-        u32* mytab = tab + el * (size_t)tsize * W;
+        u32* mytab = tab + ((size_t)q.t * C::EPB + ln.eslot) * (size_t)tsize * W;
         u32 a[C::L];
         if (ph == 0) {
             odd_power_table<C>(a, mytab, tsize, x + ec * W, ln, nn, n0inv);
@@ -94,6 +124,41 @@ k_modpow_shared_phased(u32* __restrict__ out, const u32* __restrict__ x, const S
         if (live) store_elem<C>(out + el * W, a, ln);
         q.hand_over();
     }
+}
+
+template <class C>
+__global__ void __launch_bounds__(BLOCK, C::MINW)
+k_modpow_shared(u32* __restrict__ out, const u32* __restrict__ x, const SlideStep* __restrict__ steps, int nsteps, int tsize, size_t n,
+                const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab) {
+    extern __shared__ u32 lds[];
+    modpow_shared_tiles<C>(OneArray{x, out}, 0, (n + C::EPB - 1) / C::EPB, steps, nsteps, tsize, n, nmod, n0inv, tab, lds);
+}
+template <class C>
+__global__ void __launch_bounds__(BLOCK, C::MINW)
+k_modpow_shared_phased(u32* __restrict__ out, const u32* __restrict__ x, const SlideStep* __restrict__ steps, int nsteps, int tsize,
+                       size_t n, const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab, int phases, u32* __restrict__ queue,
+                       u32* __restrict__ done) {
+    extern __shared__ u32 lds[];
+    __shared__ u32 s_unit;
+    modpow_shared_units<C>(OneArray{x, out}, 0, (u32)((n + C::EPB - 1) / C::EPB), steps, nsteps, tsize, n, nmod, n0inv, tab, phases, queue,
+                           done, &s_unit, lds);
+}
+// several arrays of n elements each (ntiles tiles each, `total` = arrays x ntiles)
+template <class C>
+__global__ void __launch_bounds__(BLOCK, C::MINW)
+k_modpow_shared_multi(SharedArrays arrs, u32 ntiles, u32 total, const SlideStep* __restrict__ steps, int nsteps, int tsize, size_t n,
+                      const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab) {
+    extern __shared__ u32 lds[];
+    modpow_shared_tiles<C>(arrs, ntiles, total, steps, nsteps, tsize, n, nmod, n0inv, tab, lds);
+}
+template <class C>
+__global__ void __launch_bounds__(BLOCK, C::MINW)
+k_modpow_shared_multi_phased(SharedArrays arrs, u32 ntiles, u32 total, const SlideStep* __restrict__ steps, int nsteps, int tsize, size_t n,
+                             const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab, int phases, u32* __restrict__ queue,
+                             u32* __restrict__ done) {
+    extern __shared__ u32 lds[];
+    __shared__ u32 s_unit;
+    modpow_shared_units<C>(arrs, ntiles, total, steps, nsteps, tsize, n, nmod, n0inv, tab, phases, queue, done, &s_unit, lds);
 }
 
 // Two independent exponentiations in ONE launch (small arrays): job 0 = out0[i] = x0[i]^e0 (one exponent for all), job 1 =

@@ -1649,14 +1649,15 @@ struct PhasePlan {
     size_t epb, ntiles;
     int phases = 1;            // > 1 after split(): launch the phased kernel with table(), queue() and done()
     DevTmp tab, sync_words;
-    PhasePlan(vmn_ctx* ctx, const vmn_modulus& m, size_t n)
-        : max_blocks((unsigned)(ctx->num_cus * blocks_per_cu(m))), epb((size_t)(BLOCK / m.LPE)), ntiles((n + epb - 1) / epb), tab(ctx),
-          sync_words(ctx) {
+    // (`arrays` arrays of n elements in one launch: their tiles side by side, each array with its own ragged last tile)
+    PhasePlan(vmn_ctx* ctx, const vmn_modulus& m, size_t n, size_t arrays = 1)
+        : max_blocks((unsigned)(ctx->num_cus * blocks_per_cu(m))), epb((size_t)(BLOCK / m.LPE)), ntiles(arrays * ((n + epb - 1) / epb)),
+          tab(ctx), sync_words(ctx) {
         if (const char* mb = getenv("VMN_MODPOW_MAX_BLOCKS")) {       // test hook: a "device" of few workgroup slots, so that small arrays take the phased kernel
             const int v = atoi(mb);
             if (v >= 1) max_blocks = std::min<unsigned>(max_blocks, (unsigned)v);
         }
-        grid = std::min<unsigned>(egrid(m, n), max_blocks);
+        grid = (unsigned)std::min<size_t>(ntiles, max_blocks);
     }
     // bytes of the plain kernel's tables: `rows` rows per lane slot
     size_t slot_tables_bytes(const vmn_modulus& m, size_t rows) const { return (size_t)grid * epb * rows * elem_words(m) * sizeof(uint32_t); }
@@ -1734,7 +1735,11 @@ static int sliding_window_bits(int ebits) {
     }
     return best;
 }
-static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, const Big& e, int ebits, size_t n, uint32_t* out) {
+// `k` arrays of n elements each, all to the exponent e.  Up to SHARED_ARRAYS arrays share a launch: the geometry, the phase plan,
+// the tables and the queue are those of k n elements in k ceil(n / EPB) tiles (modp_shared_exp.h); one array takes the kernel
+// without the table of arrays.
+static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* const* xs, uint32_t* const* outs, size_t k, const Big& e,
+                         int ebits, size_t n) {
     const int w = sliding_window_bits(ebits);
     std::vector<SlideStep> steps;
     int pending = 0;
@@ -1754,27 +1759,45 @@ static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x,
         i = l - 1;
     }
     if (pending) steps.push_back(SlideStep{pending, -1});
-    for (size_t k = 1; k < steps.size(); ++k) {
-        squarings += steps[k].sq;
-        mults += steps[k].idx >= 0 ? 1 : 0;
+    for (size_t s = 1; s < steps.size(); ++s) {
+        squarings += steps[s].sq;
+        mults += steps[s].idx >= 0 ? 1 : 0;
     }
     const int tsize = 1 << (w - 1);
-    const vmn_modulus& m = geom(ctx, m0, n);
-    PhasePlan pl(ctx, m, n);
-    VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)tsize)));
     DevTmp dsteps(ctx);
     VMN_TRY(dsteps.alloc(steps.size() * sizeof(SlideStep)));
     VMN_TRY(h2d(ctx, dsteps.p, steps.data(), steps.size() * sizeof(SlideStep)));
-    note_work(ctx, m, (double)n * (double)(mults + tsize - 1), (double)n * (double)(squarings + 1));
-    VMN_TRY(pl.split(ctx, m, (int)steps.size() - 1, (size_t)tsize));
     const SlideStep* d_steps = dsteps.as<SlideStep>();
-    return with_cfg(m, [&]<class C, class W>(C, W) {
-        if (pl.phases > 1)
-            return launch(ctx, "modpow", k_modpow_shared_phased<C>, pl.max_blocks, lds_bytes(m), out, x, d_steps, (int)steps.size(), tsize, n,
-                          m.d_n, m.n0inv, pl.table(), pl.phases, pl.queue(), pl.done());
-        return launch(ctx, "modpow", k_modpow_shared<C>, pl.grid, lds_bytes(m), out, x, d_steps, (int)steps.size(), tsize, n, m.d_n, m.n0inv,
-                      reinterpret_cast<uint32_t*>(ctx->scratch));
-    });
+    for (size_t a0 = 0; a0 < k; a0 += SHARED_ARRAYS) {
+        const size_t ga = std::min<size_t>(SHARED_ARRAYS, k - a0);
+        const vmn_modulus& m = geom(ctx, m0, ga * n);
+        PhasePlan pl(ctx, m, n, ga);
+        VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)tsize)));
+        note_work(ctx, m, (double)(ga * n) * (double)(mults + tsize - 1), (double)(ga * n) * (double)(squarings + 1));
+        VMN_TRY(pl.split(ctx, m, (int)steps.size() - 1, (size_t)tsize));
+        const uint32_t* x = xs[a0];
+        uint32_t* out = outs[a0];
+        SharedArrays arrs{};
+        for (size_t a = 0; a < ga; ++a) {
+            arrs.x[a] = xs[a0 + a];
+            arrs.out[a] = outs[a0 + a];
+        }
+        const uint32_t ntiles = (uint32_t)(pl.ntiles / ga), total = (uint32_t)pl.ntiles;
+        VMN_TRY(with_cfg(m, [&]<class C, class W>(C, W) {
+            if (ga == 1 && pl.phases > 1)
+                return launch(ctx, "modpow", k_modpow_shared_phased<C>, pl.max_blocks, lds_bytes(m), out, x, d_steps, (int)steps.size(), tsize,
+                              n, m.d_n, m.n0inv, pl.table(), pl.phases, pl.queue(), pl.done());
+            if (ga == 1)
+                return launch(ctx, "modpow", k_modpow_shared<C>, pl.grid, lds_bytes(m), out, x, d_steps, (int)steps.size(), tsize, n, m.d_n,
+                              m.n0inv, reinterpret_cast<uint32_t*>(ctx->scratch));
+            if (pl.phases > 1)
+                return launch(ctx, "modpow", k_modpow_shared_multi_phased<C>, pl.max_blocks, lds_bytes(m), arrs, ntiles, total, d_steps,
+                              (int)steps.size(), tsize, n, m.d_n, m.n0inv, pl.table(), pl.phases, pl.queue(), pl.done());
+            return launch(ctx, "modpow", k_modpow_shared_multi<C>, pl.grid, lds_bytes(m), arrs, ntiles, total, d_steps, (int)steps.size(), tsize,
+                          n, m.d_n, m.n0inv, reinterpret_cast<uint32_t*>(ctx->scratch));
+        }));
+    }
+    return VMN_OK;
 }
 
 // big-endian integers (ebytes each) -> packed little-endian words on the host
@@ -2004,32 +2027,76 @@ extern "C" int vmn_garray_exp_ints(const vmn_garray* x, const uint8_t* exps_be, 
     return VMN_OK;
 }
 
-extern "C" int vmn_garray_exp_scalar(const vmn_garray* x, const uint8_t* e_be, size_t ebytes, vmn_garray** out) {
-    ARG_CHECK(x && e_be && out && ebytes > 0, "null argument");
-    vmn_group* g = x->grp;
-    vmn_ctx* ctx = LANE(g->ctx);
-    VMN_ENTER(ctx);
+// outs[c][i] = xs[c][i]^e for k arrays of one group and one size.  Modular groups and exponents above 32 bits: the sliding window
+// with one exponent for all, the arrays of a call in one launch (VMN_EXP_MULTI_FUSED=0, read per call: one launch per array);
+// curves and short exponents: the fixed-window kernel, array by array.  On failure nothing stays allocated.
+static bool exp_multi_fused() {
+    const char* env = getenv("VMN_EXP_MULTI_FUSED");
+    return !(env && *env && atoi(env) == 0);
+}
+static int exp_scalar_arrays(vmn_ctx* ctx, vmn_group* g, const vmn_garray* const* xs, size_t k, const uint8_t* e_be, size_t ebytes,
+                             vmn_garray** outs) {
     int ewords = (int)((ebytes + 3) / 4);
     Big e = hostbig::from_be(e_be, ebytes, ewords);
     int ebits = std::max(1, hostbig::bit_length(e));
     ewords = (ebits + 31) / 32;
-    vmn_garray* r = nullptr;
-    VMN_TRY(new_garray(g, x->n, &r));
+    const size_t n = xs[0]->n;
+    for (size_t c = 0; c < k; ++c) outs[c] = nullptr;
+    auto fail = [&](int rc) {
+        for (size_t c = 0; c < k; ++c) {
+            if (outs[c]) vmn_garray_free(outs[c]);
+            outs[c] = nullptr;
+        }
+        return rc;
+    };
+    for (size_t c = 0; c < k; ++c) {
+        int rc = new_garray(g, n, &outs[c]);
+        if (rc != VMN_OK) return fail(rc);
+    }
     DevTmp ew(ctx);
     int rc = ew.alloc(ewords * sizeof(uint32_t));
     if (rc == VMN_OK) {
         rc = h2d(ctx, ew.p, e.data(), ewords * sizeof(uint32_t));
     }
-    if (rc == VMN_OK && !g->P.ec && ebits > 32 && x->n > 0 && sliding_window_bits(ebits) > 0)
-        rc = modpow_shared(ctx, g->P, x->d, e, ebits, x->n, r->d);                 // one exponent for all: sliding window
-    else if (rc == VMN_OK)
-        rc = modpow_words(ctx, g->P, x->d, ew.as<uint32_t>(), ewords, 0, ebits, x->n, r->d);
-    if (rc != VMN_OK) {
-        vmn_garray_free(r);
-        return rc;
+    if (rc == VMN_OK && !g->P.ec && ebits > 32 && n > 0 && sliding_window_bits(ebits) > 0) {      // one exponent for all: sliding window
+        std::vector<const uint32_t*> xd(k);
+        std::vector<uint32_t*> od(k);
+        for (size_t c = 0; c < k; ++c) {
+            xd[c] = xs[c]->d;
+            od[c] = outs[c]->d;
+        }
+        const size_t epb_min = BLOCK / 16;                             // (the widest geometry: the fewest elements per tile)
+        const bool fused = k > 1 && exp_multi_fused() && (n + epb_min - 1) / epb_min < ((size_t)1 << 32) / SHARED_ARRAYS;
+        if (fused) rc = modpow_shared(ctx, g->P, xd.data(), od.data(), k, e, ebits, n);
+        for (size_t c = 0; !fused && rc == VMN_OK && c < k; ++c) rc = modpow_shared(ctx, g->P, &xd[c], &od[c], 1, e, ebits, n);
+    } else {
+        for (size_t c = 0; rc == VMN_OK && c < k; ++c)
+            rc = modpow_words(ctx, g->P, xs[c]->d, ew.as<uint32_t>(), ewords, 0, ebits, n, outs[c]->d);
     }
+    return rc == VMN_OK ? VMN_OK : fail(rc);
+}
+
+extern "C" int vmn_garray_exp_scalar(const vmn_garray* x, const uint8_t* e_be, size_t ebytes, vmn_garray** out) {
+    ARG_CHECK(x && e_be && out && ebytes > 0, "null argument");
+    vmn_group* g = x->grp;
+    vmn_ctx* ctx = LANE(g->ctx);
+    VMN_ENTER(ctx);
+    vmn_garray* r = nullptr;
+    VMN_TRY(exp_scalar_arrays(ctx, g, &x, 1, e_be, ebytes, &r));
     *out = r;
     return VMN_OK;
+}
+
+extern "C" int vmn_garray_exp_scalar_multi(const vmn_garray* const* xs, size_t k, const uint8_t* e_be, size_t ebytes, vmn_garray** outs) {
+    ARG_CHECK(xs && e_be && outs && ebytes > 0, "null argument");
+    ARG_CHECK(k > 0, "no arrays");
+    for (size_t c = 0; c < k; ++c) outs[c] = nullptr;
+    for (size_t c = 0; c < k; ++c) ARG_CHECK(xs[c], "null array");
+    for (size_t c = 1; c < k; ++c) ARG_CHECK(xs[c]->grp == xs[0]->grp && xs[c]->n == xs[0]->n, "the arrays differ in group or size");
+    vmn_group* g = xs[0]->grp;
+    vmn_ctx* ctx = LANE(g->ctx);
+    VMN_ENTER(ctx);
+    return exp_scalar_arrays(ctx, g, xs, k, e_be, ebytes, outs);
 }
 
 // out[i] = x[i]^e * y[i]^f[i] over a modular group, exponents in packed words on the device: e one exponent of ewords words,

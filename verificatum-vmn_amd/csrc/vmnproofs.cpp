@@ -2286,25 +2286,32 @@ int lagrange(const HostGroup& G, const uint8_t* correct, int k, int threshold, s
 
 }  // namespace vmnp
 
+// A value of the plaintext group G^width (DistrElGamalSessionBasic's u, A, B', B_l live there; g, y, the secret, the randomizer,
+// the reply and the challenge stay in G / Z_q): one element per component, component 0 first.
+typedef std::vector<Bytes> Wide;
+
 struct vmn_decproof {
     HostGroup G;
     int j = 0, k = 0, threshold = 0, ebitlen = 0, e_bits = 0;
+    size_t width = 1;
     bool has_rs = false;
     vmn_random_source rs{};
     Num inverseFactor;
-    const vmn_garray* u = nullptr;
+    std::vector<const vmn_garray*> u;               // width component arrays
     std::vector<Bytes> y;
-    std::vector<const vmn_garray*> f;
+    std::vector<const vmn_garray*> f;               // (k + 1) * width: entry l * width + c
     RA e;
-    Bytes A;
+    Wide A;
     Num x, r;
-    std::vector<Bytes> yp, Bp, B;
+    std::vector<Bytes> yp;
+    std::vector<Wide> Bp, B;
     std::vector<Num> k_x;
     std::vector<char> have_kx;
     // combined
-    Bytes combinedyp, combinedBp, combinedy, combinedB;
+    Bytes combinedyp, combinedy;
+    Wide combinedBp, combinedB;
     Num combinedk_x;
-    const vmn_garray* combinedf = nullptr;
+    std::vector<const vmn_garray*> combinedf;       // width
 
     int init(vmn_group* grp, int j_, int k_, int threshold_, int ebitlen_, const vmn_random_source* r_) {
         TRY(G.init(grp));
@@ -2320,29 +2327,58 @@ struct vmn_decproof {
         }
         inverseFactor = G.Zq.inv(prod_factor(G, k));
         y.assign(k + 1, Bytes());
-        f.assign(k + 1, nullptr);
         yp.assign(k + 1, Bytes());
-        Bp.assign(k + 1, Bytes());
-        B.assign(k + 1, Bytes());
+        Bp.assign(k + 1, Wide());
+        B.assign(k + 1, Wide());
         k_x.assign(k + 1, Num());
         have_kx.assign(k + 1, 0);
         return VMN_OK;
     }
     int party(int l) const { return l >= 1 && l <= k ? VMN_OK : fail(VMN_ERR_ARG, "party index %d outside 1..%d", l, k); }
-    int set_instance(const vmn_garray* u_, const uint8_t* y_be, const vmn_garray* const* f_) {
-        REQUIRE(u_ && y_be && f_, "null argument");
-        u = u_;
+    const vmn_garray* const* factors(int l) const { return f.data() + (size_t)l * width; }
+    bool has_factors(int l) const { return !f.empty() && factors(l)[0] != nullptr; }
+    int set_instance(size_t width_, const vmn_garray* const* u_, const uint8_t* y_be, const vmn_garray* const* f_) {
+        REQUIRE(width_ >= 1 && u_ && y_be && f_, "null argument");
+        for (size_t c = 0; c < width_; ++c) {
+            REQUIRE(u_[c], "null argument");
+            if (vmn_garray_size(u_[c]) != vmn_garray_size(u_[0])) return fail(VMN_ERR_ARG, "the components of u differ in size");
+        }
+        if (width_ != width) {                          // values of another width are no values of this instance
+            A.clear();
+            combinedB.clear();
+            for (int l = 0; l <= k; ++l) {
+                Bp[l].clear();
+                B[l].clear();
+            }
+        }
+        width = width_;
+        u.assign(u_, u_ + width);
+        f.assign((size_t)(k + 1) * width, nullptr);
         for (int l = 1; l <= k; ++l) {
             y[l].assign(y_be + (size_t)l * G.eb, y_be + (size_t)(l + 1) * G.eb);
-            f[l] = f_[l];
-            if (f[l] && vmn_garray_size(f[l]) != vmn_garray_size(u)) return fail(VMN_ERR_ARG, "decryption factors of party %d differ in size from u", l);
+            const vmn_garray* const* fl = f_ + (size_t)l * width;
+            for (size_t c = 0; c < width; ++c) {
+                if (!fl[c] != !fl[0]) return fail(VMN_ERR_ARG, "decryption factors of party %d lack a component", l);
+                f[(size_t)l * width + c] = fl[c];
+                if (fl[c] && vmn_garray_size(fl[c]) != vmn_garray_size(u[0])) return fail(VMN_ERR_ARG, "decryption factors of party %d differ in size from u", l);
+            }
         }
         return VMN_OK;
     }
+    // arrays.expProd(e) in every component: ONE multi-exponentiation, the digits of e are sorted once
+    int expprod(const vmn_garray* const* arrays, Wide& out) const {
+        Bytes flat(width * G.eb);
+        if (width == 1)
+            TRY(vmn_garray_expprod(arrays[0], e, e_bits, flat.data()));
+        else
+            TRY(vmn_garray_expprod_multi(arrays, width, e, e_bits, flat.data()));
+        out.assign(width, Bytes());
+        for (size_t c = 0; c < width; ++c) out[c].assign(flat.begin() + c * G.eb, flat.begin() + (c + 1) * G.eb);
+        return VMN_OK;
+    }
     int batch_input() {
-        REQUIRE(u && e.p, "batchInput needs the instance and the batching vector");
-        A.resize(G.eb);
-        return vmn_garray_expprod(u, e, e_bits, A.data());                       // :524-526
+        REQUIRE(!u.empty() && e.p, "batchInput needs the instance and the batching vector");
+        return expprod(u.data(), A);                                             // :524-526
     }
     int commit(const uint8_t* x_be, uint8_t* yp_out, uint8_t* Bp_out) {
         REQUIRE(x_be && yp_out && Bp_out && has_rs && !A.empty(), "commit needs a random source and batchInput()");
@@ -2352,9 +2388,10 @@ struct vmn_decproof {
         r = G.ring_from(rows);
         if (vmn::num64::cmp(r, G.Zq.n) >= 0) return fail(VMN_ERR_FORMAT, "random source returned a value >= q");
         TRY(G.el_exp(G.g, r, yp[j]));                                            // y' = g^r
-        TRY(G.el_exp(A, r, Bp[j]));                                              // B' = A^r
+        Bp[j].assign(width, Bytes());
+        for (size_t c = 0; c < width; ++c) TRY(G.el_exp(A[c], r, Bp[j][c]));     // B' = A^r, component by component
         memcpy(yp_out, yp[j].data(), G.eb);
-        memcpy(Bp_out, Bp[j].data(), G.eb);
+        for (size_t c = 0; c < width; ++c) memcpy(Bp_out + c * G.eb, Bp[j][c].data(), G.eb);
         return VMN_OK;
     }
     int reply(const uint8_t* v_be, size_t vbytes, uint8_t* kx_out) {
@@ -2366,70 +2403,86 @@ struct vmn_decproof {
         memcpy(kx_out, out.data(), G.xb);
         return VMN_OK;
     }
+    int set_commitment(int l, const uint8_t* yp_be, const uint8_t* Bp_be) {
+        Bytes a(yp_be, yp_be + G.eb);
+        Wide b(width);
+        std::vector<const Bytes*> els{&a};
+        for (size_t c = 0; c < width; ++c) {
+            b[c].assign(Bp_be + c * G.eb, Bp_be + (c + 1) * G.eb);
+            els.push_back(&b[c]);
+        }
+        int ok = 1;
+        TRY(G.check_elements(els, &ok));
+        if (!ok) return fail(VMN_ERR_FORMAT, "commitment holds a value that is not a group element");
+        yp[l] = a;
+        Bp[l] = b;
+        return VMN_OK;
+    }
+    // y^(-cv) y' = g^k checked once, B^v B' = A^k in every component (:693-700, :718-727)
+    int check(const Bytes& y_, const Num& yexp, const Bytes& yp_, const Wide& B_, const Wide& Bp_, const Num& v, const Num& kx, int* verdict) const {
+        Bytes yinv, t, lhs, rhs;
+        TRY(G.el_inv(y_, yinv));
+        TRY(G.el_exp(yinv, yexp, t));
+        TRY(G.el_mul(t, yp_, lhs));
+        TRY(G.el_exp(G.g, kx, rhs));
+        int ok = lhs == rhs;
+        for (size_t c = 0; c < width; ++c) {
+            TRY(G.el_exp(B_[c], v, t));
+            TRY(G.el_mul(t, Bp_[c], lhs));
+            TRY(G.el_exp(A[c], kx, rhs));
+            ok = ok && lhs == rhs;
+        }
+        *verdict = ok;
+        return VMN_OK;
+    }
     int verify(int l, const uint8_t* v_be, size_t vbytes, int* verdict) {
         TRY(party(l));
-        REQUIRE(verdict && v_be && vbytes && !A.empty() && !B[l].empty() && !yp[l].empty() && have_kx[l], "verify needs batch(l), the commitment and the reply of l");
+        REQUIRE(verdict && v_be && vbytes && !A.empty() && B[l].size() == width && Bp[l].size() == width && !yp[l].empty() && have_kx[l],
+                "verify needs batch(l), the commitment and the reply of l");
         if (have_kx[l] == 2) {                                                   // malformed reply: verdicts[l] = false (:719-721)
             *verdict = 0;
             return VMN_OK;
         }
         Num v = G.reduce(v_be, vbytes);
-        Bytes yinv, t, lhs, rhs;
-        TRY(G.el_inv(y[l], yinv));
-        TRY(G.el_exp(yinv, G.Zq.mul(inverseFactor, v), t));
-        TRY(G.el_mul(t, yp[l], lhs));
-        TRY(G.el_exp(G.g, k_x[l], rhs));
-        const int ok1 = lhs == rhs;
-        TRY(G.el_exp(B[l], v, t));
-        TRY(G.el_mul(t, Bp[l], lhs));
-        TRY(G.el_exp(A, k_x[l], rhs));
-        *verdict = ok1 && lhs == rhs;
-        return VMN_OK;
+        return check(y[l], G.Zq.mul(inverseFactor, v), yp[l], B[l], Bp[l], v, k_x[l], verdict);
     }
-    int combine(const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* combinedf_) {
+    int combine(const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* const* combinedf_) {
         REQUIRE(correct && combinedy_be && combinedf_, "null argument");
+        for (size_t c = 0; c < width; ++c) REQUIRE(combinedf_[c], "null argument");
         std::vector<Num> abs;
         std::vector<int> neg, parties;
         TRY(lagrange(G, correct, k, threshold, abs, neg, &parties));
         combinedyp = G.one();
-        combinedBp = G.one();
+        combinedBp.assign(width, G.one());
         combinedk_x = Num(G.ql, 0);
         for (size_t t = 0; t < parties.size(); ++t) {
             const int l = parties[t];
-            REQUIRE(!yp[l].empty() && have_kx[l], "combine needs the commitment and the reply of every combined party");
+            REQUIRE(!yp[l].empty() && Bp[l].size() == width && have_kx[l], "combine needs the commitment and the reply of every combined party");
             Num ex = neg[t] ? G.Zq.neg(abs[t]) : abs[t];
             Bytes a, b2;
             TRY(G.el_exp(yp[l], ex, a));
             TRY(G.el_mul(combinedyp, a, b2));
             combinedyp = b2;
-            TRY(G.el_exp(Bp[l], ex, a));
-            TRY(G.el_mul(combinedBp, a, b2));
-            combinedBp = b2;
+            for (size_t c = 0; c < width; ++c) {
+                TRY(G.el_exp(Bp[l][c], ex, a));
+                TRY(G.el_mul(combinedBp[c], a, b2));
+                combinedBp[c] = b2;
+            }
             combinedk_x = G.Zq.add(combinedk_x, G.Zq.mul(k_x[l], ex));
         }
         combinedy.assign(combinedy_be, combinedy_be + G.eb);
-        combinedf = combinedf_;
+        combinedf.assign(combinedf_, combinedf_ + width);
+        combinedB.clear();
         return VMN_OK;
     }
     int batch_combined() {
-        REQUIRE(combinedf && e.p, "batchCombined needs combine() and the batching vector");
-        combinedB.resize(G.eb);
-        return vmn_garray_expprod(combinedf, e, e_bits, combinedB.data());
+        REQUIRE(!combinedf.empty() && e.p, "batchCombined needs combine() and the batching vector");
+        return expprod(combinedf.data(), combinedB);
     }
     int verify_combined(const uint8_t* v_be, size_t vbytes, int* verdict) {
         REQUIRE(verdict && v_be && vbytes && !combinedB.empty() && !A.empty(), "verifyCombined needs batchCombined()");
         Num v = G.reduce(v_be, vbytes);
-        Bytes yinv, t, lhs, rhs;
-        TRY(G.el_inv(combinedy, yinv));
-        TRY(G.el_exp(yinv, v, t));
-        TRY(G.el_mul(t, combinedyp, lhs));
-        TRY(G.el_exp(G.g, combinedk_x, rhs));
-        const int ok1 = lhs == rhs;
-        TRY(G.el_exp(combinedB, v, t));
-        TRY(G.el_mul(t, combinedBp, lhs));
-        TRY(G.el_exp(A, combinedk_x, rhs));
-        *verdict = ok1 && lhs == rhs;
-        return VMN_OK;
+        return check(combinedy, v, combinedyp, combinedB, combinedBp, v, combinedk_x, verdict);
     }
 };
 
@@ -2932,7 +2985,8 @@ vmn_group* vmn_igen_group(const vmn_igen* p) { return p ? p->G.grp : nullptr; }
 size_t vmn_pos_size(const vmn_pos* p) { return p ? p->Ntot : 0; }
 size_t vmn_posc_size(const vmn_posc* p) { return p ? p->Ntot : 0; }
 size_t vmn_ccpos_size(const vmn_ccpos* p) { return p ? p->Ntot : 0; }
-size_t vmn_decproof_size(const vmn_decproof* p) { return p ? vmn_garray_size(p->u) : 0; }
+size_t vmn_decproof_size(const vmn_decproof* p) { return p && !p->u.empty() ? vmn_garray_size(p->u[0]) : 0; }
+size_t vmn_decproof_width(const vmn_decproof* p) { return p ? p->width : 0; }
 size_t vmn_igen_size(const vmn_igen* p) { return p ? p->N : 0; }
 int vmn_decproof_parties(const vmn_decproof* p) { return p ? p->k : 0; }
 int vmn_igen_parties(const vmn_igen* p) { return p ? p->threshold : 0; }
@@ -3155,53 +3209,73 @@ int vmn_lagrange_coefficients(vmn_group* grp, const uint8_t* correct, int k, int
     }
     return VMN_OK;
 }
-int vmn_decryption_factors(vmn_group* grp, const vmn_garray* u, const uint8_t* secret_be, int k, vmn_garray** f_out) {
-    if (!grp || !u || !secret_be || !f_out || k < 1) return fail(VMN_ERR_ARG, "vmn_decryption_factors: bad argument");
+int vmn_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* const* u, const uint8_t* secret_be, int k, vmn_garray** f_out) {
+    if (!grp || !u || !secret_be || !f_out || k < 1 || width < 1) return fail(VMN_ERR_ARG, "vmn_decryption_factors: bad argument");
+    for (size_t c = 0; c < width; ++c) {
+        if (!u[c]) return fail(VMN_ERR_ARG, "vmn_decryption_factors: bad argument");
+    }
     HostGroup G;
     TRY(G.init(grp));
     // firstComponents.exp(secretKey.neg().mul(inverseFactor))   DistrElGamalSession.java:384-385
     Num ex = G.Zq.mul(G.Zq.neg(G.ring_from(secret_be)), G.Zq.inv(prod_factor(G, k)));
     Bytes eb = G.ring_bytes(ex);
-    return vmn_garray_exp_scalar(u, eb.data(), eb.size(), f_out);
+    return vmn_garray_exp_scalar_multi(u, width, eb.data(), eb.size(), f_out);
 }
-int vmn_combine_decryption_factors(vmn_group* grp, const vmn_garray* const* f, const uint8_t* correct, int k, int threshold,
-                                   vmn_garray** out) {
-    if (!grp || !f || !correct || !out) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: null argument");
+int vmn_decryption_factors(vmn_group* grp, const vmn_garray* u, const uint8_t* secret_be, int k, vmn_garray** f_out) {
+    return vmn_decryption_factors_wide(grp, 1, &u, secret_be, k, f_out);
+}
+int vmn_combine_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* const* f, const uint8_t* correct, int k, int threshold,
+                                        vmn_garray** out) {
+    if (!grp || !f || !correct || !out || width < 1) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: null argument");
     HostGroup G;
     TRY(G.init(grp));
     std::vector<Num> abs;
     std::vector<int> neg, parties;
     TRY(lagrange(G, correct, k, threshold, abs, neg, &parties));
-    GA pos, negp;                                   // products of the positive / negative parts (:465-503)
+    std::vector<GA> pos(width), negp(width);        // products of the positive / negative parts (:465-503), per component
     for (size_t t = 0; t < parties.size(); ++t) {
         if (vmn::num64::is_zero(abs[t])) continue;
-        const vmn_garray* base = f[parties[t]];
-        if (!base) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: factors of party %d are missing", parties[t]);
+        const vmn_garray* const* base = f + (size_t)parties[t] * width;
+        for (size_t c = 0; c < width; ++c) {
+            if (!base[c]) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: factors of party %d are missing", parties[t]);
+        }
         Bytes eb = G.ring_bytes(abs[t]);
-        GA tpow;
-        TRY(vmn_garray_exp_scalar(base, eb.data(), eb.size(), tpow.out()));
-        GA& acc = neg[t] ? negp : pos;
-        if (!acc.p) {
-            acc.p = tpow.release();
+        std::vector<vmn_garray*> raw(width, nullptr);
+        TRY(vmn_garray_exp_scalar_multi(base, width, eb.data(), eb.size(), raw.data()));       // the party's components: one call
+        std::vector<GA> tpow(width);
+        for (size_t c = 0; c < width; ++c) tpow[c].p = raw[c];
+        for (size_t c = 0; c < width; ++c) {
+            GA& acc = neg[t] ? negp[c] : pos[c];
+            if (!acc.p) {
+                acc.p = tpow[c].release();
+            } else {
+                GA prod;
+                TRY(vmn_garray_mul(acc, tpow[c], prod.out()));
+                acc.reset();
+                acc.p = prod.release();
+            }
+        }
+    }
+    if (!pos[0].p && !negp[0].p) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: all coefficients are zero");
+    std::vector<GA> res(width);
+    for (size_t c = 0; c < width; ++c) {
+        if (negp[c].p) {
+            GA ninv;
+            TRY(vmn_garray_inv(negp[c], ninv.out()));
+            if (!pos[c].p)
+                res[c].p = ninv.release();
+            else
+                TRY(vmn_garray_mul(pos[c], ninv, res[c].out()));
         } else {
-            GA prod;
-            TRY(vmn_garray_mul(acc, tpow, prod.out()));
-            acc.reset();
-            acc.p = prod.release();
+            res[c].p = pos[c].release();
         }
     }
-    if (negp.p) {
-        GA ninv;
-        TRY(vmn_garray_inv(negp, ninv.out()));
-        if (!pos.p) {
-            *out = ninv.release();
-            return VMN_OK;
-        }
-        return vmn_garray_mul(pos, ninv, out);
-    }
-    if (!pos.p) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: all coefficients are zero");
-    *out = pos.release();
+    for (size_t c = 0; c < width; ++c) out[c] = res[c].release();
     return VMN_OK;
+}
+int vmn_combine_decryption_factors(vmn_group* grp, const vmn_garray* const* f, const uint8_t* correct, int k, int threshold,
+                                   vmn_garray** out) {
+    return vmn_combine_decryption_factors_wide(grp, 1, f, correct, k, threshold, out);
 }
 
 int vmn_decproof_create(vmn_group* grp, int j, int k, int threshold, int ebitlen, const vmn_random_source* rs, vmn_decproof** out) {
@@ -3213,19 +3287,23 @@ int vmn_decproof_create(vmn_group* grp, int j, int k, int threshold, int ebitlen
     return VMN_OK;
 }
 void vmn_decproof_free(vmn_decproof* p) { delete p; }
+int vmn_decproof_set_instance_wide(vmn_decproof* p, size_t width, const vmn_garray* const* u, const uint8_t* y_be, const vmn_garray* const* f) {
+    NONNULL(p);
+    return p->set_instance(width, u, y_be, f);
+}
 int vmn_decproof_set_instance(vmn_decproof* p, const vmn_garray* u, const uint8_t* y_be, const vmn_garray* const* f) {
     NONNULL(p);
-    return p->set_instance(u, y_be, f);
+    return p->set_instance(1, &u, y_be, f);
 }
 int vmn_decproof_set_batch_vector(vmn_decproof* p, const uint8_t* e_be) {
     NONNULL(p);
-    if (!p->u || !e_be) return fail(VMN_ERR_ARG, "vmn_decproof_set_batch_vector: instance not set");
-    return import_batch_vector(p->G.grp, e_be, vmn_garray_size(p->u), p->ebitlen, p->e);
+    if (p->u.empty() || !e_be) return fail(VMN_ERR_ARG, "vmn_decproof_set_batch_vector: instance not set");
+    return import_batch_vector(p->G.grp, e_be, vmn_garray_size(p->u[0]), p->ebitlen, p->e);
 }
 int vmn_decproof_set_batch_vector_seed(vmn_decproof* p, const uint8_t* seed, size_t seedlen) {
     NONNULL(p);
-    if (!p->u) return fail(VMN_ERR_ARG, "vmn_decproof_set_batch_vector_seed: instance not set");
-    return vmn_rarray_from_prg(p->G.grp, seed, seedlen, vmn_garray_size(p->u), p->ebitlen, p->e.out());
+    if (p->u.empty()) return fail(VMN_ERR_ARG, "vmn_decproof_set_batch_vector_seed: instance not set");
+    return vmn_rarray_from_prg(p->G.grp, seed, seedlen, vmn_garray_size(p->u[0]), p->ebitlen, p->e.out());
 }
 int vmn_decproof_batch_input(vmn_decproof* p) {
     NONNULL(p);
@@ -3243,13 +3321,7 @@ int vmn_decproof_set_commitment(vmn_decproof* p, int l, const uint8_t* yp_be, co
     NONNULL(p);
     TRY(p->party(l));
     if (!yp_be || !Bp_be) return fail(VMN_ERR_ARG, "vmn_decproof_set_commitment: null argument");
-    Bytes a(yp_be, yp_be + p->G.eb), b(Bp_be, Bp_be + p->G.eb);
-    int ok = 1;
-    TRY(p->G.check_elements({&a, &b}, &ok));
-    if (!ok) return fail(VMN_ERR_FORMAT, "commitment holds a value that is not a group element");
-    p->yp[l] = a;
-    p->Bp[l] = b;
-    return VMN_OK;
+    return p->set_commitment(l, yp_be, Bp_be);
 }
 int vmn_decproof_set_reply(vmn_decproof* p, int l, const uint8_t* kx_be) {
     NONNULL(p);
@@ -3266,17 +3338,21 @@ int vmn_decproof_set_reply(vmn_decproof* p, int l, const uint8_t* kx_be) {
 int vmn_decproof_batch(vmn_decproof* p, int l) {
     NONNULL(p);
     TRY(p->party(l));
-    if (!p->f[l] || !p->e.p) return fail(VMN_ERR_ARG, "vmn_decproof_batch: factors of party %d or the batching vector are missing", l);
-    p->B[l].resize(p->G.eb);
-    return vmn_garray_expprod(p->f[l], p->e, p->e_bits, p->B[l].data());              // :707-709
+    if (!p->has_factors(l) || !p->e.p) return fail(VMN_ERR_ARG, "vmn_decproof_batch: factors of party %d or the batching vector are missing", l);
+    return p->expprod(p->factors(l), p->B[l]);                                        // :707-709
 }
 int vmn_decproof_verify(vmn_decproof* p, int l, const uint8_t* v_be, size_t vbytes, int* verdict) {
     NONNULL(p);
     return p->verify(l, v_be, vbytes, verdict);
 }
-int vmn_decproof_combine(vmn_decproof* p, const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* combinedf) {
+int vmn_decproof_combine_wide(vmn_decproof* p, const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* const* combinedf) {
     NONNULL(p);
     return p->combine(correct, combinedy_be, combinedf);
+}
+int vmn_decproof_combine(vmn_decproof* p, const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* combinedf) {
+    NONNULL(p);
+    if (p->width != 1) return fail(VMN_ERR_ARG, "vmn_decproof_combine: the instance has width %zu, use vmn_decproof_combine_wide", p->width);
+    return p->combine(correct, combinedy_be, &combinedf);
 }
 int vmn_decproof_batch_combined(vmn_decproof* p) {
     NONNULL(p);

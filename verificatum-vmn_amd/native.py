@@ -78,7 +78,7 @@ def plib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise VmnError(-2, f"{LIB_PATH} is missing: run __graft_entry__.build()")
         _plib = C.CDLL(LIB_PATH)
-        for name in ("vmn_msg_items", "vmn_msg_bytetree_size", "vmn_pos_width", "vmn_ccpos_width"):
+        for name in ("vmn_msg_items", "vmn_msg_bytetree_size", "vmn_pos_width", "vmn_ccpos_width", "vmn_decproof_width"):
             getattr(_plib, name).restype = C.c_size_t
         for name in ("vmn_msg_item_garray", "vmn_msg_item_rarray", "vmn_pos_permutation_commitment"):
             getattr(_plib, name).restype = C.c_void_p
@@ -681,30 +681,62 @@ def modifiedLagrangeCoefficients(q: int, correct, k: int, threshold: int, group=
     return [(-1 if neg[t] else 1) * int.from_bytes(absb.raw[t * nb:(t + 1) * nb], "big") for t in range(threshold)]
 
 
-def decryptionFactors(u, secretKey: int, q: int, k: int):
-    out = C.c_void_p()
-    _check(plib().vmn_decryption_factors(u.group._h, u._h, int_to_be(secretKey % q, u.group.exp_bytes), C.c_int(k), C.byref(out)))
-    return PGroupElementArray(u.group, out)
+# A width-omega list is a Python list (or tuple) of omega arrays, component 0 first; a single array is width 1.  What goes in
+# as a list comes back as a list.
+def _is_wide(x) -> bool:
+    return isinstance(x, (list, tuple))
 
 
 def _opt_ptr_array(arrs):
     return (C.c_void_p * len(arrs))(*[(a._h.value if a is not None else None) for a in arrs])
 
 
+def decryptionFactors(u, secretKey: int, q: int, k: int):
+    """``vmn_decryption_factors[_wide]``: u^(-x_j / c), for a list of component arrays in one call."""
+    if not _is_wide(u):
+        out = C.c_void_p()
+        _check(plib().vmn_decryption_factors(u.group._h, u._h, int_to_be(secretKey % q, u.group.exp_bytes), C.c_int(k), C.byref(out)))
+        return PGroupElementArray(u.group, out)
+    group, width = u[0].group, len(u)
+    outs = (C.c_void_p * width)()
+    _check(plib().vmn_decryption_factors_wide(group._h, C.c_size_t(width), _opt_ptr_array(u), int_to_be(secretKey % q, group.exp_bytes), C.c_int(k),
+                                              outs))
+    return [PGroupElementArray(group, C.c_void_p(h)) for h in outs]
+
+
+def _wide_factor_table(f, width: int):
+    """(k + 1) * width handles, entry l * width + c; None = the party's factors are absent."""
+    flat = []
+    for fl in f:
+        flat += [None] * width if fl is None else list(fl)
+    return _opt_ptr_array(flat)
+
+
 def combineDecryptionFactors(decryptionFactors_, correct, k: int, threshold: int, q: int):
-    group = next(a for a in decryptionFactors_ if a is not None).group
-    out = C.c_void_p()
-    _check(plib().vmn_combine_decryption_factors(group._h, _opt_ptr_array(decryptionFactors_), _flags(correct), C.c_int(k),
-                                                 C.c_int(threshold), C.byref(out)))
-    return PGroupElementArray(group, out)
+    first = next(a for a in decryptionFactors_ if a is not None)
+    if not _is_wide(first):
+        group = first.group
+        out = C.c_void_p()
+        _check(plib().vmn_combine_decryption_factors(group._h, _opt_ptr_array(decryptionFactors_), _flags(correct), C.c_int(k),
+                                                     C.c_int(threshold), C.byref(out)))
+        return PGroupElementArray(group, out)
+    group, width = first[0].group, len(first)
+    outs = (C.c_void_p * width)()
+    _check(plib().vmn_combine_decryption_factors_wide(group._h, C.c_size_t(width), _wide_factor_table(decryptionFactors_, width),
+                                                      _flags(correct), C.c_int(k), C.c_int(threshold), outs))
+    return [PGroupElementArray(group, C.c_void_p(h)) for h in outs]
 
 
 def plaintexts(v, combinedFactors):
+    if _is_wide(v):
+        return [vc.mul(fc) for vc, fc in zip(v, combinedFactors)]
     return v.mul(combinedFactors)
 
 
 class DistrElGamalSessionBasic:
-    """``vmn_decproof_*`` — ref: elgamal/DistrElGamalSessionBasic.java (one instance per party j)."""
+    """``vmn_decproof_*`` — ref: elgamal/DistrElGamalSessionBasic.java (one instance per party j).  With a list of omega
+    component arrays as ``u`` (and lists as the parties' factors) the session works over G^omega: ``commit`` returns B' as an
+    omega-tuple, ``setCommitment`` takes one, ``combine`` takes a list of combined factors."""
 
     def __init__(self, group, j: int, k: int, threshold: int, ebitlen: int, rand=None):
         self.G, self.j, self.k, self.q = group, j, k, group.q
@@ -714,6 +746,7 @@ class DistrElGamalSessionBasic:
                                           C.byref(self._rs.struct) if self._rs else None, C.byref(self._h)))
         self.k_x = {}
         self._keep = []
+        self.width = None                           # None: width 1 through the width-1 entry points
 
     def free(self):
         if self._h and self.G.alive:
@@ -733,7 +766,12 @@ class DistrElGamalSessionBasic:
         G = self.G
         ybuf = b"".join(G.enc_el(el) if el is not None else bytes(G.elem_bytes) for el in y)
         self._keep = [u, f]
-        self._call("set_instance", u._h, ybuf, _opt_ptr_array(f))
+        if _is_wide(u):
+            self.width = len(u)
+            self._call("set_instance_wide", C.c_size_t(self.width), _opt_ptr_array(u), ybuf, _wide_factor_table(f, self.width))
+        else:
+            self.width = None
+            self._call("set_instance", u._h, ybuf, _opt_ptr_array(f))
 
     def setBatchVector(self, e_ints):
         blk = host_block(e_ints) or host_block(b"".join(int_to_be(x, self.G.exp_bytes) for x in e_ints))
@@ -747,9 +785,12 @@ class DistrElGamalSessionBasic:
 
     def commit(self, x: int):
         G = self.G
-        yp, Bp = C.create_string_buffer(G.elem_bytes), C.create_string_buffer(G.elem_bytes)
+        eb, w = G.elem_bytes, self.width or 1
+        yp, Bp = C.create_string_buffer(eb), C.create_string_buffer(w * eb)
         self._call("commit", int_to_be(x % self.q, G.exp_bytes), yp, Bp)
-        return G.dec_el(yp.raw), G.dec_el(Bp.raw)
+        if self.width is None:
+            return G.dec_el(yp.raw), G.dec_el(Bp.raw)
+        return G.dec_el(yp.raw), tuple(G.dec_el(Bp.raw[c * eb:(c + 1) * eb]) for c in range(w))
 
     def reply(self, v: int) -> int:
         b = _be(v)
@@ -759,7 +800,12 @@ class DistrElGamalSessionBasic:
         return self.k_x[self.j]
 
     def setCommitment(self, l: int, yp, Bp):
-        self._call("set_commitment", C.c_int(l), self.G.enc_el(yp), self.G.enc_el(Bp))
+        if self.width is None:
+            self._call("set_commitment", C.c_int(l), self.G.enc_el(yp), self.G.enc_el(Bp))
+            return
+        if len(Bp) != self.width:
+            raise ValueError(f"B' has {len(Bp)} components, the instance has width {self.width}")
+        self._call("set_commitment", C.c_int(l), self.G.enc_el(yp), b"".join(self.G.enc_el(b) for b in Bp))
 
     def setReply(self, l: int, k_x: int):
         # a value that fits the wire width is handed over as it is: one >= q is not a field element and costs the party
@@ -779,7 +825,12 @@ class DistrElGamalSessionBasic:
 
     def combine(self, correct, combinedy, combinedf):
         self._keep.append(combinedf)
-        self._call("combine", _flags(correct), self.G.enc_el(combinedy), combinedf._h)
+        if self.width is None:
+            self._call("combine", _flags(correct), self.G.enc_el(combinedy), combinedf._h)
+            return
+        if len(combinedf) != self.width:
+            raise ValueError(f"{len(combinedf)} combined factor arrays, the instance has width {self.width}")
+        self._call("combine_wide", _flags(correct), self.G.enc_el(combinedy), _opt_ptr_array(combinedf))
 
     def batchCombined(self):
         self._call("batch_combined")

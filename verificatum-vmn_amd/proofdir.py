@@ -99,6 +99,17 @@ def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray]) -> None:
                 f.write(a.toByteTree())
 
 
+def _ciphertexts_tree(comps: Sequence[PGroupElementArray]) -> bytes:
+    """The bytes write_ciphertexts puts into a list file."""
+    half = len(comps) // 2
+    out = [fs._hdr(0, 2)]
+    for part in (comps[:half], comps[half:]):
+        if half > 1:
+            out.append(fs._hdr(0, half))
+        out += [a.toByteTree() for a in part]
+    return b"".join(out)
+
+
 def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0) -> Optional[List[PGroupElementArray]]:
     """The 2w component arrays of a ciphertext list file, parsed (range + membership) on the GPU; None when the file is not
     such a list (the verifier then fails the party, :1446-1460)."""
@@ -533,3 +544,293 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     for a in W + WP + [H, U, U_s, H_s]:
         a.free()
     return bool(verdict)
+
+
+# =============================================================================================================================
+# Verifiable threshold decryption of the last list (row A6), widths >= 1 over a modular group
+#     <nizkp>/proofs/PolynomialInExponent.bt      the coefficients g^(a_d) of the key's polynomial in the exponent
+#     <nizkp>/proofs/DecryptionFactors%02d.bt     f_l = u^(-x_l / c) of party l     elgamal/DistrElGamalSession.java:574-577
+#     <nizkp>/proofs/DecrFactCommitment%02d.bt    node(y'_l, B'_l)                  :586-589
+#     <nizkp>/proofs/DecrFactReply%02d.bt         k_x,l                             :598-601
+#     <nizkp>/proofs/CorrectIndices.bt            k + 1 booleans (entry 0 unused)   :553-555
+#     <nizkp>/Plaintexts.bt                       second components x combined factors   mixnet/MixNetElGamalSession.java:413
+# Prover side: DistrElGamalSession.decrypt (:344-545) with every party played here; verifier: the decryption branch of
+# MixNetElGamalVerifyFiatShamirSession.verify (:1545-1667, helpers :1098-1297).  An array of G^omega (the factors, the plaintexts)
+# is node(omega array trees), the array's own tree at omega = 1 -- a part of a ciphertext list file; an element of G^omega (B')
+# is node(omega leaves), a leaf at omega = 1.  Curve sessions are not covered: the directory code hashes a curve point as one
+# leaf, which is not the reference's tree of a point.
+# =============================================================================================================================
+def poly_file(nizkp):
+    return _p(nizkp, "proofs", "PolynomialInExponent.bt")
+
+
+def df_file(nizkp, l):
+    return _p(nizkp, "proofs", "DecryptionFactors%02d.bt" % l)
+
+
+def dfc_file(nizkp, l):
+    return _p(nizkp, "proofs", "DecrFactCommitment%02d.bt" % l)
+
+
+def dfr_file(nizkp, l):
+    return _p(nizkp, "proofs", "DecrFactReply%02d.bt" % l)
+
+
+def cr_file(nizkp):
+    return _p(nizkp, "proofs", "CorrectIndices.bt")
+
+
+def plaintexts_file(nizkp):
+    return _p(nizkp, "Plaintexts.bt")
+
+
+def _prg_seed_bits(params: dict) -> int:
+    """8 * prg.minNoSeedBytes(): the digest length of the PRG's hash function (PRGHeuristic)."""
+    return 8 * hashlib.new({"SHA-256": "sha256", "SHA-384": "sha384", "SHA-512": "sha512"}[params.get("prg", "SHA-256")]).digest_size
+
+
+def _wide_array_tree(comps: Sequence[PGroupElementArray]) -> bytes:
+    """toByteTree() of an array of G^omega given as its omega component arrays."""
+    body = b"".join(a.toByteTree() for a in comps)
+    return body if len(comps) == 1 else fs._hdr(0, len(comps)) + body
+
+
+def _read_wide_array(grp, path: str, width: int, n: int) -> Optional[List[PGroupElementArray]]:
+    """The omega component arrays (n elements each) of such a file; None when the file is missing or is no such array."""
+    try:
+        with open(path, "rb") as f:
+            buf = f.read()
+        pos = 0
+        if width > 1:
+            if buf[:5] != fs._hdr(0, width):
+                return None
+            pos = 5
+        size = 5 + n * (5 + grp.elem_bytes)
+        comps = []
+        for _ in range(width):
+            comps.append(grp.toElementArrayFromByteTree(buf[pos:pos + size], n))
+            pos += size
+        if pos != len(buf) or not all(c.isMember() for c in comps):
+            return None
+        return comps
+    except (OSError, ValueError, native.VmnError):
+        return None
+
+
+def _wide_element_tree(grp, els) -> bytes:
+    enc = [fs.leaf(grp.enc_el(e)) for e in els]
+    return enc[0] if len(enc) == 1 else fs._hdr(0, len(enc)) + b"".join(enc)
+
+
+def _commitment_tree(grp, yp, Bp) -> bytes:
+    return fs._hdr(0, 2) + fs.leaf(grp.enc_el(yp)) + _wide_element_tree(grp, Bp)
+
+
+def _read_commitment(grp, path: str, width: int):
+    """(y', (B'_0 .. B'_(omega-1))) of a commitment file as integers; None when the framing is wrong."""
+    eb = grp.elem_bytes
+    try:
+        with open(path, "rb") as f:
+            buf = f.read()
+    except OSError:
+        return None
+    want = 5 + (5 + eb) + ((5 + eb) if width == 1 else 5 + width * (5 + eb))
+    if len(buf) != want or buf[:5] != fs._hdr(0, 2):
+        return None
+    pos, els = 5, []
+    for i in range(1 + width):
+        if i == 1 and width > 1:
+            if buf[pos:pos + 5] != fs._hdr(0, width):
+                return None
+            pos += 5
+        if buf[pos:pos + 5] != fs._hdr(1, eb):
+            return None
+        els.append(grp.dec_el(buf[pos + 5:pos + 5 + eb]))
+        pos += 5 + eb
+    return els[0], tuple(els[1:])
+
+
+def eval_polynomial_in_exponent(grp, coeffs: Sequence[int], l: int) -> int:
+    """y_l = prod_d coeffs[d]^(l^d): the public key share of party l (PolynomialInExponent.evaluate)."""
+    acc, power = 1, 1
+    for c in coeffs:
+        acc = acc * pow(c, power, grp.p) % grp.p
+        power = power * l % grp.q
+    return acc
+
+
+def _decryption_seed(chal, grp, params, list_bytes: bytes, poly_bt: bytes, factor_trees: Sequence[bytes]) -> bytes:
+    """challenge(node(node(g, ciphertexts), node(polynomial, node(factors of parties 1..k))), 8 * minNoSeedBytes)  :434-461"""
+    bits = _prg_seed_bits(params)
+    d = chal.start(bits)
+    d.update(fs._hdr(0, 2) + fs._hdr(0, 2) + fs.leaf(grp.enc_el(grp.g)))
+    d.update(list_bytes)
+    d.update(fs._hdr(0, 2) + poly_bt + fs._hdr(0, len(factor_trees)))
+    for t in factor_trees:
+        d.update(t)
+    return chal.finish(d, bits)
+
+
+def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], poly: Sequence[int],
+                     shares: Sequence[Optional[int]], rand, k: int, threshold: int,
+                     tamper=None) -> List[PGroupElementArray]:
+    """All k parties of DistrElGamalSession.decrypt (:344-545) on the list W (2 omega component arrays, the list the last mix
+    server wrote): `poly` = the coefficients g^(a_d) of the polynomial in the exponent (threshold of them), `shares` = the
+    secret shares x_l (k + 1 entries, entry 0 unused), `rand` = the parties' random source.  Writes the six kinds of files and
+    returns the plaintexts (omega arrays).  The polynomial in the exponent is written as the array tree of its coefficients:
+    PGroup.toByteTree(PGroupElement[]) is VCR code, not part of the reference tree.  `tamper(l, factors)` (tests): replaces the
+    factors party l publishes."""
+    os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
+    NV, NE = int(params["vbitlenro"]), int(params["ebitlenro"])
+    width = len(W) // 2
+    hn = _hashname(params)
+    chal = fs.Challenger(global_prefix(params), hn)
+    U, V = list(W[:width]), list(W[width:])
+    y = pkey[-1]
+    ys = [None] + [eval_polynomial_in_exponent(grp, poly, l) for l in range(1, k + 1)]
+    poly_bt = grp.toElementArray(list(poly)).toByteTree()
+    with open(poly_file(nizkp), "wb") as f:
+        f.write(poly_bt)
+    F: List[Optional[List[PGroupElementArray]]] = [None]
+    for l in range(1, k + 1):                                                      # :384-399
+        fl = native.decryptionFactors(U, shares[l], grp.q, k)
+        if tamper is not None:
+            fl = tamper(l, fl)
+        F.append(fl)
+        with open(df_file(nizkp, l), "wb") as f:
+            f.write(_wide_array_tree(fl))
+    correct = [True] * (k + 1)
+    comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)         # :406-410
+    seed = _decryption_seed(chal, grp, params, _ciphertexts_tree(W), poly_bt, [_wide_array_tree(fl) for fl in F[1:]])
+    sessions = []
+    for l in range(1, k + 1):
+        s = native.DistrElGamalSessionBasic(grp, l, k, threshold, NE, rand=rand)
+        s.setInstance(U, ys, F)
+        s.setBatchVectorSeed(seed)
+        s.batchInput()
+        sessions.append(s)
+    commitments = [None]
+    for l in range(1, k + 1):                                                      # :469
+        yp, Bp = sessions[l - 1].commit(shares[l])
+        commitments.append((yp, Bp))
+        with open(dfc_file(nizkp, l), "wb") as f:
+            f.write(_commitment_tree(grp, yp, Bp))
+    com_bt = fs._hdr(0, k) + b"".join(_commitment_tree(grp, *c) for c in commitments[1:])
+    v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")      # :474-480
+    ver = sessions[0]
+    for l in range(1, k + 1):                                                      # :483
+        kx = sessions[l - 1].reply(v)
+        with open(dfr_file(nizkp, l), "wb") as f:
+            f.write(fs.leaf(kx.to_bytes(grp.exp_bytes, "big")))
+        if l != 1:
+            ver.setCommitment(l, *commitments[l])
+            ver.setReply(l, kx)
+    ver.combine(correct, y, comb)                                                  # :492-498
+    ver.batchCombined()
+    if not ver.verifyCombined(v):                                                  # :512-528: every party on its own
+        for l in range(1, k + 1):
+            ver.batch(l)
+            correct[l] = ver.verify(l, v)
+        for a in comb:
+            a.free()
+        comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)
+    plain = native.plaintexts(V, comb)                                             # :536-538
+    with open(plaintexts_file(nizkp), "wb") as f:
+        f.write(_wide_array_tree(plain))
+    with open(cr_file(nizkp), "wb") as f:                                          # :542
+        f.write(_booleans_tree(correct))
+    for s in sessions:
+        s.free()
+    for a in comb + [c for fl in F[1:] for c in fl]:
+        a.free()
+    return plain
+
+
+def verify_decryption(nizkp: str, grp, params: dict, pkey: Sequence, list_file: str, vectors: Optional[Dict[str, str]] = None) -> bool:
+    """The verifier's decryption branch (MixNetElGamalVerifyFiatShamirSession.java:1545-1667) for the list in `list_file`:
+    read the correct indices (at least `threshold` of them, :1163-1174) and every party's factors, combine the indicated ones,
+    derive the seed and the challenge, check the COMBINED proof, and match Plaintexts.bt with second components x combined
+    factors.  k and the threshold are params["k"], params["threshold"].  `vectors` receives Dec.s (hexadecimal), Dec.v
+    (decimal: integerChallenge.toString()) and the public key shares Dec.y_l = poly(l).  A missing file, a file that cannot be
+    parsed or too few correct indices give False."""
+    tv = vectors if vectors is not None else {}
+    NV, NE = int(params["vbitlenro"]), int(params["ebitlenro"])
+    k, threshold = int(params["k"]), int(params["threshold"])
+    width = len(pkey) // 2
+    hn = _hashname(params)
+    chal = fs.Challenger(global_prefix(params), hn)
+    try:
+        with open(list_file, "rb") as f:
+            list_bytes = f.read()
+        with open(poly_file(nizkp), "rb") as f:
+            poly_bt = f.read()
+        correct = _read_booleans(cr_file(nizkp), k + 1)
+    except OSError:
+        return False
+    if correct is None or sum(1 for l in range(1, k + 1) if correct[l]) < threshold:
+        return False
+    W = read_ciphertexts(grp, list_file, width)
+    if W is None:
+        return False
+    n = W[0].size()
+    try:
+        P = grp.toElementArrayFromByteTree(poly_bt, threshold)
+        if not P.isMember():
+            return False
+        poly = P.toInts()
+    except (ValueError, native.VmnError):
+        return False
+    ys = [None] + [eval_polynomial_in_exponent(grp, poly, l) for l in range(1, k + 1)]
+    for l in range(1, k + 1):
+        tv["Dec.y_%d" % l] = _hex(ys[l])
+    F: List[Optional[List[PGroupElementArray]]] = [None]
+    for l in range(1, k + 1):                                                      # getDecryptionFactors :1098-1114
+        fl = _read_wide_array(grp, df_file(nizkp, l), width, n)
+        if fl is None:
+            return False
+        F.append(fl)
+    U, V = W[:width], W[width:]
+    try:
+        comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)     # :1569-1574
+    except native.VmnError:
+        return False
+    seed = _decryption_seed(chal, grp, params, list_bytes, poly_bt, [_wide_array_tree(fl) for fl in F[1:]])
+    tv["Dec.s"] = seed.hex()                                                       # :1609
+    basic = native.DistrElGamalSessionBasic(grp, 1, k, threshold, NE)
+    basic.setInstance(U, ys, F)
+    basic.setBatchVectorSeed(seed)
+    basic.batchInput()
+    trees = []
+    for l in range(1, k + 1):                                                      # readCommitments :1182-1190
+        c = _read_commitment(grp, dfc_file(nizkp, l), width)
+        if c is None:
+            return False
+        try:
+            basic.setCommitment(l, *c)
+        except native.VmnError:
+            return False
+        trees.append(_commitment_tree(grp, *c))
+    v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + fs._hdr(0, k) + b"".join(trees), NV), "big")
+    tv["Dec.v"] = str(v)                                                           # :1634
+    for l in range(1, k + 1):                                                      # readReplies :1198-1206
+        try:
+            with open(dfr_file(nizkp, l), "rb") as f:
+                buf = f.read()
+        except OSError:
+            return False
+        if len(buf) != 5 + grp.exp_bytes or buf[:5] != fs._hdr(1, grp.exp_bytes):
+            return False
+        basic.setReply(l, int.from_bytes(buf[5:], "big"))
+    try:
+        basic.combine(correct, pkey[-1], comb)                                     # :1640-1644
+        basic.batchCombined()
+        verdict = basic.verifyCombined(v)
+    except native.VmnError:
+        return False
+    computed = native.plaintexts(V, comb)                                          # :1652-1663
+    plain = _read_wide_array(grp, plaintexts_file(nizkp), width, n)
+    ok = bool(verdict) and plain is not None and all(a.equals(b) for a, b in zip(plain, computed))
+    basic.free()
+    for a in W + comb + computed + (plain or []) + [c for fl in F[1:] for c in fl] + [P]:
+        a.free()
+    return ok
