@@ -18,7 +18,8 @@ Instruction stream per row (exactly 2*S v_mad_u64_u32 + 5 other VALU, no memory,
 The a*b and m*N multiply-adds of neighbouring columns are interleaved so that no instruction
 depends on its immediate predecessor.
 
-usage: gen_mont_asm.py S [S ...] > csrc/gen/mont_rows.inc
+usage: gen_mont_asm.py S [S ...] [pS qS oS hS: 2, 4, 8, 16 lanes per element] > csrc/gen/mont_rows.inc
+       gen_mont_asm.py rS [rS ...] > csrc/gen/mont29_rows.inc      (radix 2^29, see gen29)
 """
 import sys
 
@@ -29,8 +30,8 @@ FILL_FROM_BLOCK = int(__import__("os").environ.get("VMN_ROW_FILL", "0"))
 LEAD = int(__import__("os").environ.get("VMN_ROW_LEAD", "3"))   # products issued ahead of the reduction (see _row)
 
 
-def _row(S: int, first: bool, j0: int = 0, blk: int = 0):
-    """Instruction list and operand lists of one row.
+def _row(S: int, first: bool, j0: int = 0, blk: int = 0, bits: int = 28, any_row: bool = False):
+    """Instruction list and operand lists of one row (limbs of `bits` bits).
 
     blk == 0: general multiplication row, multiplier b for every column.
     blk  > 0: squaring row of the block of rows [j0, j0+blk): the row's own limb a_i multiplies the
@@ -39,6 +40,9 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0):
               earlier rows).  Every cross product a_i a_j is thus formed once (doubled) when i and j are in
               different blocks and twice (plain) inside a block; only the multiplications differ from the
               general row, the reduction half (m * N) is identical.
+    any_row:  (blk = 1) ONE text for the squaring rows 1 .. S-1: the row's index is an immediate operand and the assembler's
+              .if / .endif pick each column's product -- none (column < row), by b (column = row) or by b2.  The order of the
+              instructions does not depend on the row, so this is the text of every row with the products it skips left out.
     """
     sqr = blk > 0
     P = lambda j: f"%{j}"                 # 0..S-1      u64 "+v"
@@ -49,7 +53,8 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0):
     N = lambda j: f"%{2 * S + 3 + j}"     # N[j]        u32 "s"
     NI = f"%{3 * S + 3}"                  # n0inv       u32 "s"
     B2 = f"%{3 * S + 4}"                  # 2*b         u32 "v"  (squaring rows only)
-    MASK = "0xfffffff"                    # 2^28-1 as a 32-bit literal (saves an SGPR)
+    ROW = f"%{3 * S + 5}"                 # the row's index, "n" (any_row only)
+    MASK = hex((1 << bits) - 1)           # 2^bits-1 as a 32-bit literal (saves an SGPR)
 
     L = []
     emitted = set()
@@ -58,6 +63,13 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0):
         if j in emitted or j >= S:
             return
         emitted.add(j)
+        if any_row:
+            if j == 0:
+                return                                # rows >= 1 skip column 0
+            addend = "0" if j == S - 1 else P(j)
+            L.extend([f".if {ROW} == {j}", f"v_mad_u64_u32 {P(j)}, vcc, {A(j)}, {B}, {addend}", ".endif",
+                      f".if {ROW} < {j}", f"v_mad_u64_u32 {P(j)}, vcc, {A(j)}, {B2}, {addend}", ".endif"])
+            return
         if sqr and j < j0:
             return                                    # no product for this column in this block
         mult = B2 if (sqr and j >= j0 + blk) else B
@@ -87,7 +99,7 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0):
     L.append(f"v_mad_u64_u32 {C}, vcc, {M}, {N(0)}, {P(0)}")
     ab(1)                                            # column 1 must have its product before it moves to column 0
     L.append(f"v_mad_u64_u32 {P(0)}, vcc, {M}, {N(1)}, {P(1)}")
-    L.append(f"v_lshrrev_b64 {C}, 28, {C}")
+    L.append(f"v_lshrrev_b64 {C}, {bits}, {C}")
     lead(per)
     L.append(f"v_lshl_add_u64 {P(0)}, {P(0)}, 0, {C}")
     # steady state: a*b for column j+LEAD is issued LEAD slots before m*N consumes column j
@@ -98,11 +110,16 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0):
     return L
 
 
-def _emit(name: str, S: int, lines, first: bool, sqr: bool, tparams: str) -> str:
+def _emit(name: str, S: int, lines, first: bool, sqr: bool, tparams: str, any_row: bool = False) -> str:
     out = []
     extra = ", u32 b2" if sqr else ""
-    out.append(f"template <> __device__ __forceinline__ void {name}<{tparams}>(u64 (&P)[{S}], const u32 (&a)[{S}], u32 b{extra},\n"
-               f"        const u32 (&n)[{S}], u32 n0inv) {{")
+    if any_row:       # the primary template, for this S only: the row is a template argument and an operand of the text
+        out.append(f"template <int S, int I> __device__ __forceinline__ void {name}(u64 (&P)[S], const u32 (&a)[S], u32 b{extra},\n"
+                   f"        const u32 (&n)[S], u32 n0inv) {{")
+        out.append(f'    static_assert(S == {S} && I >= 1 && I < S, "generated for rows 1 .. {S - 1} of {S} limbs");')
+    else:
+        out.append(f"template <> __device__ __forceinline__ void {name}<{tparams}>(u64 (&P)[{S}], const u32 (&a)[{S}], u32 b{extra},\n"
+                   f"        const u32 (&n)[{S}], u32 n0inv) {{")
     out.append("    u32 m; u64 c;")
     out.append("    asm volatile(")
     for l in lines:
@@ -111,7 +128,7 @@ def _emit(name: str, S: int, lines, first: bool, sqr: bool, tparams: str) -> str
     cons = lambda j: ("=&" if first else "+") + ("{v[%d:%d]}" % (P0REG, P0REG + 1) if j == 0 else "v")
     outs = ", ".join([f'"{cons(j)}"(P[{j}])' for j in range(S)] + ['"=&v"(m)', '"=&v"(c)'])
     ins = ", ".join([f'"v"(a[{j}])' for j in range(S)] + ['"v"(b)'] + [f'"s"(n[{j}])' for j in range(S)]
-                    + ['"s"(n0inv)'] + (['"v"(b2)'] if sqr else []))
+                    + ['"s"(n0inv)'] + (['"v"(b2)'] if sqr else []) + (['"n"(I)'] if any_row else []))
     out.append(f"        : {outs}")
     out.append(f"        : {ins}")
     out.append('        : "vcc");')
@@ -129,6 +146,176 @@ def gen(S: int) -> str:
     parts.append(_emit("mont_sqr_row_asm_first", S, _row(S, True, 0, SQR_BLK), True, True, f"{S}"))
     for j0 in range(0, S, SQR_BLK):
         parts.append(_emit("mont_sqr_row_asm", S, _row(S, False, j0, SQR_BLK), False, True, f"{S}, {j0}"))
+    return "\n".join(parts)
+
+
+# ------------------------------------------------------------------------------------------------
+# Radix 2^29 (the one-lane power kernels at 2048 bits: 71 limbs instead of 74, R' = 2^(29*71) > 4N).
+# The rows are the rows above with mask and shift 29.  What 29 bits lose is the guarantee that a 64-bit
+# column cannot overflow: a product is < 2^58 (doubled in a squaring: < 2^59) and a column collects up
+# to 2*S of them.  The columns are therefore RELIEVED before the rows RELIEF29: the high dword of every
+# live column moves into the column above (2^32 = 8 * 2^29),
+#     P[j+1] = lo32(P[j+1]) + 8 * hi32(P[j])      for j = S-3 .. 0  (column S-2, the top live one, keeps its
+#     P[0]   = lo32(P[0])                          high dword; column S-1 is dead between rows)
+# which changes the spread of the value over the columns and not the value.  Descending j: no instruction
+# waits for its predecessor.  The squaring rows 1 .. S-1 are one text (_row, any_row) instead of S-1 specialisations: the
+# same instructions reach the GPU, the file is a tenth of the size.  The schedule (rows and reliefs in order) is a list that is both rendered to
+# C++ and executed on Python integers (run29): static_bound29() runs it with every limb, modulus limb and
+# quotient digit at 2^29-1 and no wrap-around, and render() refuses a schedule whose columns reach 2^64.
+# ------------------------------------------------------------------------------------------------
+BITS29 = 29
+# Reliefs sit in front of these rows (row 0 is the "first" row).  S = 71: the static bound is 2^63.954 for a product and 2^63.977
+# for a squaring; of the placements around it only (20, 40) and (21, 40) also stay below 2^64, both within 10^-8 of it.
+RELIEF29 = (21, 41)
+
+
+def relief29_ops(S: int):
+    """[(dst, src, clear)]: P[dst] = (lo32(P[dst]) if clear else P[dst]) + 8 * hi32(P[src]); last entry (0, None, True)."""
+    ops = [(j + 1, j, j + 1 <= S - 3) for j in range(S - 3, -1, -1)]
+    ops.append((0, None, True))
+    return ops
+
+
+def schedule29(S: int, sqr: bool):
+    """The steps of one product (sqr: squaring) in order: ("row", name, tparams, lines, first) or ("relief", ops)."""
+    steps = []
+    for i in range(S):
+        if i in RELIEF29:
+            steps.append(("relief", relief29_ops(S)))
+        if sqr:
+            if i == 0:
+                steps.append(("row", "mont29_sqr_row_asm_first", f"{S}", _row(S, True, 0, SQR_BLK, BITS29), True))
+            else:                                     # one text for all of them (_row, any_row); run29 hands it the row
+                steps.append(("row", "mont29_sqr_row_asm", "any", _row(S, False, i, SQR_BLK, BITS29, any_row=True), False))
+        else:
+            name = "mont29_row_asm_first" if i == 0 else "mont29_row_asm_next"
+            steps.append(("row", name, f"{S}", _row(S, i == 0, bits=BITS29), i == 0))
+    return steps
+
+
+def run29(S: int, sqr: bool, a, b, n, n0inv, worst: bool = False):
+    """Execute schedule29 on Python integers: a, b, n lists of S limbs (sqr: b is a).  Returns (columns, largest value any
+    64-bit register held before wrap-around).  worst: the quotient digit of every row is 2^29-1 and nothing wraps."""
+    M64 = (1 << 64) - 1
+    P = [0] * S
+    big = 0
+    row = -1
+    for step in schedule29(S, sqr):
+        if step[0] == "relief":
+            for dst, src, clear in step[1]:
+                v = P[dst] & 0xffffffff if clear else P[dst]
+                if src is not None:
+                    v += 8 * (P[src] >> 32)
+                big = max(big, v)
+                P[dst] = v if worst else v & M64
+            continue
+        lines = step[3]
+        row += 1
+        reg = {"m": 0, "c": 0}
+
+        def get(tok, row=row):
+            if tok == f"v{P0REG}":
+                return P[0] & 0xffffffff
+            if not tok.startswith("%"):
+                return int(tok, 0)
+            k = int(tok[1:])
+            if k < S:
+                return P[k]
+            if k == S:
+                return reg["m"]
+            if k == S + 1:
+                return reg["c"]
+            if k < 2 * S + 2:
+                return a[k - S - 2]
+            if k == 2 * S + 2:
+                return b[row]
+            if k < 3 * S + 3:
+                return n[k - 2 * S - 3]
+            if k == 3 * S + 3:
+                return n0inv
+            if k == 3 * S + 4:
+                return b[row] << 1
+            assert k == 3 * S + 5
+            return row
+
+        def put(tok, v):
+            nonlocal big
+            big = max(big, v)
+            if not worst:
+                v &= M64
+            k = int(tok[1:])
+            if k < S:
+                P[k] = v
+            elif k == S:
+                reg["m"] = v
+            else:
+                assert k == S + 1
+                reg["c"] = v
+
+        skip = False
+        for line in lines:
+            if line == ".endif":
+                skip = False
+                continue
+            op, rest = line.split(" ", 1)
+            if op == ".if":                           # ".if x == y" / ".if x < y", not nested
+                x, rel, y = rest.split()
+                skip = not (get(x) == get(y) if rel == "==" else get(x) < get(y))
+                continue
+            if skip:
+                continue
+            t = [x.strip() for x in rest.split(",")]
+            if op == "v_mad_u64_u32":
+                put(t[0], get(t[2]) * get(t[3]) + get(t[4]))
+            elif op == "v_mul_lo_u32":
+                put(t[0], (get(t[1]) * get(t[2])) & 0xffffffff)
+            elif op == "v_and_b32":
+                put(t[0], (1 << BITS29) - 1 if worst else get(t[1]) & get(t[2]))
+            elif op == "v_lshrrev_b64":
+                put(t[0], get(t[2]) >> get(t[1]))
+            elif op == "v_lshl_add_u64":
+                put(t[0], (get(t[1]) << get(t[2])) + get(t[3]))
+            else:
+                raise ValueError(line)
+    P[S - 1] = 0          # dead after the last row (the drivers clear it)
+    return P, big
+
+
+def static_bound29(S: int, sqr: bool) -> int:
+    top = [(1 << BITS29) - 1] * S
+    return run29(S, sqr, top, top, top, 0, worst=True)[1]
+
+
+def _emit_relief29(S: int) -> str:
+    o = [f"template <> __device__ __forceinline__ void mont29_relieve<{S}>(u64 (&P)[{S}]) {{"]
+    for dst, src, clear in relief29_ops(S):
+        if src is None:
+            o.append(f"    P[{dst}] &= 0xffffffffull;")
+            continue
+        clr = f" P[{dst}] &= 0xffffffffull;" if clear else ""
+        o.append(f"    {{ const u32 h = (u32)(P[{src}] >> 32);{clr} "
+                 f'asm volatile("v_mad_u64_u32 %0, vcc, %1, 8, %0" : "+v"(P[{dst}]) : "v"(h) : "vcc"); }}')
+    o.append("}")
+    o.append("")
+    return "\n".join(o)
+
+
+def gen29(S: int) -> str:
+    for sqr in (False, True):
+        bound = static_bound29(S, sqr)
+        if bound >= 1 << 64:
+            raise SystemExit(f"radix 2^29, S = {S}: reliefs before rows {RELIEF29} let a column reach 2^{bound.bit_length()} "
+                             f"in a {'squaring' if sqr else 'product'}")
+    parts = [f"// radix 2^29, S = {S} limbs: rows with mask and shift 29, reliefs in front of rows {', '.join(map(str, RELIEF29))}",
+             f"template <> struct Relief29<{S}> {{ static constexpr int A = {RELIEF29[0]}, B = {RELIEF29[1]}; }};", ""]
+    seen = set()
+    for sqr in (False, True):
+        for step in schedule29(S, sqr):
+            if step[0] != "row" or (step[1], step[2]) in seen:
+                continue
+            seen.add((step[1], step[2]))
+            parts.append(_emit(step[1], S, step[3], step[4], sqr, step[2], any_row=step[2] == "any"))
+    parts.append(_emit_relief29(S))
     return "\n".join(parts)
 
 
@@ -337,12 +524,25 @@ def render(sizes, pair_sizes=(), quad_sizes=(), octo_sizes=(), hexa_sizes=()) ->
     return "\n".join(parts) + "\n"
 
 
+def render29(sizes) -> str:
+    """csrc/gen/mont29_rows.inc: the radix-2^29 rows, a file of their own."""
+    parts = ["// GENERATED by tools/gen_mont_asm.py " + " ".join(f"r{S}" for S in sizes) + " -- do not edit.",
+             "// The rows of mont_rows.inc on limbs of 29 bits, and the relief of their columns: see the generator."]
+    for S in sizes:
+        parts.append(gen29(S))
+    return "\n".join(parts) + "\n"
+
+
 def main():
     args = sys.argv[1:]
     pair = [int(x[1:]) for x in args if x.startswith("p")]
     quad = [int(x[1:]) for x in args if x.startswith("q")]
     octo = [int(x[1:]) for x in args if x.startswith("o")]
     hexa = [int(x[1:]) for x in args if x.startswith("h")]
+    r29 = [int(x[1:]) for x in args if x.startswith("r")]
+    if r29:
+        sys.stdout.write(render29(r29))
+        return
     sizes = [int(x) for x in args if x[0].isdigit()] or [74]
     sys.stdout.write(render(sizes, pair, quad, octo, hexa))
 

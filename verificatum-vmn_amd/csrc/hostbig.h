@@ -101,6 +101,25 @@ inline Big div(const Big& a, const Big& b, Big* rem = nullptr) {
     return q;
 }
 
+// 2^k mod n (n > 1): double 1 k times
+inline Big pow2_mod(int k, const Big& n) {
+    Big r(n.size(), 0);
+    r[0] = 1;
+    for (int i = 0; i < k; ++i) dbl_mod(r, n);
+    return r;
+}
+// the first `count` limbs of `bits` bits (bits < 32) of a, one per word
+inline std::vector<uint32_t> to_limbs(const Big& a, int bits, int count) {
+    std::vector<uint32_t> l((size_t)count, 0);
+    for (int j = 0; j < count; ++j) {
+        const size_t k = (size_t)(bits * j) / 32;
+        const int sh = (bits * j) % 32;
+        const uint64_t lo = k < a.size() ? a[k] : 0, hi = k + 1 < a.size() ? a[k + 1] : 0;
+        l[j] = (uint32_t)(((hi << 32) | lo) >> sh) & ((1u << bits) - 1);
+    }
+    return l;
+}
+
 // -n^{-1} mod 2^bits for odd n0 (bits <= 32)
 inline uint32_t neg_inv_pow2(uint32_t n0, int bits) {
     uint32_t x = 1;

@@ -57,10 +57,34 @@ struct Cfg {
     static constexpr int W = BASE_LPE * BASE_LW;        // words per element in memory
     static constexpr int EPB = BLOCK / LPE_;            // elements per workgroup
     static constexpr int MINW = 2;                      // waves per SIMD the kernels are built for
+    static constexpr int BITS = LIMB_BITS;              // bits per limb
     static_assert(S_ % LPE_ == 0 && ROWS % BASE_LPE == 0, "limbs must split evenly over the lanes of an element");
     // word of limb g (< ROWS) in the row
     static __host__ __device__ constexpr int word_of(int g) { return (g / BASE_L) * BASE_LW + g % BASE_L; }
 };
+
+// The geometry the two variable-base power kernels of Cfg<74, 1> work in (k_modpow, k_modpow_phased; no other kernel): one
+// element per lane on 71 limbs of 29 bits, R' = 2^(29*71) = 2^2059 > 4N for every modulus of up to 2048 bits.  A product is
+// 2 * 71^2 multiply-adds where 74 limbs of 28 bits take 2 * 74^2, and the kernels are bound by their instruction count.
+// Only registers, the LDS column, the table rows and -- between the phases of the phased kernel -- the running value in out[]
+// hold this form, 71 (stored: 72) of the 76 words of a row; arrays stay in M28 form.  A power enters with one product by
+// c_in = R'^2 / R mod N (x R -> x R') and leaves with one by c_out = R mod N (y R' -> y R).
+struct Cfg29 {
+    static constexpr int S = 71, LPE = 1, L = 71, ROWS = 71, BASE_LPE = 1;
+    static constexpr bool WIDE = false;
+    static constexpr int BASE_L = 71, BASE_LW = stride_for_limbs(71), LW = BASE_LW;
+    static constexpr int W = Cfg<74, 1>::W;             // its rows are the rows of Cfg<74, 1>
+    static constexpr int EPB = BLOCK, MINW = 2;
+    static constexpr int BITS = 29;
+    static __host__ __device__ constexpr int word_of(int g) { return g; }
+    // the constants of a modulus in this form, rows of W words one after the other (the kernels' nmod argument)
+    static constexpr int ROW_N = 0, ROW_ONE = 1, ROW_CIN = 2, ROW_COUT = 3, CONST_ROWS = 4;
+};
+static_assert(Cfg29::LW <= Cfg29::W && 29 * Cfg29::S >= 2048 + 2, "71 limbs of 29 bits: a row of Cfg<74, 1>, R' > 4N");
+// PowGeom<C>::type: the geometry k_modpow<C> and k_modpow_phased<C> run in -- C itself, except for Cfg<74, 1>
+template <class C> struct PowGeom { using type = C; };
+template <> struct PowGeom<Cfg<74, 1>> { using type = Cfg29; };
+template <class C> constexpr bool POW29 = !__is_same(typename PowGeom<C>::type, C);
 
 // What a lane needs to know about its place: element slot in the workgroup, which half it holds, its
 // LDS column (limb i of the element's multiplier is bl[i*EPB]).
@@ -250,14 +274,14 @@ __device__ __forceinline__ void load_modulus(u32 (&n)[C::L], const u32* __restri
 // carry / borrow chains (within a lane, and across the two lanes of a pair)
 // ---------------------------------------------------------------------------------------------
 // out = limbs of sum_j v[j] 2^(28j) (+ carry-in), v[j] arbitrary 64-bit columns; returns the carry out
-template <int L>
+template <int L, int BITS = LIMB_BITS>
 __device__ __forceinline__ u64 carry_sweep(u32 (&out)[L], const u64 (&v)[L], u64 cin) {
     u64 c = cin;
 #pragma unroll
     for (int j = 0; j < L; ++j) {
         c += v[j];
-        out[j] = (u32)c & LIMB_MASK;
-        c >>= LIMB_BITS;
+        out[j] = (u32)c & ((1u << BITS) - 1);
+        c >>= BITS;
     }
     return c;
 }
@@ -266,7 +290,7 @@ __device__ __forceinline__ u64 carry_sweep(u32 (&out)[L], const u64 (&v)[L], u64
 // LPE sweeps settle the element.
 template <class C>
 __device__ __forceinline__ void normalize(u32 (&out)[C::L], const u64 (&T)[C::L], const Lane<C>& ln) {
-    u64 c = carry_sweep<C::L>(out, T, 0);
+    u64 c = carry_sweep<C::L, C::BITS>(out, T, 0);
     if constexpr (C::LPE > 1) {
 #pragma unroll
         for (int t = 1; t < C::LPE; ++t) {
@@ -276,21 +300,21 @@ __device__ __forceinline__ void normalize(u32 (&out)[C::L], const u64 (&T)[C::L]
     }
 }
 // d = x - n (limbs, borrow-in bin = 0 / -1); returns borrow-out (0 / -1)
-template <int L>
+template <int L, int BITS = LIMB_BITS>
 __device__ __forceinline__ int32_t borrow_sweep(u32 (&d)[L], const u32 (&x)[L], const u32 (&n)[L], int32_t bin) {
     int32_t borrow = bin;
 #pragma unroll
     for (int j = 0; j < L; ++j) {
-        int32_t v = (int32_t)x[j] - (int32_t)n[j] + borrow;      // limbs < 2^28: no int32 overflow
-        d[j] = (u32)v & LIMB_MASK;
-        borrow = v >> LIMB_BITS;
+        int32_t v = (int32_t)x[j] - (int32_t)n[j] + borrow;      // limbs < 2^29: no int32 overflow
+        d[j] = (u32)v & ((1u << BITS) - 1);
+        borrow = v >> BITS;
     }
     return borrow;
 }
 // element-wide x - n: d and the final borrow (0: x >= n, -1: x < n), identical on all lanes of the element
 template <class C>
 __device__ __forceinline__ int32_t sub_full(u32 (&d)[C::L], const u32 (&x)[C::L], const u32 (&n)[C::L], const Lane<C>& ln) {
-    int32_t b = borrow_sweep<C::L>(d, x, n, 0);
+    int32_t b = borrow_sweep<C::L, C::BITS>(d, x, n, 0);
     if constexpr (C::LPE > 1) {
 #pragma unroll
         for (int t = 1; t < C::LPE; ++t) {
@@ -354,7 +378,9 @@ __device__ __forceinline__ void mod_neg(u32 (&r)[C::L], const u32 (&a)[C::L], co
 template <class C>
 __device__ __forceinline__ void mont_mul(u32 (&r)[C::L], const u32 (&a)[C::L], const Lane<C>& ln, const u32 (&n)[C::L], u32 n0inv) {
     u64 T[C::L];
-    if constexpr (C::LPE == 1) {
+    if constexpr (C::BITS == 29) {
+        mont29_mul_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
+    } else if constexpr (C::LPE == 1) {
         mont_mul_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
     } else {
         mont_mul_columns_lanes<C::L, C::LPE, C::ROWS>(T, a, ln.bl, C::EPB, n, n0inv, ln.lowmask, ln.nottopmask);
@@ -365,7 +391,9 @@ __device__ __forceinline__ void mont_mul(u32 (&r)[C::L], const u32 (&a)[C::L], c
 template <class C>
 __device__ __forceinline__ void mont_sqr(u32 (&r)[C::L], const u32 (&a)[C::L], const Lane<C>& ln, const u32 (&n)[C::L], u32 n0inv) {
     u64 T[C::L];
-    if constexpr (C::LPE == 1) {
+    if constexpr (C::BITS == 29) {
+        mont29_sqr_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
+    } else if constexpr (C::LPE == 1) {
         mont_sqr_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
     } else {
         mont_sqr_columns_lanes<C::L, C::LPE, C::ROWS>(T, a, ln.bl, C::EPB, n, n0inv, ln.lowmask, ln.nottopmask);
@@ -710,6 +738,64 @@ __device__ __forceinline__ void straus_windows(u32 (&a)[C::L], const u32* __rest
     }
 }
 
+// The same value on limbs of the other width (static indices: shifts and ors in registers).  A limb of either width lies in at
+// most two limbs of the other; the value must fit the target (callers: canonical values, < 2^2048).
+template <int SD, int BD, int SS, int BS>
+__device__ __forceinline__ void repack_limbs(u32 (&d)[SD], const u32 (&s)[SS]) {
+    static_assert(BD < 32 && BS < 32 && 2 * BS >= BD + BS - 1, "two source limbs cover a target limb");
+#pragma unroll
+    for (int i = 0; i < SD; ++i) {
+        const int bit = BD * i, j = bit / BS, sh = bit % BS;
+        u32 v = j < SS ? s[j] >> sh : 0u;
+        if (j + 1 < SS) v |= s[j + 1] << (BS - sh);                 // (bits shifted out of the word lie above the mask)
+        d[i] = v & ((1u << BD) - 1);
+    }
+}
+// The first and the last step of k_modpow / k_modpow_phased where they work in Cfg29 (K; C = Cfg<74, 1>): the table of the
+// element at `base` (an M28 row of C), and the running value to its row -- finished: out of K's domain, canonical, an M28 row
+// again.  one_m is the row ROW_ONE of the modulus' constants in that form; c_in and c_out are found from it (the kernels keep
+// one_m anyway, a second pointer held across the row loops is a pair of SGPRs they do not have).
+template <class C, class K>
+__device__ __forceinline__ void pow29_table(u32 (&a)[K::L], u32* __restrict__ tb, int tsize, const u32* __restrict__ base,
+                                            const u32* __restrict__ one_m, const Lane<K>& ln, const u32 (&nn)[K::L], u32 n0inv) {
+    constexpr int W = K::W;
+    {
+        u32 x[C::L];
+        load_elem<C>(x, base, Lane<C>(ln.bl - ln.eslot));
+        repack_limbs<K::L, K::BITS, C::L, C::BITS>(a, x);
+    }
+    const_to_lds<K>(ln, one_m + (Cfg29::ROW_CIN - Cfg29::ROW_ONE) * W);
+    mont_mul<K>(a, a, ln, nn, n0inv);                              // x R -> x R'; from here on window_table's steps
+    {
+        u32 o[K::L];
+        load_modulus<K>(o, one_m, ln);
+        store_elem<K>(tb, o, ln);
+    }
+    store_elem<K>(tb + W, a, ln);
+    regs_to_lds<K>(ln, a);
+#pragma unroll 1
+    for (int k = 2; k < tsize; ++k) {
+        u32 r[K::L];
+        mont_mul<K>(r, a, ln, nn, n0inv);                          // x R' * tb[k-1]
+        store_elem<K>(tb + (size_t)k * W, r, ln);
+        regs_to_lds<K>(ln, r);
+    }
+}
+template <class C, class K>
+__device__ __forceinline__ void pow29_store(u32* __restrict__ dst, u32 (&a)[K::L], bool finished, bool live,
+                                            const u32* __restrict__ one_m, const Lane<K>& ln, const u32 (&nn)[K::L], u32 n0inv) {
+    if (finished) {
+        const_to_lds<K>(ln, one_m + (Cfg29::ROW_COUT - Cfg29::ROW_ONE) * K::W);
+        mont_mul<K>(a, a, ln, nn, n0inv);                          // y R' -> y R
+        canonicalize<K>(a, nn, ln);
+        u32 y[C::L];
+        repack_limbs<C::L, C::BITS, K::L, K::BITS>(y, a);
+        if (live) store_elem<C>(dst, y, Lane<C>(ln.bl - ln.eslot));
+    } else if (live) {
+        store_elem<K>(dst, a, ln);
+    }
+}
+
 // The queue of a phased kernel.  Every tile of k_modpow takes the same time T, so an array of r = ntiles / slots rounds finishes
 // after ceil(r) T: 10^6 elements are 7.63 rounds of the 512 workgroup slots and cost 8 -- 4.6 % of the launch is the idle tail of
 // its last round (measured: 0.632 of the roof at exactly 2 rounds, 0.603 at 7.63).  A phased kernel cuts a tile's power into
@@ -778,11 +864,12 @@ __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e, int ewords, size_t estride,
          int ebits, int wbits, size_t n, const u32* __restrict__ nmod, u32 n0inv, const u32* __restrict__ one_m,
          u32* __restrict__ tab) {
+    using K = typename PowGeom<C>::type;                 // (Cfg29: nmod, n0inv and one_m are that form's)
     constexpr int W = C::W;
     extern __shared__ u32 lds[];
-    Lane<C> ln(lds);
-    u32 nn[C::L];
-    load_modulus<C>(nn, nmod, ln);
+    Lane<K> ln(lds);
+    u32 nn[K::L];
+    load_modulus<K>(nn, nmod, ln);
     const size_t ntiles = (n + C::EPB - 1) / C::EPB;
     const int tsize = 1 << wbits;
     u32* mytab = tab + ((size_t)blockIdx.x * C::EPB + ln.eslot) * (size_t)tsize * W;
@@ -793,12 +880,17 @@ k_modpow(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict
         bool live = el < n;
         size_t ec = live ? el : n - 1;
         const u32* ep = e + ec * estride;
-        u32 a[C::L];
-        window_table<C>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
-        load_elem<C>(a, mytab + (size_t)exp_digit(ep, ewords, (nwin - 1) * wbits, wbits) * W, ln);     // the top window
-        fixed_windows<C>(a, ep, ewords, wbits, nwin - 2, 0, mytab, ln, nn, n0inv);
-        canonicalize<C>(a, nn, ln);
-        if (live) store_elem<C>(out + el * W, a, ln);
+        u32 a[K::L];
+        if constexpr (POW29<C>) pow29_table<C, K>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
+        else window_table<C>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
+        load_elem<K>(a, mytab + (size_t)exp_digit(ep, ewords, (nwin - 1) * wbits, wbits) * W, ln);     // the top window
+        fixed_windows<K>(a, ep, ewords, wbits, nwin - 2, 0, mytab, ln, nn, n0inv);
+        if constexpr (POW29<C>) {
+            pow29_store<C, K>(out + el * W, a, true, live, one_m, ln, nn, n0inv);
+        } else {
+            canonicalize<C>(a, nn, ln);
+            if (live) store_elem<C>(out + el * W, a, ln);
+        }
     }
 }
 
@@ -809,12 +901,13 @@ __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow_phased(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e, int ewords, size_t estride,
                 int ebits, int wbits, size_t n, const u32* __restrict__ nmod, u32 n0inv, const u32* __restrict__ one_m,
                 u32* __restrict__ tab, int phases, u32* __restrict__ queue, u32* __restrict__ done) {
-    constexpr int W = C::W;
+    using K = typename PowGeom<C>::type;                 // (Cfg29: nmod, n0inv and one_m are that form's; so are the table and,
+    constexpr int W = C::W;                              // between a tile's phases, its running value in out[])
     extern __shared__ u32 lds[];
     __shared__ u32 s_unit;
-    Lane<C> ln(lds);
-    u32 nn[C::L];
-    load_modulus<C>(nn, nmod, ln);
+    Lane<K> ln(lds);
+    u32 nn[K::L];
+    load_modulus<K>(nn, nmod, ln);
     const int tsize = 1 << wbits;
     const int nwin = (ebits + wbits - 1) / wbits;
     const int M = nwin - 1;                              // windows of the main loop (the top one is the first table read)
@@ -826,18 +919,23 @@ k_modpow_phased(u32* __restrict__ out, const u32* __restrict__ x, const u32* __r
         size_t ec = live ? el : n - 1;
         const u32* ep = e + ec * estride;
         u32* mytab = tab + el * (size_t)tsize * W;
-        u32 a[C::L];
+        u32 a[K::L];
         if (ph == 0) {
-            window_table<C>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
-            load_elem<C>(a, mytab + (size_t)exp_digit(ep, ewords, (nwin - 1) * wbits, wbits) * W, ln);
+            if constexpr (POW29<C>) pow29_table<C, K>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
+            else window_table<C>(a, mytab, tsize, x + ec * W, one_m, ln, nn, n0inv);
+            load_elem<K>(a, mytab + (size_t)exp_digit(ep, ewords, (nwin - 1) * wbits, wbits) * W, ln);
         } else {
-            load_elem<C>(a, out + ec * W, ln);
+            load_elem<K>(a, out + ec * W, ln);
         }
         // the windows of this phase: M - 1 - M ph / P  down to  M - M (ph + 1) / P
         const int hi = M - 1 - (int)((long)M * ph / phases), lo = M - (int)((long)M * (ph + 1) / phases);
-        fixed_windows<C>(a, ep, ewords, wbits, hi, lo, mytab, ln, nn, n0inv);
-        if (q.last()) canonicalize<C>(a, nn, ln);
-        if (live) store_elem<C>(out + el * W, a, ln);
+        fixed_windows<K>(a, ep, ewords, wbits, hi, lo, mytab, ln, nn, n0inv);
+        if constexpr (POW29<C>) {
+            pow29_store<C, K>(out + el * W, a, q.last(), live, one_m, ln, nn, n0inv);
+        } else {
+            if (q.last()) canonicalize<C>(a, nn, ln);
+            if (live) store_elem<C>(out + el * W, a, ln);
+        }
         q.hand_over();
     }
 }

@@ -64,6 +64,17 @@ template <int L, int LPE> __device__ __forceinline__ void mont_lanes_row_asm_nex
 template <int L, int LPE> __device__ __forceinline__ void mont_lanes_sqr_row_asm_first(u64 (&P)[L], const u32 (&a)[L], u32 b, u32 b2, const u32 (&n)[L], u32 n0inv, u32 lowmask, u32 nottopmask);
 template <int L, int LPE, int J0> __device__ __forceinline__ void mont_lanes_sqr_row_asm(u64 (&P)[L], const u32 (&a)[L], u32 b, u32 b2, const u32 (&n)[L], u32 n0inv, u32 lowmask, u32 nottopmask);
 #include "gen/mont_rows.inc"
+// The one-lane rows on limbs of 29 bits (the 2048-bit power kernels: 71 limbs where 28 bits need 74, R' = 2^(29*71)).  A column
+// of 29-bit products can overflow 64 bits, so the columns are relieved in front of the rows Relief29<S>::A and ::B; the
+// generator proves the bound for the schedule it emits (gen29 / static_bound29) and the drivers below follow that schedule.
+template <int S> struct Relief29;
+template <int S> __device__ __forceinline__ void mont29_row_asm_first(u64 (&P)[S], const u32 (&a)[S], u32 b, const u32 (&n)[S], u32 n0inv);
+template <int S> __device__ __forceinline__ void mont29_row_asm_next(u64 (&P)[S], const u32 (&a)[S], u32 b, const u32 (&n)[S], u32 n0inv);
+template <int S> __device__ __forceinline__ void mont29_sqr_row_asm_first(u64 (&P)[S], const u32 (&a)[S], u32 b, u32 b2, const u32 (&n)[S], u32 n0inv);
+// (rows 1 .. S-1 of a squaring: ONE text, the row is an immediate operand and assembler conditionals leave out the products it skips)
+template <int S, int I> __device__ __forceinline__ void mont29_sqr_row_asm(u64 (&P)[S], const u32 (&a)[S], u32 b, u32 b2, const u32 (&n)[S], u32 n0inv);
+template <int S> __device__ __forceinline__ void mont29_relieve(u64 (&P)[S]);
+#include "gen/mont29_rows.inc"
 
 // T (S lazy columns, value < 2N when a, b < 2N and R > 4N) = a * b / R mod N.
 // b is read as b_lds[i * bstride] (one 28-bit limb per row), n[] are the wave-uniform modulus
@@ -106,6 +117,52 @@ __device__ __forceinline__ void mont_sqr_columns(u64 (&T)[S], const u32 (&a)[S],
     u32 bn = a_lds[bstride];
     mont_sqr_row_asm_first<S>(T, a, b0, b0 << 1, n, n0inv);
     mont_sqr_blocks<S, 0>(T, a, a_lds, bstride, n, n0inv, bn);
+    T[S - 1] = 0;
+}
+
+// The same two drivers on limbs of 29 bits: T = a * b / R' resp. a * a / R' mod N, R' = 2^(29 S); rows i0 .. i1-1, then the
+// relief that precedes row i1.
+template <int S>
+__device__ __forceinline__ void mont29_mul_rows(u64 (&T)[S], const u32 (&a)[S], const u32* b_lds, int bstride, const u32 (&n)[S],
+                                                u32 n0inv, u32& bn, int i0, int i1) {
+#pragma unroll 2
+    for (int i = i0; i < i1; ++i) {
+        u32 bi = bn;
+        bn = b_lds[(i + 1 < S ? i + 1 : 0) * bstride];            // prefetch the next row's limb under this row
+        mont29_row_asm_next<S>(T, a, bi, n, n0inv);
+    }
+}
+template <int S>
+__device__ __forceinline__ void mont29_mul_columns(u64 (&T)[S], const u32 (&a)[S], const u32* b_lds, int bstride,
+                                                   const u32 (&n)[S], u32 n0inv) {
+    constexpr int A = Relief29<S>::A, B = Relief29<S>::B;
+    static_assert(0 < A && A < B && B < S, "reliefs between rows");
+    u32 b0 = b_lds[0];
+    u32 bn = b_lds[bstride];
+    mont29_row_asm_first<S>(T, a, b0, n, n0inv);
+    mont29_mul_rows<S>(T, a, b_lds, bstride, n, n0inv, bn, 1, A);
+    mont29_relieve<S>(T);
+    mont29_mul_rows<S>(T, a, b_lds, bstride, n, n0inv, bn, A, B);
+    mont29_relieve<S>(T);
+    mont29_mul_rows<S>(T, a, b_lds, bstride, n, n0inv, bn, B, S);
+    T[S - 1] = 0;
+}
+template <int S, int I>
+__device__ __forceinline__ void mont29_sqr_rows(u64 (&T)[S], const u32 (&a)[S], const u32* a_lds, int bstride,
+                                                const u32 (&n)[S], u32 n0inv, u32& bn) {
+    if constexpr (I == Relief29<S>::A || I == Relief29<S>::B) mont29_relieve<S>(T);
+    u32 bi = bn;
+    bn = a_lds[(I + 1 < S ? I + 1 : 0) * bstride];
+    mont29_sqr_row_asm<S, I>(T, a, bi, bi << 1, n, n0inv);
+    if constexpr (I + 1 < S) mont29_sqr_rows<S, I + 1>(T, a, a_lds, bstride, n, n0inv, bn);
+}
+template <int S>
+__device__ __forceinline__ void mont29_sqr_columns(u64 (&T)[S], const u32 (&a)[S], const u32* a_lds, int bstride,
+                                                   const u32 (&n)[S], u32 n0inv) {
+    u32 b0 = a_lds[0];
+    u32 bn = a_lds[bstride];
+    mont29_sqr_row_asm_first<S>(T, a, b0, b0 << 1, n, n0inv);
+    mont29_sqr_rows<S, 1>(T, a, a_lds, bstride, n, n0inv, bn);
     T[S - 1] = 0;
 }
 

@@ -807,6 +807,7 @@ static void modulus_destroy(vmn_modulus& m) {
     if (m.d_n) (void)hipFree(m.d_n);
     if (m.d_rr) (void)hipFree(m.d_rr);
     if (m.d_one) (void)hipFree(m.d_one);
+    if (m.d_pow29) (void)hipFree(m.d_pow29);
     delete m.hm;
     delete m.hm64;
     m.hm64 = nullptr;
@@ -847,6 +848,21 @@ static int modulus_init(vmn_ctx* ctx, vmn_modulus& m, const uint8_t* be, size_t 
     VMN_TRY(upload_words(ctx, &m.d_n, words_to_row_host(m.n_words, S, LPE)));
     VMN_TRY(upload_words(ctx, &m.d_one, words_to_row_host(r, S, LPE)));
     VMN_TRY(upload_words(ctx, &m.d_rr, words_to_row_host(rr, S, LPE)));
+    if (S == 74 && LPE == 1) {
+        // the power kernels' form (Cfg29): R' = 2^(29*71); in with c_in = R'^2 / R, out with c_out = R mod N
+        constexpr int S9 = Cfg29::S, B9 = Cfg29::BITS, W9 = Cfg29::W;
+        std::vector<uint32_t> rows((size_t)Cfg29::CONST_ROWS * W9, 0);
+        auto put = [&](int row, const Big& v) {
+            const std::vector<uint32_t> l = hostbig::to_limbs(v, B9, S9);
+            std::copy(l.begin(), l.end(), rows.begin() + (size_t)row * W9);
+        };
+        put(Cfg29::ROW_N, m.n_words);
+        put(Cfg29::ROW_ONE, hostbig::pow2_mod(B9 * S9, m.n_words));
+        put(Cfg29::ROW_CIN, hostbig::pow2_mod(2 * B9 * S9 - 28 * S, m.n_words));
+        put(Cfg29::ROW_COUT, r);
+        m.n0inv29 = hostbig::neg_inv_pow2(m.n_words[0] & ((1u << B9) - 1), B9);
+        VMN_TRY(upload_words(ctx, &m.d_pow29, rows));
+    }
     m.hm = new hostbig::Mont(m.n_words);
     {
         std::vector<uint8_t> nbe((size_t)NW * 4);
@@ -1707,13 +1723,26 @@ static int modpow_words(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, 
     PhasePlan pl(ctx, m, n);
     VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)1 << wbits)));
     note_work(ctx, m, (double)n * (nwin - 1 + (1 << wbits) - 2), (double)n * (nwin - 1) * wbits);
+    const bool pow29 = m.S == 74 && m.LPE == 1;            // POW29<Cfg<74, 1>>: the kernels work on 71 limbs of 29 bits
+    if (pow29 && ctx->timing) {
+        // the multiply-adds of those rows: the same products and squarings, the two products that change the domain, and in
+        // each of them two reliefs of S - 2 multiply-adds
+        const double S9 = Cfg29::S, relief = 2 * (S9 - 2);
+        ctx->next_mads = (double)n * ((nwin - 1 + (1 << wbits) - 2 + 2) * (2 * S9 * S9 + relief) +
+                                      (double)(nwin - 1) * wbits * (S9 * S9 + S9 * (S9 + SQR_BLK) / 2 + relief));
+    }
     VMN_TRY(pl.split(ctx, m, nwin - 1, (size_t)1 << wbits));
+    // (those kernels take the modulus, -1/N and 1 in their own form)
+    static_assert(POW29<Cfg<74, 1>>, "modpow_words passes the 29-bit constants to the kernels of Cfg<74, 1>");
+    const uint32_t* d_n = pow29 ? m.d_pow29 + (size_t)Cfg29::ROW_N * Cfg29::W : m.d_n;
+    const uint32_t* d_one = pow29 ? m.d_pow29 + (size_t)Cfg29::ROW_ONE * Cfg29::W : m.d_one;
+    const uint32_t n0inv = pow29 ? m.n0inv29 : m.n0inv;
     return with_cfg(m, [&]<class C, class W>(C, W) {
         if (pl.phases > 1)
             return launch(ctx, "modpow", k_modpow_phased<C>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, n,
-                          m.d_n, m.n0inv, m.d_one, pl.table(), pl.phases, pl.queue(), pl.done());
-        return launch(ctx, "modpow", k_modpow<C>, pl.grid, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, n, m.d_n, m.n0inv,
-                      m.d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
+                          d_n, n0inv, d_one, pl.table(), pl.phases, pl.queue(), pl.done());
+        return launch(ctx, "modpow", k_modpow<C>, pl.grid, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, n, d_n, n0inv,
+                      d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
     });
 }
 
