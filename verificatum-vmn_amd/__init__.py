@@ -323,6 +323,7 @@ class ModPGroup:
         ok = C.c_int(1)
         _check(lib().vmn_rarray_from_be(self._h, blk[0], C.c_size_t(n), C.byref(h), C.byref(ok)))
         arr = PRingElementArray(self, h)
+        arr.all_in_range = bool(ok.value)
         if checked and not ok.value:
             arr.free()
             raise ValueError("ArithmFormatException: ring element out of range")
@@ -711,6 +712,7 @@ class PRingElementArray(_ArrayBase):
     """Device-resident ``PRingElementArray`` / ``PFieldElementArray`` over Z_q."""
 
     _free_fn = "vmn_rarray_free"
+    all_in_range = True
 
     def size(self) -> int:
         return lib().vmn_rarray_size(self._h)
