@@ -462,7 +462,8 @@ def test_worst_case_column_magnitudes(bits, vmn, gpu_ctx):
 def test_subgroup_membership_by_jacobi_symbol(bits, groups):
     """K10: x is in the order-q subgroup of a safe-prime group iff (x / p) = 1.  The Jacobi kernels (one element per
     lane up to 2048 bits, the element's own two / four lanes at 3072 / 4096 bits) against Python on residues, non-residues
-    and special values, one element at a time and inside large arrays."""
+    and special values, one element at a time and inside large arrays.  The special values reach the kernel in Montgomery
+    form, as rows without zero limbs; tests/test_gpu_jacobi_edges.py holds the limb-level edges."""
     G, grp, _ = groups[bits]
     p, q, g = grp["p"], grp["q"], grp["g"]
     rnd = pyref.stream_ints(b"jacobi%d" % bits, 40, p)

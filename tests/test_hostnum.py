@@ -6,7 +6,9 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from jacobi_edges import jacobi as _jacobi
 from oracle import pyref
+from ring_edges import seeded_odd
 
 
 @pytest.fixture(scope="module")
@@ -39,19 +41,27 @@ def test_order_of_p256_and_edge_values(harness):
         assert got == [a * b % n, pow(a, e, n), pow(a, -1, n), e % n, (a + b) % n, (-a) % n]
 
 
-def _jacobi(a, n):
-    a %= n
-    t = 1
-    while a:
-        while a % 2 == 0:
-            a //= 2
-            if n % 8 in (3, 5):
-                t = -t
-        a, n = n, a
-        if a % 4 == 3 and n % 4 == 3:
-            t = -t
-        a %= n
-    return t if n == 1 else 0
+def jac(harness, n, vals):
+    out = subprocess.run([harness, "jac", "%x" % n] + ["%x" % v for v in vals], check=True, capture_output=True, text=True).stdout.split()
+    return [int(x) for x in out]
+
+
+def limb64_edges(n, tag):
+    """What num64::jacobi's whole-limb shortcut and its shift meet on 64-bit limbs, as plain values below n: 2^(64 j) and
+    n - 2^(64 j) for every limb, odd values under 1 to 63 (and 64 j + 63) zero bits, values next to n and to its factors."""
+    nl = (n.bit_length() + 63) // 64
+    rnd = iter(pyref.stream_ints(b"hostnum-jac/" + tag, 2 * nl + 80, n))
+    vals = [0, 1, 2, 3, 4, n - 1, n - 2, n - 4, (n - 1) // 2, (n + 1) // 2]
+    for j in range(1, nl):
+        b = 1 << (64 * j)
+        vals += [b, 3 * b, b - 1, b + 1, n - b, ((next(rnd) >> (64 * j)) | 1) << (64 * j), b << 63]
+    for k in range(1, 64):
+        vals += [1 << k, n - (1 << k), ((next(rnd) >> k) | 1) << k]
+    for f in (3, 5, 7, (1 << 32) - 1, (1 << 64) - 1):
+        if n % f == 0:
+            vals += [f, f << 64, n // f]
+    vals += [next(rnd) for _ in range(16)]
+    return sorted({v for v in vals if 0 <= v < n})
 
 
 @pytest.mark.parametrize("bits", [2048, 3072])
@@ -68,6 +78,25 @@ def test_jacobi_symbol_is_subgroup_membership_for_safe_primes(bits, harness):
     vals = list(range(0, 60))
     out = subprocess.run([harness, "jac", "%x" % n] + ["%x" % v for v in vals], check=True, capture_output=True, text=True).stdout.split()
     assert [int(x) for x in out] == [_jacobi(v, n) for v in vals]
+    if bits != 2048:
+        return
+    # the 64-bit analogue of tests/jacobi_edges.py: whole zero limbs, ctz up to 63, moduli that are 3 and 5 mod 8 (p is
+    # 7 mod 8) and composite ones -- 2^256 - 1 has the factors 3, 5, 2^32 - 1 and 2^64 - 1: symbol 0
+    moduli = [("p", p)]
+    for size in (2048, 256):
+        moduli += [("rnd3/%d" % size, seeded_odd(b"hostnum-jac/N3/%d" % size, size) & ~7 | 3),
+                   ("rnd5/%d" % size, seeded_odd(b"hostnum-jac/N5/%d" % size, size) & ~7 | 5)]
+    moduli.append(("ones/256", (1 << 256) - 1))
+    for tag, n in moduli:
+        vals = limb64_edges(n, tag.encode())
+        nl = (n.bit_length() + 63) // 64
+        assert {1 << (64 * j) for j in range(1, nl)} | {n - (1 << (64 * j)) for j in range(1, nl)} | {1 << 63, n - (1 << 63)} <= set(vals)
+        want = [_jacobi(v, n) for v in vals]
+        assert jac(harness, n, vals) == want, tag
+        assert {-1, 1} <= set(want) and vals[0] == 0 and want[0] == 0, tag
+        assert tag != "ones/256" or want[1:].count(0) >= 12
+        assert tag != "p" or 0 not in want[1:]
+    assert [n % 8 for _, n in moduli] == [7, 3, 5, 3, 5, 7]
 
 
 @pytest.mark.parametrize("name", ["P-256", "P-384"])

@@ -1316,8 +1316,8 @@ k_bucket_level(u32* __restrict__ out, size_t out_stride, LevelInputs ins, unsign
 // ---------------------------------------------------------------------------------------------
 // K10: membership in the order-q subgroup of a safe-prime group (p = 2q + 1): x is a member iff it is a quadratic
 // residue iff the Jacobi symbol (x / p) = 1.  Binary Jacobi algorithm on 28-bit limbs, one element per lane (moduli
-// up to 3072 bits), no multiplications: a few limb passes per step, at most 2 * bits(p) steps -- about a tenth of
-// the instructions of the x^q = 1 test.  The rows are in Montgomery form x R mod p; (R / p) = 1 because R is an even
+// up to 2048 bits; above that the element's own lanes, k_jacobi_member_lanes), no multiplications: a few limb passes per
+// step, at most 2 * bits(p) steps -- about a tenth of the instructions of the x^q = 1 test.  The rows are in Montgomery form x R mod p; (R / p) = 1 because R is an even
 // power of two, so the symbol of the row is the symbol of x.  flags[0] |= 1 when some element is not a member
 // (zero included).  ref: the membership test VCR makes when an array is read (pGroup.toElementArray), e.g.
 // P/hvzk/PoSBasicTW.java:787-792.
