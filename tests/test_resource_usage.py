@@ -61,3 +61,8 @@ def test_p256_point_kernels_do_not_spill(tmp_path):
     # (found by this test in round 4; DESIGN.md §9 lists it).  The bound keeps it from growing unnoticed.
     for name, r in {k: v for k, v in rep.items() if "k_ec_mulvarILi10E" in k}.items():
         assert r["scratch"] <= 240 and r["occupancy"] >= 2, (name, r)
+    # the import reads the framed coordinates where they lie: no per-thread byte buffer (it was 80 B of scratch per lane)
+    hits = {k: v for k, v in rep.items() if "k_ec_importILi10ELi8E" in k}
+    assert hits
+    for name, r in hits.items():
+        assert r["scratch"] == 0 and r["occupancy"] >= 8, (name, r)

@@ -21,3 +21,7 @@ def test_general_a_point_kernels_over_10_limbs_do_not_spill(tmp_path):
     assert hits
     for name, r in hits.items():
         assert r["scratch"] <= 240 and r["occupancy"] >= 2, (name, r)
+    hits = {k: v for k, v in rep.items() if "k_ec_importILi10ELi8ELi1E" in k}      # (no per-thread byte buffer: see test_resource_usage.py)
+    assert hits
+    for name, r in hits.items():
+        assert r["scratch"] == 0, (name, r)

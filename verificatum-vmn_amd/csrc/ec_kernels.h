@@ -882,31 +882,25 @@ template <int S, int NW, int KIND = EC_NIST>
 __global__ void __launch_bounds__(BLOCK) k_ec_import(u32* __restrict__ out, const uint8_t* __restrict__ be, size_t nbytes,
                                                      size_t stride, int framed, size_t n, ECDev E, u32* __restrict__ flags) {
     // framed: every point is the byte tree node(leaf(x), leaf(y)) = 00 00000002 | 01 len x | 01 len y (the form VCR gives a
-    // curve point; [NOT-IN-REF]: restated from the verifier specification); the coordinates are moved together first
+    // curve point; [NOT-IN-REF]: restated from the verifier specification); the coordinates are read where they lie, so every
+    // width vmn_group_set_wire_bytes takes comes back through the byte tree it was written to
     using C1 = Cfg<S, 1>;
     constexpr int ROW = ECfg<S>::ROW;
     size_t el = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (el >= n) return;
     const uint8_t* rec = be + el * stride;
-    uint8_t packed[2 * (4 * NW + 4)];
-    const uint8_t* src = rec;
+    const uint8_t* srcx = rec;
+    const uint8_t* srcy = rec + nbytes;
     if (framed) {
         auto hdr_ok = [&](const uint8_t* h, uint8_t tag, size_t len) {
             return h[0] == tag && h[1] == (uint8_t)(len >> 24) && h[2] == (uint8_t)(len >> 16) && h[3] == (uint8_t)(len >> 8) && h[4] == (uint8_t)len;
         };
         if (!(hdr_ok(rec, 0, 2) && hdr_ok(rec + 5, 1, nbytes) && hdr_ok(rec + 10 + nbytes, 1, nbytes))) atomicOr(flags, 4u);
-        if (nbytes <= sizeof(packed) / 2) {
-            for (size_t i = 0; i < nbytes; ++i) {
-                packed[i] = rec[10 + i];
-                packed[nbytes + i] = rec[15 + nbytes + i];
-            }
-            src = packed;
-        } else {
-            atomicOr(flags, 4u);
-        }
+        srcx = rec + 10;
+        srcy = rec + 15 + nbytes;
     }
     u32 allff = 0xff;
-    for (size_t i = 0; i < 2 * nbytes; ++i) allff &= src[i];
+    for (size_t i = 0; i < nbytes; ++i) allff &= srcx[i] & srcy[i];
     Pt<S> P;
     bool bad = false;
     if (allff == 0xff) {
@@ -916,10 +910,10 @@ __global__ void __launch_bounds__(BLOCK) k_ec_import(u32* __restrict__ out, cons
         u32 x[S], y[S], pp[S], d[S];
 #pragma unroll
         for (int j = 0; j < S; ++j) pp[j] = E.p[j];
-        limbs_from_be<C1, NW>(x, src, (long)nbytes, ln);
-        limbs_from_be<C1, NW>(y, src + nbytes, (long)nbytes, ln);
+        limbs_from_be<C1, NW>(x, srcx, (long)nbytes, ln);
+        limbs_from_be<C1, NW>(y, srcy, (long)nbytes, ln);
         u32 extra = 0;
-        for (long o = (long)nbytes - 4L * NW - 1; o >= 0; --o) extra |= src[o] | src[nbytes + o];
+        for (long o = (long)nbytes - 4L * NW - 1; o >= 0; --o) extra |= srcx[o] | srcy[o];
         bad = extra != 0 || borrow_sweep<S>(d, x, pp, 0) == 0 || borrow_sweep<S>(d, y, pp, 0) == 0;
         u32 rrc[S];
 #pragma unroll
