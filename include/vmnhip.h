@@ -192,6 +192,14 @@ int vmn_garray_exp_scalar(const vmn_garray* x, const uint8_t* e_be, size_t ebyte
  * appear twice.  k = 0, arrays of two groups or of different sizes: VMN_ERR_ARG.  On failure no output stays allocated
  * (outs[c] = NULL). */
 int vmn_garray_exp_scalar_multi(const vmn_garray* const* xs, size_t k, const uint8_t* e_be, size_t ebytes, vmn_garray** outs);
+/* The same with an exponent per ARRAY: outs[c][i] = xs[c][i]^(e_c), es_be holds k rows of ebytes bytes, row c the exponent of
+ * array c; bit for bit what vmn_garray_exp_scalar gives for (xs[c], e_c).  Under a public key of width kappa the component
+ * arrays of a party's decryption factors take kappa different secrets (P/elgamal/DistrElGamalSession.java:365-389 over
+ * (G^kappa)^omega).  Over a modular group with every exponent above 32 bits up to eight arrays share one launch, each under a
+ * schedule of its own; VMN_EXP_MULTI_FUSED=0 (read per call) runs them one after the other.  Over a curve, or with any exponent
+ * of at most 32 bits in the call, the arrays run one after the other, each as vmn_garray_exp_scalar runs it.  Arguments and
+ * failures as for vmn_garray_exp_scalar_multi. */
+int vmn_garray_exp_scalars_multi(const vmn_garray* const* xs, size_t k, const uint8_t* es_be, size_t ebytes, vmn_garray** outs);
 /* K2  g.exp(E): out[i] = base^E[i] for one fixed base.  ref: P/mixnet/ShufflerElGamalSession.java:407,
  * 658; P/hvzk/PoSBasicTW.java:447, 606, 608, 644, 646, 1030; P/mixnet/PermutationCommitment.java:200. */
 int vmn_group_exp_fixed(vmn_group* grp, const uint8_t* base_be, const vmn_rarray* e, vmn_garray** out);

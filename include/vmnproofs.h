@@ -320,6 +320,29 @@ int vmn_decproof_set_instance_wide(vmn_decproof* p, size_t width, const vmn_garr
                                    const vmn_garray* const* f);
 size_t vmn_decproof_width(const vmn_decproof* p);
 int vmn_decproof_combine_wide(vmn_decproof* p, const uint8_t* correct, const uint8_t* combinedy_be, const vmn_garray* const* combinedf);
+/* Key width kappa (ProtocolElGamal.getKeyPGroup: the key group is G^kappa, a plaintext of width omega lives in (G^kappa)^omega).
+ * W = kappa * omega component arrays, component c = l * kappa + j the key j of plaintext component l; the secret key, the
+ * randomizer and the reply are kappa rows of exp_bytes, a public key and y' kappa rows of elem_bytes, key 0 first, and an
+ * exponent of Z_q^kappa acts on component c through its row c mod kappa.  The challenge stays one field element.
+ * vmn_decryption_factors_keyed: f_c = u_c^(-x_{c mod kappa} / c_k), u and f_out W arrays, secrets_be kappa rows -- ONE
+ * vmn_garray_exp_scalars_multi over the W arrays (kappa = 1: the vmn_garray_exp_scalar_multi of vmn_decryption_factors_wide).
+ * Combining factors and plaintexts needs nothing new: vmn_combine_decryption_factors_wide and vmn_garray_mul at width W.
+ * After vmn_decproof_set_instance_keyed (y_be: (k + 1) * kappa rows, row l * kappa + j the key j of party l; f: (k + 1) * W
+ * arrays, entry l * W + c) the entry points above read and write kappa rows where they handle one at key width 1:
+ *   commit          x_be kappa rows, yp_out kappa rows (y'_j = g^(r_j)), Bp_out W rows (B'_c = A_c^(r_{c mod kappa})); the kappa
+ *                   randomizers are ONE ring_elements(user, kappa, &rows) call, row j = r_j, a row >= q: VMN_ERR_FORMAT
+ *   reply           kx_out kappa rows, k_{x,j} = -x_j c_k^-1 v + r_j
+ *   set_commitment  yp_be kappa rows, Bp_be W rows; any row that is no group element: VMN_ERR_FORMAT, nothing is stored
+ *   set_reply       kx_be kappa rows; ANY row >= q: the zero of Z_q^kappa is stored and the party's verdict is false
+ *   combine_wide    combinedy_be kappa rows, combinedf W arrays
+ *   verify(l), verify_combined   the y equation under every key and the B equation in every component, with k_{x, c mod kappa}
+ * vmn_decproof_width returns W; batch_input, batch(l) and batch_combined stay one vmn_garray_expprod_multi over the W
+ * components.  set_instance and set_instance_wide are set_instance_keyed with kappa = 1. */
+int vmn_decryption_factors_keyed(vmn_group* grp, size_t keywidth, size_t width, const vmn_garray* const* u, const uint8_t* secrets_be, int k,
+                                 vmn_garray** f_out);
+int vmn_decproof_set_instance_keyed(vmn_decproof* p, size_t keywidth, size_t width, const vmn_garray* const* u, const uint8_t* y_be,
+                                    const vmn_garray* const* f);
+size_t vmn_decproof_keywidth(const vmn_decproof* p);
 
 /* ---- interactive derivation of independent generators -----------------------------------
  * distr/IndependentGeneratorsBasicI.java: setInstance :166-175, setBatchVector :186-193, commit :201-208,

@@ -175,6 +175,8 @@ def need_expr(name, ptype, pname, plist):
     if k == "handles_out":
         if name.endswith("_wide") and pname in ("f_out", "out"):
             return "(size_t)width"
+        if name.endswith("_keyed") and pname == "f_out":
+            return "(size_t)keywidth * (size_t)width"
         if pname == "outs":
             return "(size_t)k"
         return {"wp_out": "2 * (size_t)width", "factors_out": "2 * (size_t)width", "s_out": "(size_t)width"}.get(pname, "1")
@@ -187,8 +189,12 @@ def need_expr(name, ptype, pname, plist):
             return "(size_t)width"
         if name.endswith("_wide") and pname in ("u", "combinedf"):
             return "(size_t)width" if "width" in names else f"vmn_decproof_width({pobj})"
+        if name.endswith("_keyed") and pname == "u":
+            return "(size_t)keywidth * (size_t)width"
         if pname == "f":
             parties = "(size_t)k + 1" if "k" in names else f"(size_t)vmn_decproof_parties({pobj}) + 1"
+            if name.endswith("_keyed"):
+                return f"({parties}) * (size_t)keywidth * (size_t)width"
             return f"({parties}) * (size_t)width" if name.endswith("_wide") else parties
         if pname == "h" and name == "vmn_igen_set_instance":
             return f"(size_t)vmn_igen_parties({pobj}) + 1"
@@ -232,6 +238,17 @@ def need_expr(name, ptype, pname, plist):
             return f"(size_t){explicit[pname]}"
         if pname == "exps_be":
             return f"{asize} * (size_t)ebytes"
+        if pname == "es_be":                                                  # a row per array
+            return "(size_t)k * (size_t)ebytes"
+        if pname == "secrets_be":
+            return f"(size_t)keywidth * {XB}"
+        # after a keyed instance the key, the randomizer's image and the reply are keywidth rows
+        if proof == "vmn_decproof" and pname in ("x_be", "kx_out", "kx_be"):
+            return f"vmn_decproof_keywidth({pobj}) * {XB}"
+        if proof == "vmn_decproof" and pname in ("yp_out", "yp_be", "combinedy_be"):
+            return f"vmn_decproof_keywidth({pobj}) * {EB}"
+        if pname == "y_be" and name == "vmn_decproof_set_instance_keyed":
+            return f"((size_t)vmn_decproof_parties({pobj}) + 1) * (size_t)keywidth * {EB}"
         if name == "vmn_prg_bytes" and pname == "out":
             return "(size_t)nbytes"
         if name.startswith("vmn_random_oracle") and pname == "out":

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """What one launch for the omega component arrays of a party's decryption factors is worth: vmn_garray_exp_scalar_multi over a
 2048-bit group with a full-length exponent, omega = 3, fused (the default) against VMN_EXP_MULTI_FUSED=0 (one launch per
-array), same build, same process, the two arms alternating.
+array), same build, same process, the two arms alternating.  With --keywidth kappa > 1 the factors are those under a key of
+width kappa: kappa * omega arrays, array c under exponent c mod kappa of kappa full-length exponents
+(vmn_garray_exp_scalars_multi: one launch per eight arrays, each array under its own schedule).
 
-    python3 tools/wide_factor_rate.py [--sizes 10000,100000,1000000] [--passes 7] [--out profiles/wide_factor_rates.txt]
+    python3 tools/wide_factor_rate.py [--keywidth 2] [--sizes 10000,100000,1000000] [--passes 7] [--out profiles/wide_factor_rates.txt]
 
 A pass times one call of each arm: host clock around the call and a device synchronise, results freed outside the window.
 Two warm-up passes per size (code objects, scratch and pool blocks of the size exist afterwards).  Reported per size and arm:
@@ -31,7 +33,7 @@ def timed(ctx, vmn, arrays, e, fused):
         os.environ["VMN_EXP_MULTI_FUSED"] = "0"
     ctx.synchronize()
     t0 = time.perf_counter()
-    out = vmn.PGroupElementArray.expMulti(arrays, e)
+    out = vmn.PGroupElementArray.expMultiEach(arrays, e) if isinstance(e, list) else vmn.PGroupElementArray.expMulti(arrays, e)
     ctx.synchronize()
     dt = time.perf_counter() - t0
     os.environ.pop("VMN_EXP_MULTI_FUSED", None)
@@ -42,18 +44,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="10000,100000,1000000")
     ap.add_argument("--passes", type=int, default=7)
+    ap.add_argument("--keywidth", type=int, default=1)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     vmn = entry.load_package()
     ctx = vmn.Context(0)
     p, q, g = pyref.modp_group(2048)
     G = vmn.ModPGroup(ctx, p, q, g)
-    e = pyref.stream_ints(b"wide_factor_rate/e", 1, q)[0] | (1 << (q.bit_length() - 2))
-    lines = [f"# vmn_garray_exp_scalar_multi, 2048-bit group, {e.bit_length()}-bit exponent, omega = {WIDTH}; {args.passes} alternating passes after 2 warm-up passes",
-             "# times in ms per call (all omega arrays); spread = (max - min) / median of the arm",
+    kw = max(1, args.keywidth)
+    narrays = kw * WIDTH
+    es = [v | (1 << (q.bit_length() - 2)) for v in pyref.stream_ints(b"wide_factor_rate/e", kw, q)]
+    e = es[0] if kw == 1 else [es[c % kw] for c in range(narrays)]
+    what = "vmn_garray_exp_scalar_multi" if kw == 1 else f"vmn_garray_exp_scalars_multi, key width {kw},"
+    lines = [f"# {what} 2048-bit group, {es[0].bit_length()}-bit exponent{'s' if kw > 1 else ''}, omega = {WIDTH}; {args.passes} alternating passes after 2 warm-up passes",
+             f"# times in ms per call (all {narrays} arrays); spread = (max - min) / median of the arm",
              f"# {'N':>8} {'arm':>9} {'median':>9} {'min':>9} {'max':>9} {'spread':>7} {'modexp/s':>10}  fused/separate"]
     for n in [int(s) for s in args.sizes.split(",")]:
-        arrays = [G.exp(g, G.ringArrayFromPRG(hashlib.sha256(b"wide_factor_rate/%d/%d" % (n, c)).digest(), n, q.bit_length() - 1)) for c in range(WIDTH)]
+        arrays = [G.exp(g, G.ringArrayFromPRG(hashlib.sha256(b"wide_factor_rate/%d/%d" % (n, c)).digest(), n, q.bit_length() - 1)) for c in range(narrays)]
         first = {}
         for fused in (True, False):                                   # warm-up, and: the two arms give the same arrays
             for _ in range(2):
@@ -74,7 +81,7 @@ def main():
             ts = t[fused]
             ratio = f"  {med[True] / med[False]:.3f}" if fused else ""
             lines.append(f"  {n:>8} {'fused' if fused else 'separate':>9} {med[fused]:9.3f} {min(ts):9.3f} {max(ts):9.3f} {(max(ts) - min(ts)) / med[fused]:7.3f} "
-                         f"{WIDTH * n / med[fused] * 1e3:10.4g}{ratio}")
+                         f"{narrays * n / med[fused] * 1e3:10.4g}{ratio}")
         for a in arrays:
             a.free()
     text = "\n".join(lines) + "\n"

@@ -586,6 +586,21 @@ class PGroupElementArray(_ArrayBase):
         _check(lib().vmn_garray_exp_scalar_multi(hs, C.c_size_t(k), int_to_be(e, nb), C.c_size_t(nb), outs))
         return [PGroupElementArray(arrays[0].group, C.c_void_p(h)) for h in outs]
 
+    @staticmethod
+    def expMultiEach(arrays, exps) -> list:
+        """``vmn_garray_exp_scalars_multi``: ``[a.exp(e) for a, e in zip(arrays, exps)]`` for arrays of one group and one size,
+        each under an exponent of its own (the components of a list under a key of width kappa); over a modular group with
+        every exponent above 32 bits the arrays of a call share one launch."""
+        k = len(arrays)
+        if k == 0 or len(exps) != k:
+            raise ValueError("expMultiEach needs at least one array and one exponent per array")
+        hs = (C.c_void_p * k)(*[a._h for a in arrays])
+        outs = (C.c_void_p * k)()
+        exps = [int(e) for e in exps]
+        nb = max(1, max((e.bit_length() + 7) // 8 for e in exps))
+        _check(lib().vmn_garray_exp_scalars_multi(hs, C.c_size_t(k), b"".join(int_to_be(e, nb) for e in exps), C.c_size_t(nb), outs))
+        return [PGroupElementArray(arrays[0].group, C.c_void_p(h)) for h in outs]
+
     def expInts(self, exps: Sequence[int], ebits: int) -> "PGroupElementArray":
         """Exponents that are plain integers of ``ebits`` bits (not reduced mod q)."""
         nb = (ebits + 7) // 8

@@ -1,6 +1,6 @@
 // modp_shared_exp.h — variants of K1 beside k_modpow: ONE exponent for the whole array (out[i] = x[i]^e, sliding window), for one
-// array or for several arrays of one size in one launch, and two independent exponentiations of small arrays in one launch
-// (k_modpow_jobs, at the end).
+// array or for several arrays of one size in one launch (all under one exponent, or each array under its own), and two
+// independent exponentiations of small arrays in one launch (k_modpow_jobs, at the end).
 //
 // The reference raises whole arrays to a single exponent in the decryption half of the mix-net -- the decryption factors
 // f = u^(-x_j / c), a full-length secret exponent per party (elgamal/DistrElGamalSession.java:365-385) -- and in the
@@ -43,6 +43,7 @@ __device__ __forceinline__ void slide_steps(u32 (&a)[C::L], const SlideStep* __r
 // of the same body (OneArray: no table, no division).
 constexpr int SHARED_ARRAYS = 8;
 struct SharedArrays {
+    static constexpr bool OWN_SCHEDULES = false;
     const u32* x[SHARED_ARRAYS];
     u32* out[SHARED_ARRAYS];
     // the array of global tile T, and T's index among that array's tiles (the host keeps k * ntiles below 2^32)
@@ -50,14 +51,39 @@ struct SharedArrays {
     __device__ __forceinline__ size_t tile_of(size_t T, u32 a, u32 ntiles) const { return (u32)T - a * ntiles; }
     __device__ __forceinline__ const u32* x_of(u32 a) const { return x[a]; }
     __device__ __forceinline__ u32* out_of(u32 a) const { return out[a]; }
+    // (one schedule for the launch)
+    __device__ __forceinline__ const SlideStep* steps_of(u32, const SlideStep* steps) const { return steps; }
+    __device__ __forceinline__ int nsteps_of(u32, int nsteps) const { return nsteps; }
 };
 struct OneArray {
+    static constexpr bool OWN_SCHEDULES = false;
     const u32* x;
     u32* out;
     __device__ __forceinline__ u32 array_of(size_t, u32) const { return 0; }
     __device__ __forceinline__ size_t tile_of(size_t T, u32, u32) const { return T; }
     __device__ __forceinline__ const u32* x_of(u32) const { return x; }
     __device__ __forceinline__ u32* out_of(u32) const { return out; }
+    __device__ __forceinline__ const SlideStep* steps_of(u32, const SlideStep* steps) const { return steps; }
+    __device__ __forceinline__ int nsteps_of(u32, int nsteps) const { return nsteps; }
+};
+// Arrays that each have an exponent of their OWN.  Under a public key of width kappa a party's decryption factors are
+// f_c = u_c^(-x_{c mod kappa} / c_k) (DistrElGamalSession.java:365-389 over (G^kappa)^omega): kappa different exponents over
+// kappa omega arrays of one size.  The schedules lie one after the other in the launch's one buffer of steps: array a walks the
+// `count[a]` steps from `first[a]` on.  Everything else is the launch's: one window width (the tables of odd powers have one
+// size), one phase count.  In the phased body a phase's steps come from the array's own count, so an array with fewer steps
+// than the launch has phases passes through phases without a step: it loads its value from out[], stores it and hands over.
+struct EachArrays {
+    static constexpr bool OWN_SCHEDULES = true;
+    const u32* x[SHARED_ARRAYS];
+    u32* out[SHARED_ARRAYS];
+    u32 first[SHARED_ARRAYS];
+    int count[SHARED_ARRAYS];
+    __device__ __forceinline__ u32 array_of(size_t T, u32 ntiles) const { return (u32)T / ntiles; }
+    __device__ __forceinline__ size_t tile_of(size_t T, u32 a, u32 ntiles) const { return (u32)T - a * ntiles; }
+    __device__ __forceinline__ const u32* x_of(u32 a) const { return x[a]; }
+    __device__ __forceinline__ u32* out_of(u32 a) const { return out[a]; }
+    __device__ __forceinline__ const SlideStep* steps_of(u32 a, const SlideStep* steps) const { return steps + first[a]; }
+    __device__ __forceinline__ int nsteps_of(u32 a, int) const { return count[a]; }
 };
 
 // `total` global tiles, `ntiles` of them per array of n elements; a table per lane slot in `tab`
@@ -74,13 +100,14 @@ __device__ __forceinline__ void modpow_shared_tiles(const A& arrs, u32 ntiles, s
         const size_t t = arrs.tile_of(T, arr, ntiles);
         const u32* __restrict__ x = arrs.x_of(arr);
         u32* __restrict__ out = arrs.out_of(arr);
+        const SlideStep* __restrict__ st = arrs.steps_of(arr, steps);
         size_t el = t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
         u32 a[C::L];
         odd_power_table<C>(a, mytab, tsize, x + ec * W, ln, nn, n0inv);
-        load_elem<C>(a, mytab + (size_t)steps[0].idx * W, ln);
-        slide_steps<C>(a, steps, 1, nsteps, mytab, ln, nn, n0inv);
+        load_elem<C>(a, mytab + (size_t)st[0].idx * W, ln);
+        slide_steps<C>(a, st, 1, arrs.nsteps_of(arr, nsteps), mytab, ln, nn, n0inv);
         canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
     }
@@ -98,7 +125,7 @@ __device__ __forceinline__ void modpow_shared_units(const A& arrs, u32 ntiles, u
     Lane<C> ln(lds);
     u32 nn[C::L];
     load_modulus<C>(nn, nmod, ln);
-    const int M = nsteps - 1;                            // steps of the main loop (step 0 is the first table read)
+    const int M_launch = nsteps - 1;                     // steps of the main loop (step 0 is the first table read)
     UnitQueue q(queue, done, s_unit, total, phases);
     while (q.take()) {
         const int ph = q.ph;
@@ -106,6 +133,9 @@ __device__ __forceinline__ void modpow_shared_units(const A& arrs, u32 ntiles, u
         const size_t t = arrs.tile_of(q.t, arr, ntiles);
         const u32* __restrict__ x = arrs.x_of(arr);
         u32* __restrict__ out = arrs.out_of(arr);
+        const SlideStep* __restrict__ st = arrs.steps_of(arr, steps);
+        int M = M_launch;                                    // (one schedule for the launch: computed once, before the queue)
+        if constexpr (A::OWN_SCHEDULES) M = arrs.nsteps_of(arr, nsteps) - 1;
         size_t el = t * C::EPB + ln.eslot;
         bool live = el < n;
         size_t ec = live ? el : n - 1;
@@ -113,13 +143,13 @@ __device__ __forceinline__ void modpow_shared_units(const A& arrs, u32 ntiles, u
         u32 a[C::L];
         if (ph == 0) {
             odd_power_table<C>(a, mytab, tsize, x + ec * W, ln, nn, n0inv);
-            load_elem<C>(a, mytab + (size_t)steps[0].idx * W, ln);
+            load_elem<C>(a, mytab + (size_t)st[0].idx * W, ln);
         } else {
             load_elem<C>(a, out + ec * W, ln);
         }
-        // the steps of this phase: 1 + M ph / P  up to  M (ph + 1) / P (s_hi: one past it)
+        // the steps of this phase: 1 + M ph / P  up to  M (ph + 1) / P (s_hi: one past it; none where M < P leaves the phase empty)
         const int s_lo = 1 + (int)((long)M * ph / phases), s_hi = 1 + (int)((long)M * (ph + 1) / phases);
-        slide_steps<C>(a, steps, s_lo, s_hi, mytab, ln, nn, n0inv);
+        slide_steps<C>(a, st, s_lo, s_hi, mytab, ln, nn, n0inv);
         if (q.last()) canonicalize<C>(a, nn, ln);
         if (live) store_elem<C>(out + el * W, a, ln);
         q.hand_over();
@@ -159,6 +189,24 @@ k_modpow_shared_multi_phased(SharedArrays arrs, u32 ntiles, u32 total, const Sli
     extern __shared__ u32 lds[];
     __shared__ u32 s_unit;
     modpow_shared_units<C>(arrs, ntiles, total, steps, nsteps, tsize, n, nmod, n0inv, tab, phases, queue, done, &s_unit, lds);
+}
+
+// several arrays of n elements each, array a under the schedule steps[arrs.first[a]] .. of arrs.count[a] steps
+template <class C>
+__global__ void __launch_bounds__(BLOCK, C::MINW)
+k_modpow_shared_each(EachArrays arrs, u32 ntiles, u32 total, const SlideStep* __restrict__ steps, int tsize, size_t n,
+                     const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab) {
+    extern __shared__ u32 lds[];
+    modpow_shared_tiles<C>(arrs, ntiles, total, steps, 0, tsize, n, nmod, n0inv, tab, lds);
+}
+template <class C>
+__global__ void __launch_bounds__(BLOCK, C::MINW)
+k_modpow_shared_each_phased(EachArrays arrs, u32 ntiles, u32 total, const SlideStep* __restrict__ steps, int tsize, size_t n,
+                            const u32* __restrict__ nmod, u32 n0inv, u32* __restrict__ tab, int phases, u32* __restrict__ queue,
+                            u32* __restrict__ done) {
+    extern __shared__ u32 lds[];
+    __shared__ u32 s_unit;
+    modpow_shared_units<C>(arrs, ntiles, total, steps, 0, tsize, n, nmod, n0inv, tab, phases, queue, done, &s_unit, lds);
 }
 
 // Two independent exponentiations in ONE launch (small arrays): job 0 = out0[i] = x0[i]^e0 (one exponent for all), job 1 =

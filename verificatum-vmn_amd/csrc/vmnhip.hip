@@ -1767,12 +1767,12 @@ static int sliding_window_bits(int ebits) {
 // `k` arrays of n elements each, all to the exponent e.  Up to SHARED_ARRAYS arrays share a launch: the geometry, the phase plan,
 // the tables and the queue are those of k n elements in k ceil(n / EPB) tiles (modp_shared_exp.h); one array takes the kernel
 // without the table of arrays.
-static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* const* xs, uint32_t* const* outs, size_t k, const Big& e,
-                         int ebits, size_t n) {
-    const int w = sliding_window_bits(ebits);
-    std::vector<SlideStep> steps;
+// The schedule of e under windows of at most w bits, appended to `steps` (its first step lands at the old end); `mults` and
+// `squarings`: the products and squarings of its main loop.
+static void slide_schedule(const Big& e, int ebits, int w, std::vector<SlideStep>& steps, long& mults, long& squarings) {
+    const size_t first = steps.size();
     int pending = 0;
-    long mults = 0, squarings = 0;
+    mults = squarings = 0;
     for (int i = ebits - 1; i >= 0;) {
         if (!hostbig::get_bit(e, i)) {
             ++pending;
@@ -1783,15 +1783,22 @@ static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* co
         while (!hostbig::get_bit(e, l)) ++l;                      // the window ends in a one: its value is odd
         uint32_t val = 0;
         for (int b = i; b >= l; --b) val = (val << 1) | (uint32_t)hostbig::get_bit(e, b);
-        steps.push_back(SlideStep{steps.empty() ? 0 : pending + (i - l + 1), (int)((val - 1) / 2)});
+        steps.push_back(SlideStep{steps.size() == first ? 0 : pending + (i - l + 1), (int)((val - 1) / 2)});
         pending = 0;
         i = l - 1;
     }
     if (pending) steps.push_back(SlideStep{pending, -1});
-    for (size_t s = 1; s < steps.size(); ++s) {
+    for (size_t s = first + 1; s < steps.size(); ++s) {
         squarings += steps[s].sq;
         mults += steps[s].idx >= 0 ? 1 : 0;
     }
+}
+static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* const* xs, uint32_t* const* outs, size_t k, const Big& e,
+                         int ebits, size_t n) {
+    const int w = sliding_window_bits(ebits);
+    std::vector<SlideStep> steps;
+    long mults = 0, squarings = 0;
+    slide_schedule(e, ebits, w, steps, mults, squarings);
     const int tsize = 1 << (w - 1);
     DevTmp dsteps(ctx);
     VMN_TRY(dsteps.alloc(steps.size() * sizeof(SlideStep)));
@@ -1824,6 +1831,65 @@ static int modpow_shared(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* co
                               (int)steps.size(), tsize, n, m.d_n, m.n0inv, pl.table(), pl.phases, pl.queue(), pl.done());
             return launch(ctx, "modpow", k_modpow_shared_multi<C>, pl.grid, lds_bytes(m), arrs, ntiles, total, d_steps, (int)steps.size(), tsize,
                           n, m.d_n, m.n0inv, reinterpret_cast<uint32_t*>(ctx->scratch));
+        }));
+    }
+    return VMN_OK;
+}
+// `k` arrays of n elements each, array c to its own exponent es[c] (every one above 32 bits).  One window width for the call, that
+// of the longest exponent, so the tables of odd powers are those of modpow_shared; one schedule per array, all in one upload; per
+// launch of up to SHARED_ARRAYS arrays the geometry, the plan, the tables and the queue of modpow_shared for the same k and n.
+// The phases are cut by the LONGEST schedule of the launch: the long powers decide how the launch ends, and an array whose
+// schedule is shorter than the phase count passes through some phases without a step (modp_shared_exp.h, EachArrays).
+static int modpow_shared_each(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* const* xs, uint32_t* const* outs, size_t k, const Big* es,
+                              const int* ebits, size_t n) {
+    const int w = sliding_window_bits(*std::max_element(ebits, ebits + k));
+    std::vector<SlideStep> steps;
+    std::vector<uint32_t> first(k);
+    std::vector<int> count(k);
+    std::vector<long> mults(k), squarings(k);
+    for (size_t c = 0; c < k; ++c) {
+        first[c] = (uint32_t)steps.size();
+        slide_schedule(es[c], ebits[c], w, steps, mults[c], squarings[c]);
+        count[c] = (int)(steps.size() - first[c]);
+    }
+    const int tsize = 1 << (w - 1);
+    DevTmp dsteps(ctx);
+    VMN_TRY(dsteps.alloc(steps.size() * sizeof(SlideStep)));
+    VMN_TRY(h2d(ctx, dsteps.p, steps.data(), steps.size() * sizeof(SlideStep)));
+    const SlideStep* d_steps = dsteps.as<SlideStep>();
+    for (size_t a0 = 0; a0 < k; a0 += SHARED_ARRAYS) {
+        const size_t ga = std::min<size_t>(SHARED_ARRAYS, k - a0);
+        const vmn_modulus& m = geom(ctx, m0, ga * n);
+        PhasePlan pl(ctx, m, n, ga);
+        VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)tsize)));
+        double products = 0, squares = 0;
+        int longest = 0;
+        EachArrays arrs{};
+        for (size_t a = 0; a < ga; ++a) {
+            arrs.x[a] = xs[a0 + a];
+            arrs.out[a] = outs[a0 + a];
+            arrs.first[a] = first[a0 + a];
+            arrs.count[a] = count[a0 + a];
+            products += (double)n * (double)(mults[a0 + a] + tsize - 1);
+            squares += (double)n * (double)(squarings[a0 + a] + 1);
+            longest = std::max(longest, count[a0 + a]);
+        }
+        note_work(ctx, m, products, squares);
+        VMN_TRY(pl.split(ctx, m, longest - 1, (size_t)tsize));
+        const uint32_t ntiles = (uint32_t)(pl.ntiles / ga), total = (uint32_t)pl.ntiles;
+        const SlideStep* one_steps = d_steps + first[a0];             // (one array: the kernel without the table of arrays)
+        VMN_TRY(with_cfg(m, [&]<class C, class W>(C, W) {
+            if (ga == 1 && pl.phases > 1)
+                return launch(ctx, "modpow", k_modpow_shared_phased<C>, pl.max_blocks, lds_bytes(m), arrs.out[0], arrs.x[0], one_steps, count[a0],
+                              tsize, n, m.d_n, m.n0inv, pl.table(), pl.phases, pl.queue(), pl.done());
+            if (ga == 1)
+                return launch(ctx, "modpow", k_modpow_shared<C>, pl.grid, lds_bytes(m), arrs.out[0], arrs.x[0], one_steps, count[a0], tsize, n,
+                              m.d_n, m.n0inv, reinterpret_cast<uint32_t*>(ctx->scratch));
+            if (pl.phases > 1)
+                return launch(ctx, "modpow", k_modpow_shared_each_phased<C>, pl.max_blocks, lds_bytes(m), arrs, ntiles, total, d_steps, tsize, n,
+                              m.d_n, m.n0inv, pl.table(), pl.phases, pl.queue(), pl.done());
+            return launch(ctx, "modpow", k_modpow_shared_each<C>, pl.grid, lds_bytes(m), arrs, ntiles, total, d_steps, tsize, n, m.d_n, m.n0inv,
+                          reinterpret_cast<uint32_t*>(ctx->scratch));
         }));
     }
     return VMN_OK;
@@ -2126,6 +2192,62 @@ extern "C" int vmn_garray_exp_scalar_multi(const vmn_garray* const* xs, size_t k
     vmn_ctx* ctx = LANE(g->ctx);
     VMN_ENTER(ctx);
     return exp_scalar_arrays(ctx, g, xs, k, e_be, ebytes, outs);
+}
+
+// outs[c][i] = xs[c][i]^(e_c), row c of es_be the exponent of array c.  Modular groups with every exponent above 32 bits: one
+// schedule per array and the arrays of a call in one launch per SHARED_ARRAYS (modpow_shared_each; VMN_EXP_MULTI_FUSED=0, read
+// per call: array by array).  Curves, or any exponent of at most 32 bits in the call: every array exactly as
+// vmn_garray_exp_scalar runs it under its exponent, one after the other.  On failure nothing stays allocated.
+extern "C" int vmn_garray_exp_scalars_multi(const vmn_garray* const* xs, size_t k, const uint8_t* es_be, size_t ebytes, vmn_garray** outs) {
+    ARG_CHECK(xs && es_be && outs && ebytes > 0, "null argument");
+    ARG_CHECK(k > 0, "no arrays");
+    for (size_t c = 0; c < k; ++c) outs[c] = nullptr;
+    for (size_t c = 0; c < k; ++c) ARG_CHECK(xs[c], "null array");
+    for (size_t c = 1; c < k; ++c) ARG_CHECK(xs[c]->grp == xs[0]->grp && xs[c]->n == xs[0]->n, "the arrays differ in group or size");
+    vmn_group* g = xs[0]->grp;
+    vmn_ctx* ctx = LANE(g->ctx);
+    VMN_ENTER(ctx);
+    const size_t n = xs[0]->n;
+    std::vector<Big> es(k);
+    std::vector<int> ebits(k);
+    bool sliding = !g->P.ec && n > 0;
+    for (size_t c = 0; c < k; ++c) {
+        es[c] = hostbig::from_be(es_be + c * ebytes, ebytes, (int)((ebytes + 3) / 4));
+        ebits[c] = std::max(1, hostbig::bit_length(es[c]));
+        sliding = sliding && ebits[c] > 32 && sliding_window_bits(ebits[c]) > 0;
+    }
+    const size_t epb_min = BLOCK / 16;                                 // (the widest geometry: the fewest elements per tile)
+    if (!(sliding && k > 1 && exp_multi_fused() && (n + epb_min - 1) / epb_min < ((size_t)1 << 32) / SHARED_ARRAYS)) {
+        for (size_t c = 0; c < k; ++c) {
+            int rc = exp_scalar_arrays(ctx, g, &xs[c], 1, es_be + c * ebytes, ebytes, &outs[c]);
+            if (rc != VMN_OK) {
+                for (size_t d = 0; d < c; ++d) {
+                    vmn_garray_free(outs[d]);
+                    outs[d] = nullptr;
+                }
+                return rc;
+            }
+        }
+        return VMN_OK;
+    }
+    std::vector<const uint32_t*> xd(k);
+    std::vector<uint32_t*> od(k);
+    int rc = VMN_OK;
+    for (size_t c = 0; rc == VMN_OK && c < k; ++c) {
+        rc = new_garray(g, n, &outs[c]);
+        if (rc == VMN_OK) {
+            xd[c] = xs[c]->d;
+            od[c] = outs[c]->d;
+        }
+    }
+    if (rc == VMN_OK) rc = modpow_shared_each(ctx, g->P, xd.data(), od.data(), k, es.data(), ebits.data(), n);
+    if (rc != VMN_OK) {
+        for (size_t c = 0; c < k; ++c) {
+            if (outs[c]) vmn_garray_free(outs[c]);
+            outs[c] = nullptr;
+        }
+    }
+    return rc;
 }
 
 // out[i] = x[i]^e * y[i]^f[i] over a modular group, exponents in packed words on the device: e one exponent of ewords words,

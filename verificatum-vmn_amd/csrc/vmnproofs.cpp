@@ -2286,31 +2286,36 @@ int lagrange(const HostGroup& G, const uint8_t* correct, int k, int threshold, s
 
 }  // namespace vmnp
 
-// A value of the plaintext group G^width (DistrElGamalSessionBasic's u, A, B', B_l live there; g, y, the secret, the randomizer,
-// the reply and the challenge stay in G / Z_q): one element per component, component 0 first.
+// A value of the plaintext group (G^keywidth)^omega (DistrElGamalSessionBasic's u, A, B', B_l live there): one element per
+// component, component 0 first, component c = l * keywidth + j the key j of plaintext component l.  g, y, the secret, the
+// randomizer and the reply live in G^keywidth / Z_q^keywidth (`Keyed`: one row per key; an exponent of Z_q^keywidth acts on
+// component c through its entry c mod keywidth); the challenge stays one field element.  keywidth = 1 is the reference's
+// default and what the entry points without `_keyed` set.
 typedef std::vector<Bytes> Wide;
+typedef std::vector<Bytes> Keyed;
 
 struct vmn_decproof {
     HostGroup G;
     int j = 0, k = 0, threshold = 0, ebitlen = 0, e_bits = 0;
-    size_t width = 1;
+    size_t width = 1;                               // components in all: keywidth * omega
+    size_t kw = 1;                                  // keywidth
     bool has_rs = false;
     vmn_random_source rs{};
     Num inverseFactor;
     std::vector<const vmn_garray*> u;               // width component arrays
-    std::vector<Bytes> y;
+    std::vector<Keyed> y;
     std::vector<const vmn_garray*> f;               // (k + 1) * width: entry l * width + c
     RA e;
     Wide A;
-    Num x, r;
-    std::vector<Bytes> yp;
+    std::vector<Num> x, r;                          // kw each
+    std::vector<Keyed> yp;
     std::vector<Wide> Bp, B;
-    std::vector<Num> k_x;
+    std::vector<std::vector<Num>> k_x;
     std::vector<char> have_kx;
     // combined
-    Bytes combinedyp, combinedy;
+    Keyed combinedyp, combinedy;
     Wide combinedBp, combinedB;
-    Num combinedk_x;
+    std::vector<Num> combinedk_x;
     std::vector<const vmn_garray*> combinedf;       // width
 
     int init(vmn_group* grp, int j_, int k_, int threshold_, int ebitlen_, const vmn_random_source* r_) {
@@ -2326,24 +2331,25 @@ struct vmn_decproof {
             has_rs = true;
         }
         inverseFactor = G.Zq.inv(prod_factor(G, k));
-        y.assign(k + 1, Bytes());
-        yp.assign(k + 1, Bytes());
+        y.assign(k + 1, Keyed());
+        yp.assign(k + 1, Keyed());
         Bp.assign(k + 1, Wide());
         B.assign(k + 1, Wide());
-        k_x.assign(k + 1, Num());
+        k_x.assign(k + 1, std::vector<Num>());
         have_kx.assign(k + 1, 0);
         return VMN_OK;
     }
     int party(int l) const { return l >= 1 && l <= k ? VMN_OK : fail(VMN_ERR_ARG, "party index %d outside 1..%d", l, k); }
     const vmn_garray* const* factors(int l) const { return f.data() + (size_t)l * width; }
     bool has_factors(int l) const { return !f.empty() && factors(l)[0] != nullptr; }
-    int set_instance(size_t width_, const vmn_garray* const* u_, const uint8_t* y_be, const vmn_garray* const* f_) {
-        REQUIRE(width_ >= 1 && u_ && y_be && f_, "null argument");
+    int set_instance(size_t kw_, size_t omega, const vmn_garray* const* u_, const uint8_t* y_be, const vmn_garray* const* f_) {
+        REQUIRE(kw_ >= 1 && omega >= 1 && u_ && y_be && f_, "null argument");
+        const size_t width_ = kw_ * omega;
         for (size_t c = 0; c < width_; ++c) {
             REQUIRE(u_[c], "null argument");
             if (vmn_garray_size(u_[c]) != vmn_garray_size(u_[0])) return fail(VMN_ERR_ARG, "the components of u differ in size");
         }
-        if (width_ != width) {                          // values of another width are no values of this instance
+        if (width_ != width || kw_ != kw) {             // values of another width or key width are no values of this instance
             A.clear();
             combinedB.clear();
             for (int l = 0; l <= k; ++l) {
@@ -2351,11 +2357,27 @@ struct vmn_decproof {
                 B[l].clear();
             }
         }
+        if (kw_ != kw) {
+            x.clear();
+            r.clear();
+            combinedyp.clear();
+            combinedk_x.clear();
+            for (int l = 0; l <= k; ++l) {
+                yp[l].clear();
+                k_x[l].clear();
+                have_kx[l] = 0;
+            }
+        }
         width = width_;
+        kw = kw_;
         u.assign(u_, u_ + width);
         f.assign((size_t)(k + 1) * width, nullptr);
         for (int l = 1; l <= k; ++l) {
-            y[l].assign(y_be + (size_t)l * G.eb, y_be + (size_t)(l + 1) * G.eb);
+            y[l].assign(kw, Bytes());
+            for (size_t i = 0; i < kw; ++i) {
+                const uint8_t* row = y_be + ((size_t)l * kw + i) * G.eb;
+                y[l][i].assign(row, row + G.eb);
+            }
             const vmn_garray* const* fl = f_ + (size_t)l * width;
             for (size_t c = 0; c < width; ++c) {
                 if (!fl[c] != !fl[0]) return fail(VMN_ERR_ARG, "decryption factors of party %d lack a component", l);
@@ -2382,31 +2404,44 @@ struct vmn_decproof {
     }
     int commit(const uint8_t* x_be, uint8_t* yp_out, uint8_t* Bp_out) {
         REQUIRE(x_be && yp_out && Bp_out && has_rs && !A.empty(), "commit needs a random source and batchInput()");
-        x = G.ring_from(x_be);
         const uint8_t* rows = nullptr;
-        if (rs.ring_elements(rs.user, 1, &rows) != 0 || !rows) return fail(VMN_ERR_ARG, "random source failed");
-        r = G.ring_from(rows);
-        if (vmn::num64::cmp(r, G.Zq.n) >= 0) return fail(VMN_ERR_FORMAT, "random source returned a value >= q");
-        TRY(G.el_exp(G.g, r, yp[j]));                                            // y' = g^r
+        if (rs.ring_elements(rs.user, kw, &rows) != 0 || !rows) return fail(VMN_ERR_ARG, "random source failed");
+        std::vector<Num> xs(kw), rr(kw);
+        for (size_t i = 0; i < kw; ++i) {
+            xs[i] = G.ring_from(x_be + i * G.xb);
+            rr[i] = G.ring_from(rows + i * G.xb);
+            if (vmn::num64::cmp(rr[i], G.Zq.n) >= 0) return fail(VMN_ERR_FORMAT, "random source returned a value >= q");
+        }
+        x = xs;
+        r = rr;
+        yp[j].assign(kw, Bytes());
+        for (size_t i = 0; i < kw; ++i) TRY(G.el_exp(G.g, r[i], yp[j][i]));              // y' = g^r, key by key
         Bp[j].assign(width, Bytes());
-        for (size_t c = 0; c < width; ++c) TRY(G.el_exp(A[c], r, Bp[j][c]));     // B' = A^r, component by component
-        memcpy(yp_out, yp[j].data(), G.eb);
+        for (size_t c = 0; c < width; ++c) TRY(G.el_exp(A[c], r[c % kw], Bp[j][c]));     // B' = A^r, component by component
+        for (size_t i = 0; i < kw; ++i) memcpy(yp_out + i * G.eb, yp[j][i].data(), G.eb);
         for (size_t c = 0; c < width; ++c) memcpy(Bp_out + c * G.eb, Bp[j][c].data(), G.eb);
         return VMN_OK;
     }
     int reply(const uint8_t* v_be, size_t vbytes, uint8_t* kx_out) {
-        REQUIRE(v_be && vbytes && kx_out && !x.empty() && !r.empty(), "reply needs commit()");
+        REQUIRE(v_be && vbytes && kx_out && x.size() == kw && r.size() == kw, "reply needs commit()");
         Num v = G.reduce(v_be, vbytes);
-        k_x[j] = G.Zq.add(G.Zq.mul(G.Zq.mul(G.Zq.neg(x), inverseFactor), v), r);  // -x c^-1 v + r   :595-598
+        k_x[j].assign(kw, Num());
+        for (size_t i = 0; i < kw; ++i) {
+            k_x[j][i] = G.Zq.add(G.Zq.mul(G.Zq.mul(G.Zq.neg(x[i]), inverseFactor), v), r[i]);  // -x c^-1 v + r   :595-598
+            Bytes out = G.ring_bytes(k_x[j][i]);
+            memcpy(kx_out + i * G.xb, out.data(), G.xb);
+        }
         have_kx[j] = 1;
-        Bytes out = G.ring_bytes(k_x[j]);
-        memcpy(kx_out, out.data(), G.xb);
         return VMN_OK;
     }
     int set_commitment(int l, const uint8_t* yp_be, const uint8_t* Bp_be) {
-        Bytes a(yp_be, yp_be + G.eb);
+        Keyed a(kw);
         Wide b(width);
-        std::vector<const Bytes*> els{&a};
+        std::vector<const Bytes*> els;
+        for (size_t i = 0; i < kw; ++i) {
+            a[i].assign(yp_be + i * G.eb, yp_be + (i + 1) * G.eb);
+            els.push_back(&a[i]);
+        }
         for (size_t c = 0; c < width; ++c) {
             b[c].assign(Bp_be + c * G.eb, Bp_be + (c + 1) * G.eb);
             els.push_back(&b[c]);
@@ -2418,18 +2453,32 @@ struct vmn_decproof {
         Bp[l] = b;
         return VMN_OK;
     }
-    // y^(-cv) y' = g^k checked once, B^v B' = A^k in every component (:693-700, :718-727)
-    int check(const Bytes& y_, const Num& yexp, const Bytes& yp_, const Wide& B_, const Wide& Bp_, const Num& v, const Num& kx, int* verdict) const {
+    int set_reply(int l, const uint8_t* kx_be) {
+        k_x[l].assign(kw, Num());
+        have_kx[l] = 1;
+        for (size_t i = 0; i < kw; ++i) {
+            k_x[l][i] = G.ring_from(kx_be + i * G.xb);
+            if (vmn::num64::cmp(k_x[l][i], G.Zq.n) >= 0) have_kx[l] = 2;
+        }
+        if (have_kx[l] == 2) k_x[l].assign(kw, Num(G.ql, 0));      // pRing.toElement fails: k_x = 0, verdict false (:606-613)
+        return VMN_OK;
+    }
+    // y^(-cv) y' = g^k under every key, B^v B' = A^k in every component (:693-700, :718-727)
+    int check(const Keyed& y_, const Num& yexp, const Keyed& yp_, const Wide& B_, const Wide& Bp_, const Num& v, const std::vector<Num>& kx,
+              int* verdict) const {
         Bytes yinv, t, lhs, rhs;
-        TRY(G.el_inv(y_, yinv));
-        TRY(G.el_exp(yinv, yexp, t));
-        TRY(G.el_mul(t, yp_, lhs));
-        TRY(G.el_exp(G.g, kx, rhs));
-        int ok = lhs == rhs;
+        int ok = 1;
+        for (size_t i = 0; i < kw; ++i) {
+            TRY(G.el_inv(y_[i], yinv));
+            TRY(G.el_exp(yinv, yexp, t));
+            TRY(G.el_mul(t, yp_[i], lhs));
+            TRY(G.el_exp(G.g, kx[i], rhs));
+            ok = ok && lhs == rhs;
+        }
         for (size_t c = 0; c < width; ++c) {
             TRY(G.el_exp(B_[c], v, t));
             TRY(G.el_mul(t, Bp_[c], lhs));
-            TRY(G.el_exp(A[c], kx, rhs));
+            TRY(G.el_exp(A[c], kx[c % kw], rhs));
             ok = ok && lhs == rhs;
         }
         *verdict = ok;
@@ -2437,7 +2486,8 @@ struct vmn_decproof {
     }
     int verify(int l, const uint8_t* v_be, size_t vbytes, int* verdict) {
         TRY(party(l));
-        REQUIRE(verdict && v_be && vbytes && !A.empty() && B[l].size() == width && Bp[l].size() == width && !yp[l].empty() && have_kx[l],
+        REQUIRE(verdict && v_be && vbytes && !A.empty() && B[l].size() == width && Bp[l].size() == width && yp[l].size() == kw &&
+                    y[l].size() == kw && have_kx[l] && k_x[l].size() == kw,
                 "verify needs batch(l), the commitment and the reply of l");
         if (have_kx[l] == 2) {                                                   // malformed reply: verdicts[l] = false (:719-721)
             *verdict = 0;
@@ -2452,25 +2502,29 @@ struct vmn_decproof {
         std::vector<Num> abs;
         std::vector<int> neg, parties;
         TRY(lagrange(G, correct, k, threshold, abs, neg, &parties));
-        combinedyp = G.one();
+        combinedyp.assign(kw, G.one());
         combinedBp.assign(width, G.one());
-        combinedk_x = Num(G.ql, 0);
+        combinedk_x.assign(kw, Num(G.ql, 0));
         for (size_t t = 0; t < parties.size(); ++t) {
             const int l = parties[t];
-            REQUIRE(!yp[l].empty() && Bp[l].size() == width && have_kx[l], "combine needs the commitment and the reply of every combined party");
+            REQUIRE(yp[l].size() == kw && Bp[l].size() == width && have_kx[l] && k_x[l].size() == kw,
+                    "combine needs the commitment and the reply of every combined party");
             Num ex = neg[t] ? G.Zq.neg(abs[t]) : abs[t];
             Bytes a, b2;
-            TRY(G.el_exp(yp[l], ex, a));
-            TRY(G.el_mul(combinedyp, a, b2));
-            combinedyp = b2;
+            for (size_t i = 0; i < kw; ++i) {
+                TRY(G.el_exp(yp[l][i], ex, a));
+                TRY(G.el_mul(combinedyp[i], a, b2));
+                combinedyp[i] = b2;
+            }
             for (size_t c = 0; c < width; ++c) {
                 TRY(G.el_exp(Bp[l][c], ex, a));
                 TRY(G.el_mul(combinedBp[c], a, b2));
                 combinedBp[c] = b2;
             }
-            combinedk_x = G.Zq.add(combinedk_x, G.Zq.mul(k_x[l], ex));
+            for (size_t i = 0; i < kw; ++i) combinedk_x[i] = G.Zq.add(combinedk_x[i], G.Zq.mul(k_x[l][i], ex));
         }
-        combinedy.assign(combinedy_be, combinedy_be + G.eb);
+        combinedy.assign(kw, Bytes());
+        for (size_t i = 0; i < kw; ++i) combinedy[i].assign(combinedy_be + i * G.eb, combinedy_be + (i + 1) * G.eb);
         combinedf.assign(combinedf_, combinedf_ + width);
         combinedB.clear();
         return VMN_OK;
@@ -2480,7 +2534,8 @@ struct vmn_decproof {
         return expprod(combinedf.data(), combinedB);
     }
     int verify_combined(const uint8_t* v_be, size_t vbytes, int* verdict) {
-        REQUIRE(verdict && v_be && vbytes && !combinedB.empty() && !A.empty(), "verifyCombined needs batchCombined()");
+        REQUIRE(verdict && v_be && vbytes && !combinedB.empty() && !A.empty() && combinedy.size() == kw && combinedyp.size() == kw,
+                "verifyCombined needs batchCombined()");
         Num v = G.reduce(v_be, vbytes);
         return check(combinedy, v, combinedyp, combinedB, combinedBp, v, combinedk_x, verdict);
     }
@@ -2987,6 +3042,7 @@ size_t vmn_posc_size(const vmn_posc* p) { return p ? p->Ntot : 0; }
 size_t vmn_ccpos_size(const vmn_ccpos* p) { return p ? p->Ntot : 0; }
 size_t vmn_decproof_size(const vmn_decproof* p) { return p && !p->u.empty() ? vmn_garray_size(p->u[0]) : 0; }
 size_t vmn_decproof_width(const vmn_decproof* p) { return p ? p->width : 0; }
+size_t vmn_decproof_keywidth(const vmn_decproof* p) { return p ? p->kw : 0; }
 size_t vmn_igen_size(const vmn_igen* p) { return p ? p->N : 0; }
 int vmn_decproof_parties(const vmn_decproof* p) { return p ? p->k : 0; }
 int vmn_igen_parties(const vmn_igen* p) { return p ? p->threshold : 0; }
@@ -3209,17 +3265,27 @@ int vmn_lagrange_coefficients(vmn_group* grp, const uint8_t* correct, int k, int
     }
     return VMN_OK;
 }
-int vmn_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* const* u, const uint8_t* secret_be, int k, vmn_garray** f_out) {
-    if (!grp || !u || !secret_be || !f_out || k < 1 || width < 1) return fail(VMN_ERR_ARG, "vmn_decryption_factors: bad argument");
-    for (size_t c = 0; c < width; ++c) {
+int vmn_decryption_factors_keyed(vmn_group* grp, size_t keywidth, size_t width, const vmn_garray* const* u, const uint8_t* secrets_be, int k,
+                                 vmn_garray** f_out) {
+    if (!grp || !u || !secrets_be || !f_out || k < 1 || width < 1 || keywidth < 1) return fail(VMN_ERR_ARG, "vmn_decryption_factors: bad argument");
+    const size_t W = keywidth * width;
+    for (size_t c = 0; c < W; ++c) {
         if (!u[c]) return fail(VMN_ERR_ARG, "vmn_decryption_factors: bad argument");
     }
     HostGroup G;
     TRY(G.init(grp));
-    // firstComponents.exp(secretKey.neg().mul(inverseFactor))   DistrElGamalSession.java:384-385
-    Num ex = G.Zq.mul(G.Zq.neg(G.ring_from(secret_be)), G.Zq.inv(prod_factor(G, k)));
-    Bytes eb = G.ring_bytes(ex);
-    return vmn_garray_exp_scalar_multi(u, width, eb.data(), eb.size(), f_out);
+    // firstComponents.exp(secretKey.neg().mul(inverseFactor))   DistrElGamalSession.java:384-385; over G^keywidth the exponent has
+    // keywidth entries and component c takes entry c mod keywidth
+    const Num inverseFactor = G.Zq.inv(prod_factor(G, k));
+    std::vector<Bytes> eb(keywidth);
+    for (size_t i = 0; i < keywidth; ++i) eb[i] = G.ring_bytes(G.Zq.mul(G.Zq.neg(G.ring_from(secrets_be + i * G.xb)), inverseFactor));
+    if (keywidth == 1) return vmn_garray_exp_scalar_multi(u, W, eb[0].data(), eb[0].size(), f_out);
+    Bytes rows;
+    for (size_t c = 0; c < W; ++c) rows.insert(rows.end(), eb[c % keywidth].begin(), eb[c % keywidth].end());
+    return vmn_garray_exp_scalars_multi(u, W, rows.data(), eb[0].size(), f_out);
+}
+int vmn_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* const* u, const uint8_t* secret_be, int k, vmn_garray** f_out) {
+    return vmn_decryption_factors_keyed(grp, 1, width, u, secret_be, k, f_out);
 }
 int vmn_decryption_factors(vmn_group* grp, const vmn_garray* u, const uint8_t* secret_be, int k, vmn_garray** f_out) {
     return vmn_decryption_factors_wide(grp, 1, &u, secret_be, k, f_out);
@@ -3289,11 +3355,16 @@ int vmn_decproof_create(vmn_group* grp, int j, int k, int threshold, int ebitlen
 void vmn_decproof_free(vmn_decproof* p) { delete p; }
 int vmn_decproof_set_instance_wide(vmn_decproof* p, size_t width, const vmn_garray* const* u, const uint8_t* y_be, const vmn_garray* const* f) {
     NONNULL(p);
-    return p->set_instance(width, u, y_be, f);
+    return p->set_instance(1, width, u, y_be, f);
+}
+int vmn_decproof_set_instance_keyed(vmn_decproof* p, size_t keywidth, size_t width, const vmn_garray* const* u, const uint8_t* y_be,
+                                    const vmn_garray* const* f) {
+    NONNULL(p);
+    return p->set_instance(keywidth, width, u, y_be, f);
 }
 int vmn_decproof_set_instance(vmn_decproof* p, const vmn_garray* u, const uint8_t* y_be, const vmn_garray* const* f) {
     NONNULL(p);
-    return p->set_instance(1, &u, y_be, f);
+    return p->set_instance(1, 1, &u, y_be, f);
 }
 int vmn_decproof_set_batch_vector(vmn_decproof* p, const uint8_t* e_be) {
     NONNULL(p);
@@ -3327,13 +3398,7 @@ int vmn_decproof_set_reply(vmn_decproof* p, int l, const uint8_t* kx_be) {
     NONNULL(p);
     TRY(p->party(l));
     if (!kx_be) return fail(VMN_ERR_ARG, "vmn_decproof_set_reply: null argument");
-    p->k_x[l] = p->G.ring_from(kx_be);
-    p->have_kx[l] = 1;
-    if (vmn::num64::cmp(p->k_x[l], p->G.Zq.n) >= 0) {          // pRing.toElement fails: k_x = 0, verdict false (:606-613)
-        p->k_x[l] = Num(p->G.ql, 0);
-        p->have_kx[l] = 2;
-    }
-    return VMN_OK;
+    return p->set_reply(l, kx_be);
 }
 int vmn_decproof_batch(vmn_decproof* p, int l) {
     NONNULL(p);

@@ -78,7 +78,8 @@ def plib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise VmnError(-2, f"{LIB_PATH} is missing: run __graft_entry__.build()")
         _plib = C.CDLL(LIB_PATH)
-        for name in ("vmn_msg_items", "vmn_msg_bytetree_size", "vmn_pos_width", "vmn_ccpos_width", "vmn_decproof_width"):
+        for name in ("vmn_msg_items", "vmn_msg_bytetree_size", "vmn_pos_width", "vmn_ccpos_width", "vmn_decproof_width",
+                     "vmn_decproof_keywidth"):
             getattr(_plib, name).restype = C.c_size_t
         for name in ("vmn_msg_item_garray", "vmn_msg_item_rarray", "vmn_pos_permutation_commitment"):
             getattr(_plib, name).restype = C.c_void_p
@@ -691,8 +692,18 @@ def _opt_ptr_array(arrs):
     return (C.c_void_p * len(arrs))(*[(a._h.value if a is not None else None) for a in arrs])
 
 
-def decryptionFactors(u, secretKey: int, q: int, k: int):
-    """``vmn_decryption_factors[_wide]``: u^(-x_j / c), for a list of component arrays in one call."""
+def decryptionFactors(u, secretKey, q: int, k: int):
+    """``vmn_decryption_factors[_wide]``: u^(-x_j / c), for a list of component arrays in one call.  With a list of kappa
+    secrets (a key of width kappa) ``vmn_decryption_factors_keyed``: u is kappa * omega component arrays, component
+    l * kappa + j under secret j."""
+    if _is_wide(secretKey):
+        group, kw = u[0].group, len(secretKey)
+        if kw < 1 or len(u) % kw:
+            raise ValueError(f"{len(u)} component arrays are no multiple of the key width {kw}")
+        outs = (C.c_void_p * len(u))()
+        _check(plib().vmn_decryption_factors_keyed(group._h, C.c_size_t(kw), C.c_size_t(len(u) // kw), _opt_ptr_array(u),
+                                                   b"".join(int_to_be(x % q, group.exp_bytes) for x in secretKey), C.c_int(k), outs))
+        return [PGroupElementArray(group, C.c_void_p(h)) for h in outs]
     if not _is_wide(u):
         out = C.c_void_p()
         _check(plib().vmn_decryption_factors(u.group._h, u._h, int_to_be(secretKey % q, u.group.exp_bytes), C.c_int(k), C.byref(out)))
@@ -736,7 +747,10 @@ def plaintexts(v, combinedFactors):
 class DistrElGamalSessionBasic:
     """``vmn_decproof_*`` — ref: elgamal/DistrElGamalSessionBasic.java (one instance per party j).  With a list of omega
     component arrays as ``u`` (and lists as the parties' factors) the session works over G^omega: ``commit`` returns B' as an
-    omega-tuple, ``setCommitment`` takes one, ``combine`` takes a list of combined factors."""
+    omega-tuple, ``setCommitment`` takes one, ``combine`` takes a list of combined factors.  With ``keywidth`` = kappa > 1 in
+    ``setInstance`` (u: kappa * omega arrays, component l * kappa + j) the key lives in G^kappa: ``y[l]`` and ``combinedy`` are
+    kappa-tuples, ``commit`` takes kappa secrets and returns (kappa-tuple, W-tuple), ``reply`` returns a kappa-tuple and
+    ``setCommitment`` / ``setReply`` take the matching tuples."""
 
     def __init__(self, group, j: int, k: int, threshold: int, ebitlen: int, rand=None):
         self.G, self.j, self.k, self.q = group, j, k, group.q
@@ -747,6 +761,7 @@ class DistrElGamalSessionBasic:
         self.k_x = {}
         self._keep = []
         self.width = None                           # None: width 1 through the width-1 entry points
+        self.keywidth = 1
 
     def free(self):
         if self._h and self.G.alive:
@@ -762,10 +777,19 @@ class DistrElGamalSessionBasic:
     def _call(self, name, *args):
         _check(getattr(plib(), "vmn_decproof_" + name)(self._h, *args))
 
-    def setInstance(self, u, y, f):
+    def setInstance(self, u, y, f, keywidth: int = 1):
         G = self.G
-        ybuf = b"".join(G.enc_el(el) if el is not None else bytes(G.elem_bytes) for el in y)
         self._keep = [u, f]
+        if keywidth > 1:
+            if not _is_wide(u) or len(u) % keywidth:
+                raise ValueError("a key of width kappa needs a list of kappa * omega component arrays")
+            ybuf = b"".join(b"".join(G.enc_el(el) for el in yl) if yl is not None else bytes(keywidth * G.elem_bytes) for yl in y)
+            self.width, self.keywidth = len(u), keywidth
+            self._call("set_instance_keyed", C.c_size_t(keywidth), C.c_size_t(len(u) // keywidth), _opt_ptr_array(u), ybuf,
+                       _wide_factor_table(f, self.width))
+            return
+        self.keywidth = 1
+        ybuf = b"".join(G.enc_el(el) if el is not None else bytes(G.elem_bytes) for el in y)
         if _is_wide(u):
             self.width = len(u)
             self._call("set_instance_wide", C.c_size_t(self.width), _opt_ptr_array(u), ybuf, _wide_factor_table(f, self.width))
@@ -783,23 +807,43 @@ class DistrElGamalSessionBasic:
     def batchInput(self):
         self._call("batch_input")
 
-    def commit(self, x: int):
+    def _rows(self, vals, enc):
+        if len(vals) != self.keywidth:
+            raise ValueError(f"{len(vals)} rows, the key has width {self.keywidth}")
+        return b"".join(enc(v) for v in vals)
+
+    def commit(self, x):
         G = self.G
         eb, w = G.elem_bytes, self.width or 1
+        if self.keywidth > 1:
+            kw = self.keywidth
+            yp, Bp = C.create_string_buffer(kw * eb), C.create_string_buffer(w * eb)
+            self._call("commit", self._rows(x, lambda xi: int_to_be(xi % self.q, G.exp_bytes)), yp, Bp)
+            return (tuple(G.dec_el(yp.raw[i * eb:(i + 1) * eb]) for i in range(kw)),
+                    tuple(G.dec_el(Bp.raw[c * eb:(c + 1) * eb]) for c in range(w)))
         yp, Bp = C.create_string_buffer(eb), C.create_string_buffer(w * eb)
         self._call("commit", int_to_be(x % self.q, G.exp_bytes), yp, Bp)
         if self.width is None:
             return G.dec_el(yp.raw), G.dec_el(Bp.raw)
         return G.dec_el(yp.raw), tuple(G.dec_el(Bp.raw[c * eb:(c + 1) * eb]) for c in range(w))
 
-    def reply(self, v: int) -> int:
+    def reply(self, v: int):
         b = _be(v)
-        out = C.create_string_buffer(self.G.exp_bytes)
+        xb = self.G.exp_bytes
+        out = C.create_string_buffer(self.keywidth * xb)
         self._call("reply", b, C.c_size_t(len(b)), out)
-        self.k_x[self.j] = int.from_bytes(out.raw, "big")
+        if self.keywidth > 1:
+            self.k_x[self.j] = tuple(int.from_bytes(out.raw[i * xb:(i + 1) * xb], "big") for i in range(self.keywidth))
+        else:
+            self.k_x[self.j] = int.from_bytes(out.raw, "big")
         return self.k_x[self.j]
 
     def setCommitment(self, l: int, yp, Bp):
+        if self.keywidth > 1:
+            if len(Bp) != self.width:
+                raise ValueError(f"B' has {len(Bp)} components, the instance has width {self.width}")
+            self._call("set_commitment", C.c_int(l), self._rows(yp, self.G.enc_el), b"".join(self.G.enc_el(b) for b in Bp))
+            return
         if self.width is None:
             self._call("set_commitment", C.c_int(l), self.G.enc_el(yp), self.G.enc_el(Bp))
             return
@@ -807,12 +851,16 @@ class DistrElGamalSessionBasic:
             raise ValueError(f"B' has {len(Bp)} components, the instance has width {self.width}")
         self._call("set_commitment", C.c_int(l), self.G.enc_el(yp), b"".join(self.G.enc_el(b) for b in Bp))
 
-    def setReply(self, l: int, k_x: int):
+    def setReply(self, l: int, k_x):
         # a value that fits the wire width is handed over as it is: one >= q is not a field element and costs the party
         # its verdict (DistrElGamalSessionBasic.java:606-613), it is not reduced
-        raw = k_x if 0 <= k_x < 1 << (8 * self.G.exp_bytes) else k_x % self.q
+        wire = lambda kv: int_to_be(kv if 0 <= kv < 1 << (8 * self.G.exp_bytes) else kv % self.q, self.G.exp_bytes)
+        if self.keywidth > 1:
+            self.k_x[l] = tuple(kv % self.q for kv in k_x)
+            self._call("set_reply", C.c_int(l), self._rows(k_x, wire))
+            return
         self.k_x[l] = k_x % self.q
-        self._call("set_reply", C.c_int(l), int_to_be(raw, self.G.exp_bytes))
+        self._call("set_reply", C.c_int(l), wire(k_x))
 
     def batch(self, l: int):
         self._call("batch", C.c_int(l))
@@ -825,6 +873,11 @@ class DistrElGamalSessionBasic:
 
     def combine(self, correct, combinedy, combinedf):
         self._keep.append(combinedf)
+        if self.keywidth > 1:
+            if len(combinedf) != self.width:
+                raise ValueError(f"{len(combinedf)} combined factor arrays, the instance has width {self.width}")
+            self._call("combine_wide", _flags(correct), self._rows(combinedy, self.G.enc_el), _opt_ptr_array(combinedf))
+            return
         if self.width is None:
             self._call("combine", _flags(correct), self.G.enc_el(combinedy), combinedf._h)
             return
