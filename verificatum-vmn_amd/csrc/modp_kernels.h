@@ -387,12 +387,15 @@ __device__ __forceinline__ void mont_mul(u32 (&r)[C::L], const u32 (&a)[C::L], c
     }
     normalize<C>(r, T, ln);
 }
-// r = a^2 / R mod N; the element's LDS column must hold a copy of a
+// r = a^2 / R mod N.  SQR_FROM_LDS<C>: the element's LDS column must hold a copy of a (the row's own limb needs a dynamic
+// index); the 29-bit rows are unrolled one by one and read it from a's registers -- they leave the column alone.  sqr_times asks;
+// odd_power_table (never instantiated on Cfg29) writes the column anyway, its product reads it next.
+template <class C> constexpr bool SQR_FROM_LDS = C::BITS != 29;
 template <class C>
 __device__ __forceinline__ void mont_sqr(u32 (&r)[C::L], const u32 (&a)[C::L], const Lane<C>& ln, const u32 (&n)[C::L], u32 n0inv) {
     u64 T[C::L];
     if constexpr (C::BITS == 29) {
-        mont29_sqr_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
+        mont29_sqr_columns<C::L>(T, a, n, n0inv);
     } else if constexpr (C::LPE == 1) {
         mont_sqr_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
     } else {
@@ -655,7 +658,7 @@ template <class C>
 __device__ __forceinline__ void sqr_times(u32 (&a)[C::L], int count, const Lane<C>& ln, const u32 (&nn)[C::L], u32 n0inv) {
 #pragma unroll 1
     for (int s = 0; s < count; ++s) {
-        regs_to_lds<C>(ln, a);
+        if constexpr (SQR_FROM_LDS<C>) regs_to_lds<C>(ln, a);
         mont_sqr<C>(a, a, ln, nn, n0inv);
     }
 }

@@ -147,22 +147,19 @@ __device__ __forceinline__ void mont29_mul_columns(u64 (&T)[S], const u32 (&a)[S
     mont29_mul_rows<S>(T, a, b_lds, bstride, n, n0inv, bn, B, S);
     T[S - 1] = 0;
 }
+// A squaring takes row I's multiplier limb from its register: the rows are unrolled by recursion, so a[I] is a static index and
+// nothing goes through LDS.  (a[I] is then two inputs of the row's statement, as a[I] and as b; m and c are early-clobber
+// outputs and get registers of their own.)
 template <int S, int I>
-__device__ __forceinline__ void mont29_sqr_rows(u64 (&T)[S], const u32 (&a)[S], const u32* a_lds, int bstride,
-                                                const u32 (&n)[S], u32 n0inv, u32& bn) {
+__device__ __forceinline__ void mont29_sqr_rows(u64 (&T)[S], const u32 (&a)[S], const u32 (&n)[S], u32 n0inv) {
     if constexpr (I == Relief29<S>::A || I == Relief29<S>::B) mont29_relieve<S>(T);
-    u32 bi = bn;
-    bn = a_lds[(I + 1 < S ? I + 1 : 0) * bstride];
-    mont29_sqr_row_asm<S, I>(T, a, bi, bi << 1, n, n0inv);
-    if constexpr (I + 1 < S) mont29_sqr_rows<S, I + 1>(T, a, a_lds, bstride, n, n0inv, bn);
+    mont29_sqr_row_asm<S, I>(T, a, a[I], a[I] << 1, n, n0inv);
+    if constexpr (I + 1 < S) mont29_sqr_rows<S, I + 1>(T, a, n, n0inv);
 }
 template <int S>
-__device__ __forceinline__ void mont29_sqr_columns(u64 (&T)[S], const u32 (&a)[S], const u32* a_lds, int bstride,
-                                                   const u32 (&n)[S], u32 n0inv) {
-    u32 b0 = a_lds[0];
-    u32 bn = a_lds[bstride];
-    mont29_sqr_row_asm_first<S>(T, a, b0, b0 << 1, n, n0inv);
-    mont29_sqr_rows<S, 1>(T, a, a_lds, bstride, n, n0inv, bn);
+__device__ __forceinline__ void mont29_sqr_columns(u64 (&T)[S], const u32 (&a)[S], const u32 (&n)[S], u32 n0inv) {
+    mont29_sqr_row_asm_first<S>(T, a, a[0], a[0] << 1, n, n0inv);
+    mont29_sqr_rows<S, 1>(T, a, n, n0inv);
     T[S - 1] = 0;
 }
 
