@@ -30,7 +30,7 @@ FILL_FROM_BLOCK = int(__import__("os").environ.get("VMN_ROW_FILL", "0"))
 LEAD = int(__import__("os").environ.get("VMN_ROW_LEAD", "3"))   # products issued ahead of the reduction (see _row)
 
 
-def _row(S: int, first: bool, j0: int = 0, blk: int = 0, bits: int = 28, any_row: bool = False):
+def _row(S: int, first: bool, j0: int = 0, blk: int = 0, bits: int = 28, any_row: bool = False, short: bool = False):
     """Instruction list and operand lists of one row (limbs of `bits` bits).
 
     blk == 0: general multiplication row, multiplier b for every column.
@@ -43,17 +43,20 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0, bits: int = 28, any_row
     any_row:  (blk = 1) ONE text for the squaring rows 1 .. S-1: the row's index is an immediate operand and the assembler's
               .if / .endif pick each column's product -- none (column < row), by b (column = row) or by b2.  The order of the
               instructions does not depend on the row, so this is the text of every row with the products it skips left out.
+    short:    the reduction half for a modulus N = -1 mod 2^(2 bits) (SHORT29_ONES below): the modulus operands are the S-2 limbs of
+              N'' = (N + 1) >> (2 bits), there is no n0inv, and the head is and / shift / add instead of the chain through m * N[0].
     """
     sqr = blk > 0
+    NN = S - 2 if short else S            # modulus operands
     P = lambda j: f"%{j}"                 # 0..S-1      u64 "+v"
     M = f"%{S}"                           # m           u32 "=&v"
     C = f"%{S + 1}"                       # c           u64 "=&v"
     A = lambda j: f"%{S + 2 + j}"         # a[j]        u32 "v"
     B = f"%{2 * S + 2}"                   # b limb      u32 "v"
     N = lambda j: f"%{2 * S + 3 + j}"     # N[j]        u32 "s"
-    NI = f"%{3 * S + 3}"                  # n0inv       u32 "s"
-    B2 = f"%{3 * S + 4}"                  # 2*b         u32 "v"  (squaring rows only)
-    ROW = f"%{3 * S + 5}"                 # the row's index, "n" (any_row only)
+    NI = f"%{2 * S + 3 + NN}"             # n0inv       u32 "s"  (not in a short row: the operands after it move down by one)
+    B2 = f"%{2 * S + 3 + NN + (not short)}"         # 2*b         u32 "v"  (squaring rows only)
+    ROW = f"%{2 * S + 4 + NN + (not short)}"        # the row's index, "n" (any_row only)
     MASK = hex((1 << bits) - 1)           # 2^bits-1 as a 32-bit literal (saves an SGPR)
 
     L = []
@@ -91,6 +94,22 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0, bits: int = 28, any_row
             ab(k)                                    # the chain's gaps with the block's own products instead
             k += 1
     per = max(1, (LEAD - 1) // 4)
+    if short:
+        # m = P[0] mod 2^bits (n' = 1).  m * N = m * N'' * 2^(2 bits) - m: taking m from column 0 clears its low limb, so the
+        # carry into column 1 is P[0] >> bits; column 1 gets no product of the reduction, columns j >= 2 get m * N''[j-2].
+        lead(per)
+        L.append(f"v_and_b32 {M}, {MASK}, v{P0REG}")
+        lead(per)
+        L.append(f"v_lshrrev_b64 {C}, {bits}, {P(0)}")
+        lead(per)
+        ab(1)                                        # column 1 must have its product before it moves to column 0
+        L.append(f"v_lshl_add_u64 {P(0)}, {P(1)}, 0, {C}")
+        lead(per)
+        for j in range(2, S):
+            ab(j + LEAD)
+            ab(j)
+            L.append(f"v_mad_u64_u32 {P(j - 1)}, vcc, {M}, {N(j - 2)}, {P(j)}")
+        return L
     lead(per)
     L.append(f"v_mul_lo_u32 {M}, v{P0REG}, {NI}")   # low dword of column 0 (operand 0 is pinned to v[P0REG:P0REG+1])
     lead(per)
@@ -110,16 +129,18 @@ def _row(S: int, first: bool, j0: int = 0, blk: int = 0, bits: int = 28, any_row
     return L
 
 
-def _emit(name: str, S: int, lines, first: bool, sqr: bool, tparams: str, any_row: bool = False) -> str:
+def _emit(name: str, S: int, lines, first: bool, sqr: bool, tparams: str, any_row: bool = False, short: bool = False) -> str:
+    """short: same C++ signature, but n[S-2], n[S-1] and n0inv are not operands of the statement (n holds the limbs of N'')."""
     out = []
     extra = ", u32 b2" if sqr else ""
+    ni = "u32" if short else "u32 n0inv"
     if any_row:       # the primary template, for this S only: the row is a template argument and an operand of the text
         out.append(f"template <int S, int I> __device__ __forceinline__ void {name}(u64 (&P)[S], const u32 (&a)[S], u32 b{extra},\n"
-                   f"        const u32 (&n)[S], u32 n0inv) {{")
+                   f"        const u32 (&n)[S], {ni}) {{")
         out.append(f'    static_assert(S == {S} && I >= 1 && I < S, "generated for rows 1 .. {S - 1} of {S} limbs");')
     else:
         out.append(f"template <> __device__ __forceinline__ void {name}<{tparams}>(u64 (&P)[{S}], const u32 (&a)[{S}], u32 b{extra},\n"
-                   f"        const u32 (&n)[{S}], u32 n0inv) {{")
+                   f"        const u32 (&n)[{S}], {ni}) {{")
     out.append("    u32 m; u64 c;")
     out.append("    asm volatile(")
     for l in lines:
@@ -127,8 +148,8 @@ def _emit(name: str, S: int, lines, first: bool, sqr: bool, tparams: str, any_ro
     # in a "first" row of a squaring block only the columns that get a product are written before being read
     cons = lambda j: ("=&" if first else "+") + ("{v[%d:%d]}" % (P0REG, P0REG + 1) if j == 0 else "v")
     outs = ", ".join([f'"{cons(j)}"(P[{j}])' for j in range(S)] + ['"=&v"(m)', '"=&v"(c)'])
-    ins = ", ".join([f'"v"(a[{j}])' for j in range(S)] + ['"v"(b)'] + [f'"s"(n[{j}])' for j in range(S)]
-                    + ['"s"(n0inv)'] + (['"v"(b2)'] if sqr else []) + (['"n"(I)'] if any_row else []))
+    ins = ", ".join([f'"v"(a[{j}])' for j in range(S)] + ['"v"(b)'] + [f'"s"(n[{j}])' for j in range(S - 2 if short else S)]
+                    + ([] if short else ['"s"(n0inv)']) + (['"v"(b2)'] if sqr else []) + (['"n"(I)'] if any_row else []))
     out.append(f"        : {outs}")
     out.append(f"        : {ins}")
     out.append('        : "vcc");')
@@ -167,6 +188,17 @@ BITS29 = 29
 # Reliefs sit in front of these rows (row 0 is the "first" row).  S = 71: the static bound is 2^63.954 for a product and 2^63.977
 # for a squaring; of the placements around it only (20, 40) and (21, 40) also stay below 2^64, both within 10^-8 of it.
 RELIEF29 = (21, 41)
+# The short rows (_row, short): for a modulus N = -1 mod 2^58 -- every MODP prime of RFC 2409, 3526 and 7919 ends in 64 one bits --
+# -1/N = 1 mod 2^29 and m * N = m * N'' * 2^58 - m with N'' = (N + 1) >> 58.  The quotient digit is the low limb of column 0 itself,
+# columns 0 and 1 receive no product of the reduction and the columns above receive m * N''[j-2]: S - 2 multiply-adds and three
+# other instructions where the general row has S and five.  The columns hold the same integer (T + M N) / R', so the normalised
+# limbs are those of the general rows.  Fewer terms land in every column: the reliefs stay where they are, and the bound is run.
+SHORT29_ONES = 2 * BITS29                     # trailing one bits of N that the short rows need
+
+
+def short29_modulus(n: int) -> bool:
+    """Whether the short rows reduce by n: its low 58 bits are all ones."""
+    return (n + 1) % (1 << SHORT29_ONES) == 0
 
 
 def relief29_ops(S: int):
@@ -176,31 +208,36 @@ def relief29_ops(S: int):
     return ops
 
 
-def schedule29(S: int, sqr: bool):
-    """The steps of one product (sqr: squaring) in order: ("row", name, tparams, lines, first) or ("relief", ops)."""
+def schedule29(S: int, sqr: bool, short: bool = False):
+    """The steps of one product (sqr: squaring) in order: ("row", name, tparams, lines, first) or ("relief", ops).
+    short: the rows for a modulus of short29_modulus()."""
     steps = []
+    pre = "mont29s" if short else "mont29"
     for i in range(S):
         if i in RELIEF29:
             steps.append(("relief", relief29_ops(S)))
         if sqr:
             if i == 0:
-                steps.append(("row", "mont29_sqr_row_asm_first", f"{S}", _row(S, True, 0, SQR_BLK, BITS29), True))
+                steps.append(("row", pre + "_sqr_row_asm_first", f"{S}", _row(S, True, 0, SQR_BLK, BITS29, short=short), True))
             else:                                     # one text for all of them (_row, any_row); run29 hands it the row
-                steps.append(("row", "mont29_sqr_row_asm", "any", _row(S, False, i, SQR_BLK, BITS29, any_row=True), False))
+                steps.append(("row", pre + "_sqr_row_asm", "any", _row(S, False, i, SQR_BLK, BITS29, any_row=True, short=short), False))
         else:
-            name = "mont29_row_asm_first" if i == 0 else "mont29_row_asm_next"
-            steps.append(("row", name, f"{S}", _row(S, i == 0, bits=BITS29), i == 0))
+            name = pre + ("_row_asm_first" if i == 0 else "_row_asm_next")
+            steps.append(("row", name, f"{S}", _row(S, i == 0, bits=BITS29, short=short), i == 0))
     return steps
 
 
-def run29(S: int, sqr: bool, a, b, n, n0inv, worst: bool = False):
+def run29(S: int, sqr: bool, a, b, n, n0inv, worst: bool = False, short: bool = False):
     """Execute schedule29 on Python integers: a, b, n lists of S limbs (sqr: b is a).  Returns (columns, largest value any
-    64-bit register held before wrap-around).  worst: the quotient digit of every row is 2^29-1 and nothing wraps."""
+    64-bit register held before wrap-around).  worst: the quotient digit of every row is 2^29-1 and nothing wraps.
+    short: the short rows; n is the list of the S - 2 limbs of N'' and n0inv is not read."""
     M64 = (1 << 64) - 1
+    NN = S - 2 if short else S                # modulus operands of a row (_row)
+    assert len(n) == NN
     P = [0] * S
     big = 0
     row = -1
-    for step in schedule29(S, sqr):
+    for step in schedule29(S, sqr, short):
         if step[0] == "relief":
             for dst, src, clear in step[1]:
                 v = P[dst] & 0xffffffff if clear else P[dst]
@@ -229,13 +266,15 @@ def run29(S: int, sqr: bool, a, b, n, n0inv, worst: bool = False):
                 return a[k - S - 2]
             if k == 2 * S + 2:
                 return b[row]
-            if k < 3 * S + 3:
-                return n[k - 2 * S - 3]
-            if k == 3 * S + 3:
+            k -= 2 * S + 3
+            if k < NN:
+                return n[k]
+            k -= NN - short                           # (a short row has no n0inv)
+            if k == 0:
                 return n0inv
-            if k == 3 * S + 4:
+            if k == 1:
                 return b[row] << 1
-            assert k == 3 * S + 5
+            assert k == 2
             return row
 
         def put(tok, v):
@@ -281,9 +320,9 @@ def run29(S: int, sqr: bool, a, b, n, n0inv, worst: bool = False):
     return P, big
 
 
-def static_bound29(S: int, sqr: bool) -> int:
+def static_bound29(S: int, sqr: bool, short: bool = False) -> int:
     top = [(1 << BITS29) - 1] * S
-    return run29(S, sqr, top, top, top, 0, worst=True)[1]
+    return run29(S, sqr, top, top, top[:S - 2] if short else top, 0, worst=True, short=short)[1]
 
 
 def _emit_relief29(S: int) -> str:
@@ -301,21 +340,24 @@ def _emit_relief29(S: int) -> str:
 
 
 def gen29(S: int) -> str:
-    for sqr in (False, True):
-        bound = static_bound29(S, sqr)
+    for sqr, short in ((False, False), (True, False), (False, True), (True, True)):
+        bound = static_bound29(S, sqr, short)
         if bound >= 1 << 64:
             raise SystemExit(f"radix 2^29, S = {S}: reliefs before rows {RELIEF29} let a column reach 2^{bound.bit_length()} "
-                             f"in a {'squaring' if sqr else 'product'}")
+                             f"in a {'squaring' if sqr else 'product'}{' of short rows' if short else ''}")
     parts = [f"// radix 2^29, S = {S} limbs: rows with mask and shift 29, reliefs in front of rows {', '.join(map(str, RELIEF29))}",
              f"template <> struct Relief29<{S}> {{ static constexpr int A = {RELIEF29[0]}, B = {RELIEF29[1]}; }};", ""]
-    seen = set()
-    for sqr in (False, True):
-        for step in schedule29(S, sqr):
-            if step[0] != "row" or (step[1], step[2]) in seen:
-                continue
-            seen.add((step[1], step[2]))
-            parts.append(_emit(step[1], S, step[3], step[4], sqr, step[2], any_row=step[2] == "any"))
+    def rows(short):
+        seen = set()
+        for sqr in (False, True):
+            for step in schedule29(S, sqr, short):
+                if step[0] == "row" and (step[1], step[2]) not in seen:
+                    seen.add((step[1], step[2]))
+                    parts.append(_emit(step[1], S, step[3], step[4], sqr, step[2], any_row=step[2] == "any", short=short))
+    rows(False)
     parts.append(_emit_relief29(S))
+    parts.append(f"// the short rows (N = -1 mod 2^{SHORT29_ONES}): n[] holds the {S - 2} limbs of (N + 1) >> {SHORT29_ONES}; same reliefs")
+    rows(True)
     return "\n".join(parts)
 
 

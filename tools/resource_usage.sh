@@ -4,7 +4,7 @@
 # usage: tools/resource_usage.sh [unit ...]        default: all units
 cd "$(dirname "$0")/.." || exit 1
 out=${TMPDIR:-/tmp}/vmn_resource_usage; mkdir -p "$out"
-units=${*:-vmnhip inst_small inst_2048 inst_2048_wide inst_3072 inst_4096 inst_8192 inst_16384 inst_p224 inst_p256 inst_p384 inst_p521}
+units=${*:-vmnhip inst_small inst_2048 inst_2048_short inst_2048_wide inst_3072 inst_4096 inst_8192 inst_16384 inst_p224 inst_p256 inst_p384 inst_p521}
 for u in $units; do
   /opt/rocm/bin/hipcc -std=c++20 -O3 --offload-arch=gfx950 -fPIC -c verificatum-vmn_amd/csrc/$u.hip -o "$out/$u.o" \
       -Rpass-analysis=kernel-resource-usage 2> "$out/$u.log" &

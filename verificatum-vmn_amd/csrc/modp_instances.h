@@ -81,6 +81,13 @@
     VMN_MODP_INSTANCES(KW, 37, 32, 1) VMN_MEMBER_INSTANCE_ONE_LANE(KW, 10, 1) VMN_MEMBER_INSTANCE_ONE_LANE(KW, 14, 1)     \
     VMN_MEMBER_INSTANCE_ONE_LANE(KW, 19, 1) VMN_MEMBER_INSTANCE_ONE_LANE(KW, 37, 1)
 #define VMN_UNIT_2048(KW) VMN_MODP_INSTANCES(KW, 74, 64, 1) VMN_MEMBER_INSTANCE_ONE_LANE(KW, 74, 1)
+// (the variable-base power kernels of Cfg<74, 1> on the short rows of mont28.h, for moduli N = -1 mod 2^58: a unit of their own)
+#define VMN_UNIT_2048_SHORT(KW)                                                                                        \
+    KW __global__ void vmn::k_modpow<vmn::Cfg<74, 1>, true>(vmn::u32*, const vmn::u32*, const vmn::u32*, int, size_t, int, int, size_t, \
+                                                            const vmn::u32*, vmn::u32, const vmn::u32*, vmn::u32*);                     \
+    KW __global__ void vmn::k_modpow_phased<vmn::Cfg<74, 1>, true>(vmn::u32*, const vmn::u32*, const vmn::u32*, int, size_t, int, int,  \
+                                                                   size_t, const vmn::u32*, vmn::u32, const vmn::u32*, vmn::u32*, int,  \
+                                                                   vmn::u32*, vmn::u32*);
 #define VMN_UNIT_2048_WIDE(KW)                                                                                         \
     VMN_MODP_INSTANCES(KW, 76, 64, 4) VMN_MODP_INSTANCES(KW, 80, 64, 8)                                                \
     KW __global__ void vmn::k_modpow_jobs_mixed<vmn::Cfg<80, 8>, vmn::Cfg<76, 4>>(vmn::ModpowJob, vmn::ModpowJob, unsigned, int,       \

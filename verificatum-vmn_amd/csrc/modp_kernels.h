@@ -69,7 +69,11 @@ struct Cfg {
 // Only registers, the LDS column, the table rows and -- between the phases of the phased kernel -- the running value in out[]
 // hold this form, 71 (stored: 72) of the 76 words of a row; arrays stay in M28 form.  A power enters with one product by
 // c_in = R'^2 / R mod N (x R -> x R') and leaves with one by c_out = R mod N (y R' -> y R).
-struct Cfg29 {
+// SHORT: the same geometry on the short rows of mont28.h, for a modulus N = -1 mod 2^58 (the host decides per modulus and
+// launches k_modpow<C, true> / k_modpow_phased<C, true>); form, constants and results are the same, only the rows differ.
+template <bool SHORT_>
+struct Cfg29T {
+    static constexpr bool SHORT = SHORT_;               // the short rows of mont28.h: the kernel's nn[] holds the limbs of N''
     static constexpr int S = 71, LPE = 1, L = 71, ROWS = 71, BASE_LPE = 1;
     static constexpr bool WIDE = false;
     static constexpr int BASE_L = 71, BASE_LW = stride_for_limbs(71), LW = BASE_LW;
@@ -77,13 +81,20 @@ struct Cfg29 {
     static constexpr int EPB = BLOCK, MINW = 2;
     static constexpr int BITS = 29;
     static __host__ __device__ constexpr int word_of(int g) { return g; }
-    // the constants of a modulus in this form, rows of W words one after the other (the kernels' nmod argument)
-    static constexpr int ROW_N = 0, ROW_ONE = 1, ROW_CIN = 2, ROW_COUT = 3, CONST_ROWS = 4;
+    // the constants of a modulus in this form, rows of W words one after the other (the kernels' nmod argument: ROW_N, or ROW_NS
+    // for the short rows -- N'' = (N + 1) >> 58, all zero where N is not -1 mod 2^58)
+    static constexpr int ROW_N = 0, ROW_ONE = 1, ROW_CIN = 2, ROW_COUT = 3, ROW_NS = 4, CONST_ROWS = 5;
 };
+using Cfg29 = Cfg29T<false>;
+using Cfg29S = Cfg29T<true>;
 static_assert(Cfg29::LW <= Cfg29::W && 29 * Cfg29::S >= 2048 + 2, "71 limbs of 29 bits: a row of Cfg<74, 1>, R' > 4N");
-// PowGeom<C>::type: the geometry k_modpow<C> and k_modpow_phased<C> run in -- C itself, except for Cfg<74, 1>
-template <class C> struct PowGeom { using type = C; };
-template <> struct PowGeom<Cfg<74, 1>> { using type = Cfg29; };
+// PowGeom<C, SHORT>::type: the geometry k_modpow<C, SHORT> and k_modpow_phased<C, SHORT> run in -- C itself, except for Cfg<74, 1>,
+// the only one with short rows
+template <class C, bool SHORT = false> struct PowGeom {
+    static_assert(!SHORT, "short rows: Cfg<74, 1> only");
+    using type = C;
+};
+template <bool SHORT> struct PowGeom<Cfg<74, 1>, SHORT> { using type = Cfg29T<SHORT>; };
 template <class C> constexpr bool POW29 = !__is_same(typename PowGeom<C>::type, C);
 
 // What a lane needs to know about its place: element slot in the workgroup, which half it holds, its
@@ -379,7 +390,7 @@ template <class C>
 __device__ __forceinline__ void mont_mul(u32 (&r)[C::L], const u32 (&a)[C::L], const Lane<C>& ln, const u32 (&n)[C::L], u32 n0inv) {
     u64 T[C::L];
     if constexpr (C::BITS == 29) {
-        mont29_mul_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
+        mont29_mul_columns<C::L, C::SHORT>(T, a, ln.bl, C::EPB, n, n0inv);
     } else if constexpr (C::LPE == 1) {
         mont_mul_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
     } else {
@@ -395,7 +406,7 @@ template <class C>
 __device__ __forceinline__ void mont_sqr(u32 (&r)[C::L], const u32 (&a)[C::L], const Lane<C>& ln, const u32 (&n)[C::L], u32 n0inv) {
     u64 T[C::L];
     if constexpr (C::BITS == 29) {
-        mont29_sqr_columns<C::L>(T, a, n, n0inv);
+        mont29_sqr_columns<C::L, C::SHORT>(T, a, n, n0inv);
     } else if constexpr (C::LPE == 1) {
         mont_sqr_columns<C::L>(T, a, ln.bl, C::EPB, n, n0inv);
     } else {
@@ -790,7 +801,13 @@ __device__ __forceinline__ void pow29_store(u32* __restrict__ dst, u32 (&a)[K::L
     if (finished) {
         const_to_lds<K>(ln, one_m + (Cfg29::ROW_COUT - Cfg29::ROW_ONE) * K::W);
         mont_mul<K>(a, a, ln, nn, n0inv);                          // y R' -> y R
-        canonicalize<K>(a, nn, ln);
+        if constexpr (K::SHORT) {                                  // nn[] is N'': N itself from its row, once per element
+            u32 nfull[K::L];
+            load_modulus<K>(nfull, one_m + (Cfg29::ROW_N - Cfg29::ROW_ONE) * K::W, ln);
+            canonicalize<K>(a, nfull, ln);
+        } else {
+            canonicalize<K>(a, nn, ln);
+        }
         u32 y[C::L];
         repack_limbs<C::L, C::BITS, K::L, K::BITS>(y, a);
         if (live) store_elem<C>(dst, y, Lane<C>(ln.bl - ln.eslot));
@@ -862,12 +879,12 @@ private:
     __device__ __forceinline__ void fetch() { *s_unit = atomicAdd(queue, 1u); }     // (thread 0 only)
 };
 
-template <class C>
+template <class C, bool SHORT = false>
 __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e, int ewords, size_t estride,
          int ebits, int wbits, size_t n, const u32* __restrict__ nmod, u32 n0inv, const u32* __restrict__ one_m,
          u32* __restrict__ tab) {
-    using K = typename PowGeom<C>::type;                 // (Cfg29: nmod, n0inv and one_m are that form's)
+    using K = typename PowGeom<C, SHORT>::type;          // (Cfg29: nmod, n0inv and one_m are that form's; SHORT: nmod is N'')
     constexpr int W = C::W;
     extern __shared__ u32 lds[];
     Lane<K> ln(lds);
@@ -899,12 +916,12 @@ k_modpow(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict
 
 // k_modpow for arrays of MORE than one round of tiles, in phases from a queue of (phase, tile) units (UnitQueue has the
 // reasons).  Same products in the same order as k_modpow: bit-identical results.
-template <class C>
+template <class C, bool SHORT = false>
 __global__ void __launch_bounds__(BLOCK, C::MINW)
 k_modpow_phased(u32* __restrict__ out, const u32* __restrict__ x, const u32* __restrict__ e, int ewords, size_t estride,
                 int ebits, int wbits, size_t n, const u32* __restrict__ nmod, u32 n0inv, const u32* __restrict__ one_m,
                 u32* __restrict__ tab, int phases, u32* __restrict__ queue, u32* __restrict__ done) {
-    using K = typename PowGeom<C>::type;                 // (Cfg29: nmod, n0inv and one_m are that form's; so are the table and,
+    using K = typename PowGeom<C, SHORT>::type;          // (Cfg29: nmod, n0inv and one_m are that form's; so are the table and,
     constexpr int W = C::W;                              // between a tile's phases, its running value in out[])
     extern __shared__ u32 lds[];
     __shared__ u32 s_unit;

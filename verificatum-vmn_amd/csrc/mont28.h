@@ -74,6 +74,14 @@ template <int S> __device__ __forceinline__ void mont29_sqr_row_asm_first(u64 (&
 // (rows 1 .. S-1 of a squaring: ONE text, the row is an immediate operand and assembler conditionals leave out the products it skips)
 template <int S, int I> __device__ __forceinline__ void mont29_sqr_row_asm(u64 (&P)[S], const u32 (&a)[S], u32 b, u32 b2, const u32 (&n)[S], u32 n0inv);
 template <int S> __device__ __forceinline__ void mont29_relieve(u64 (&P)[S]);
+// The SHORT rows, for a modulus N = -1 mod 2^58 (the MODP primes of RFC 2409, 3526 and 7919 end in 64 one bits): -1/N = 1 mod 2^29,
+// so the quotient digit is the low limb of column 0, and m N = m N'' 2^58 - m with N'' = (N + 1) >> 58 puts nothing but a carry into
+// columns 0 and 1.  n[] holds the S - 2 limbs of N'' (n[S-2], n[S-1] and the last argument are not read): S - 2 multiply-adds and
+// three other instructions in the reduction half of a row where the general rows have S and five.  Same columns' VALUE, same reliefs.
+template <int S> __device__ __forceinline__ void mont29s_row_asm_first(u64 (&P)[S], const u32 (&a)[S], u32 b, const u32 (&n)[S], u32);
+template <int S> __device__ __forceinline__ void mont29s_row_asm_next(u64 (&P)[S], const u32 (&a)[S], u32 b, const u32 (&n)[S], u32);
+template <int S> __device__ __forceinline__ void mont29s_sqr_row_asm_first(u64 (&P)[S], const u32 (&a)[S], u32 b, u32 b2, const u32 (&n)[S], u32);
+template <int S, int I> __device__ __forceinline__ void mont29s_sqr_row_asm(u64 (&P)[S], const u32 (&a)[S], u32 b, u32 b2, const u32 (&n)[S], u32);
 #include "gen/mont29_rows.inc"
 
 // T (S lazy columns, value < 2N when a, b < 2N and R > 4N) = a * b / R mod N.
@@ -121,45 +129,49 @@ __device__ __forceinline__ void mont_sqr_columns(u64 (&T)[S], const u32 (&a)[S],
 }
 
 // The same two drivers on limbs of 29 bits: T = a * b / R' resp. a * a / R' mod N, R' = 2^(29 S); rows i0 .. i1-1, then the
-// relief that precedes row i1.
-template <int S>
+// relief that precedes row i1.  SHORT: the short rows (n[] = the limbs of N'', see above).
+template <int S, bool SHORT>
 __device__ __forceinline__ void mont29_mul_rows(u64 (&T)[S], const u32 (&a)[S], const u32* b_lds, int bstride, const u32 (&n)[S],
                                                 u32 n0inv, u32& bn, int i0, int i1) {
 #pragma unroll 2
     for (int i = i0; i < i1; ++i) {
         u32 bi = bn;
         bn = b_lds[(i + 1 < S ? i + 1 : 0) * bstride];            // prefetch the next row's limb under this row
-        mont29_row_asm_next<S>(T, a, bi, n, n0inv);
+        if constexpr (SHORT) mont29s_row_asm_next<S>(T, a, bi, n, n0inv);
+        else mont29_row_asm_next<S>(T, a, bi, n, n0inv);
     }
 }
-template <int S>
+template <int S, bool SHORT>
 __device__ __forceinline__ void mont29_mul_columns(u64 (&T)[S], const u32 (&a)[S], const u32* b_lds, int bstride,
                                                    const u32 (&n)[S], u32 n0inv) {
     constexpr int A = Relief29<S>::A, B = Relief29<S>::B;
     static_assert(0 < A && A < B && B < S, "reliefs between rows");
     u32 b0 = b_lds[0];
     u32 bn = b_lds[bstride];
-    mont29_row_asm_first<S>(T, a, b0, n, n0inv);
-    mont29_mul_rows<S>(T, a, b_lds, bstride, n, n0inv, bn, 1, A);
+    if constexpr (SHORT) mont29s_row_asm_first<S>(T, a, b0, n, n0inv);
+    else mont29_row_asm_first<S>(T, a, b0, n, n0inv);
+    mont29_mul_rows<S, SHORT>(T, a, b_lds, bstride, n, n0inv, bn, 1, A);
     mont29_relieve<S>(T);
-    mont29_mul_rows<S>(T, a, b_lds, bstride, n, n0inv, bn, A, B);
+    mont29_mul_rows<S, SHORT>(T, a, b_lds, bstride, n, n0inv, bn, A, B);
     mont29_relieve<S>(T);
-    mont29_mul_rows<S>(T, a, b_lds, bstride, n, n0inv, bn, B, S);
+    mont29_mul_rows<S, SHORT>(T, a, b_lds, bstride, n, n0inv, bn, B, S);
     T[S - 1] = 0;
 }
 // A squaring takes row I's multiplier limb from its register: the rows are unrolled by recursion, so a[I] is a static index and
 // nothing goes through LDS.  (a[I] is then two inputs of the row's statement, as a[I] and as b; m and c are early-clobber
 // outputs and get registers of their own.)
-template <int S, int I>
+template <int S, bool SHORT, int I>
 __device__ __forceinline__ void mont29_sqr_rows(u64 (&T)[S], const u32 (&a)[S], const u32 (&n)[S], u32 n0inv) {
     if constexpr (I == Relief29<S>::A || I == Relief29<S>::B) mont29_relieve<S>(T);
-    mont29_sqr_row_asm<S, I>(T, a, a[I], a[I] << 1, n, n0inv);
-    if constexpr (I + 1 < S) mont29_sqr_rows<S, I + 1>(T, a, n, n0inv);
+    if constexpr (SHORT) mont29s_sqr_row_asm<S, I>(T, a, a[I], a[I] << 1, n, n0inv);
+    else mont29_sqr_row_asm<S, I>(T, a, a[I], a[I] << 1, n, n0inv);
+    if constexpr (I + 1 < S) mont29_sqr_rows<S, SHORT, I + 1>(T, a, n, n0inv);
 }
-template <int S>
+template <int S, bool SHORT>
 __device__ __forceinline__ void mont29_sqr_columns(u64 (&T)[S], const u32 (&a)[S], const u32 (&n)[S], u32 n0inv) {
-    mont29_sqr_row_asm_first<S>(T, a, a[0], a[0] << 1, n, n0inv);
-    mont29_sqr_rows<S, 1>(T, a, n, n0inv);
+    if constexpr (SHORT) mont29s_sqr_row_asm_first<S>(T, a, a[0], a[0] << 1, n, n0inv);
+    else mont29_sqr_row_asm_first<S>(T, a, a[0], a[0] << 1, n, n0inv);
+    mont29_sqr_rows<S, SHORT, 1>(T, a, n, n0inv);
     T[S - 1] = 0;
 }
 

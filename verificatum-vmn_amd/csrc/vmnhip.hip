@@ -24,6 +24,7 @@
 // the Cfg-templated kernels are compiled in the instantiation units csrc/inst_*.hip (modp_instances.h); here they are declared
 VMN_UNIT_SMALL(extern template)
 VMN_UNIT_2048(extern template)
+VMN_UNIT_2048_SHORT(extern template)
 VMN_UNIT_2048_WIDE(extern template)
 VMN_UNIT_3072(extern template)
 VMN_UNIT_4096(extern template)
@@ -861,6 +862,20 @@ static int modulus_init(vmn_ctx* ctx, vmn_modulus& m, const uint8_t* be, size_t 
         put(Cfg29::ROW_CIN, hostbig::pow2_mod(2 * B9 * S9 - 28 * S, m.n_words));
         put(Cfg29::ROW_COUT, r);
         m.n0inv29 = hostbig::neg_inv_pow2(m.n_words[0] & ((1u << B9) - 1), B9);
+        // the short rows: N = -1 mod 2^(2*29), detected per modulus (NW = 64 words: the low 58 bits lie in words 0 and 1)
+        m.pow29_short = m.n_words[0] == 0xffffffffu && (m.n_words[1] & 0x3ffffffu) == 0x3ffffffu;
+        if (m.pow29_short) {
+            Big t(NW + 1, 0), ns(NW, 0);                            // N + 1 (2^2048 - 1 carries into a word more), then >> 58
+            uint64_t carry = 1;
+            for (int i = 0; i < NW; ++i) {
+                carry += m.n_words[i];
+                t[i] = (uint32_t)carry;
+                carry >>= 32;
+            }
+            t[NW] = (uint32_t)carry;
+            for (int i = 0; i < NW; ++i) ns[i] = (t[i + 1] >> 26) | (i + 2 <= NW ? t[i + 2] << 6 : 0u);     // one word and 26 bits
+            put(Cfg29::ROW_NS, ns);
+        }
         VMN_TRY(upload_words(ctx, &m.d_pow29, rows));
     }
     m.hm = new hostbig::Mont(m.n_words);
@@ -1724,19 +1739,32 @@ static int modpow_words(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* x, 
     VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)1 << wbits)));
     note_work(ctx, m, (double)n * (nwin - 1 + (1 << wbits) - 2), (double)n * (nwin - 1) * wbits);
     const bool pow29 = m.S == 74 && m.LPE == 1;            // POW29<Cfg<74, 1>>: the kernels work on 71 limbs of 29 bits
+    // ... and by the short rows where the modulus allows them.  VMN_POW29_SHORT=0: the general rows, to measure and to test (read
+    // per call like VMN_MODPOW_MAX_BLOCKS: the tests run both families in one process)
+    const char* short_env = getenv("VMN_POW29_SHORT");
+    const bool pow29_short = pow29 && m.pow29_short && !(short_env && *short_env && atoi(short_env) == 0);
     if (pow29 && ctx->timing) {
         // the multiply-adds of those rows: the same products and squarings, the two products that change the domain, and in
         // each of them two reliefs of S - 2 multiply-adds
-        const double S9 = Cfg29::S, relief = 2 * (S9 - 2);
-        ctx->next_mads = (double)n * ((nwin - 1 + (1 << wbits) - 2 + 2) * (2 * S9 * S9 + relief) +
-                                      (double)(nwin - 1) * wbits * (S9 * S9 + S9 * (S9 + SQR_BLK) / 2 + relief));
+        // (the short rows reduce a row with S - 2 of them)
+        const double S9 = Cfg29::S, relief = 2 * (S9 - 2), red = S9 * (pow29_short ? S9 - 2 : S9);
+        ctx->next_mads = (double)n * ((nwin - 1 + (1 << wbits) - 2 + 2) * (S9 * S9 + red + relief) +
+                                      (double)(nwin - 1) * wbits * (red + S9 * (S9 + SQR_BLK) / 2 + relief));
     }
     VMN_TRY(pl.split(ctx, m, nwin - 1, (size_t)1 << wbits));
     // (those kernels take the modulus, -1/N and 1 in their own form)
     static_assert(POW29<Cfg<74, 1>>, "modpow_words passes the 29-bit constants to the kernels of Cfg<74, 1>");
-    const uint32_t* d_n = pow29 ? m.d_pow29 + (size_t)Cfg29::ROW_N * Cfg29::W : m.d_n;
+    const uint32_t* d_n = pow29 ? m.d_pow29 + (size_t)(pow29_short ? Cfg29::ROW_NS : Cfg29::ROW_N) * Cfg29::W : m.d_n;
     const uint32_t* d_one = pow29 ? m.d_pow29 + (size_t)Cfg29::ROW_ONE * Cfg29::W : m.d_one;
     const uint32_t n0inv = pow29 ? m.n0inv29 : m.n0inv;
+    if (pow29_short) {
+        using C = Cfg<74, 1>;
+        if (pl.phases > 1)
+            return launch(ctx, "modpow", k_modpow_phased<C, true>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, estride, ebits,
+                          wbits, n, d_n, n0inv, d_one, pl.table(), pl.phases, pl.queue(), pl.done());
+        return launch(ctx, "modpow", k_modpow<C, true>, pl.grid, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, n, d_n,
+                      n0inv, d_one, reinterpret_cast<uint32_t*>(ctx->scratch));
+    }
     return with_cfg(m, [&]<class C, class W>(C, W) {
         if (pl.phases > 1)
             return launch(ctx, "modpow", k_modpow_phased<C>, pl.max_blocks, lds_bytes(m), out, x, e_words, ewords, estride, ebits, wbits, n,

@@ -164,9 +164,10 @@ struct vmn_modulus {
     uint32_t* d_rr = nullptr;  // R^2 mod N as a row, R = 2^(28 S)
     uint32_t* d_one = nullptr; // R mod N as a row == Montgomery form of 1
     // Cfg<74, 1> only: the constants of the variable-base power kernels, which work on 71 limbs of 29 bits (Cfg29 of
-    // modp_kernels.h) -- Cfg29::CONST_ROWS rows of W words in that form: N, R' mod N, c_in and c_out
+    // modp_kernels.h) -- Cfg29::CONST_ROWS rows of W words in that form: N, R' mod N, c_in, c_out and N'' = (N + 1) >> 58
     uint32_t* d_pow29 = nullptr;
     uint32_t n0inv29 = 0;      // -N^{-1} mod 2^29
+    bool pow29_short = false;  // N = -1 mod 2^58: those kernels reduce by the short rows (mont28.h), with N'' for N
     vmn::hostbig::Big n_words; // NW words
     vmn::hostbig::Mont* hm = nullptr;     // host Montgomery context (32-bit words, R = 2^(32 NW))
     vmn::num64::Mod* hm64 = nullptr;      // the same on 64-bit limbs (the sequential tails: Horner of a multi-exponentiation)
