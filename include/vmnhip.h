@@ -232,6 +232,20 @@ int vmn_garray_expprod_multi_begin(const vmn_garray* const* xs, size_t k, const 
 int vmn_pending_finish(vmn_pending* p, uint8_t* out_be);
 size_t vmn_pending_bytes(const vmn_pending* p);   /* what finish writes: k elements */
 void vmn_pending_free(vmn_pending* p);
+/* K3'  pGroup.expProd(bases[], integers[], bitLength): out[i] = prod_j xs[j][i]^(c_j), c_j = (negative[j] ? -1 : 1) * abs_j, the
+ * c_j the same for every position.  ref: P/elgamal/DistrElGamalSessionBasic.java:465-503 (the modified Lagrange integers of
+ * combineDecryptionFactors); with the second ciphertext components v as one more base under exponent 1 the same call recovers
+ * the plaintexts, v * prod_j f_j^(lambda_j) (P/mixnet/MixNetElGamalVerifyFiatShamirSession.java:1268-1273).
+ * abs_be: k rows of ebytes big-endian bytes (the layout vmn_lagrange_coefficients writes); bitlen = bound on bits(abs_j),
+ * 0 = 8*ebytes.  The integers are not reduced modulo the group order by the caller (over a curve the library reduces them).
+ * One chain of squarings (doublings) serves all bases, up to eight bases per launch; over a modular group the positive and the
+ * negative part are two products of one launch and the negative one goes through vmn_garray_inv, over a curve a negative
+ * coefficient negates its base.  The result is bit for bit what vmn_garray_exp_scalar, _mul and _inv give.  An exponent 0 drops
+ * its base; all exponents 0: the array of ones (of infinity).  The same array may appear more than once.  k = 0, arrays of two
+ * groups or sizes, an abs_j of more than bitlen bits, bitlen > 8*ebytes, over a modular group arrays of 2^31 elements or more:
+ * VMN_ERR_ARG, *out is not written. */
+int vmn_garray_expprod_arrays(const vmn_garray* const* xs, size_t k, const uint8_t* abs_be, size_t ebytes, const int* negative,
+                              int bitlen, vmn_garray** out);
 /* K4  X.mul(Y).  ref: P/mixnet/ShufflerElGamalSession.java:273, 789, 850 (the re-encryption);
  * P/hvzk/PoSBasicTW.java:448, 610, 648, 1029, 1033. */
 int vmn_garray_mul(const vmn_garray* x, const vmn_garray* y, vmn_garray** out);

@@ -62,6 +62,32 @@ public final class GPUGroup implements AutoCloseable {
         VMNException.check(VMNHip.vmn_group_precompute_fixed(grp, encode(base), nHint, usesHint));
     }
 
+    /** {@code pGroup.expProd(bases, integers, bitLength)}: out[i] = prod_j bases[j][i]^(integers[j]) with signed integers that are
+     *  the same for every position (the modified Lagrange integers of DistrElGamalSessionBasic.combineDecryptionFactors,
+     *  elgamal/DistrElGamalSessionBasic.java:465-503), one chain of squarings for all bases: vmn_garray_expprod_arrays. */
+    public PGroupElementArrayGPU expProd(final PGroupElementArrayGPU[] bases, final LargeInteger[] integers, final int bitLength) {
+        final int k = bases.length;
+        if (integers.length != k) {
+            throw new VMNException(VMNException.ERR_ARG);
+        }
+        // rows as wide as the widest integer: one that is longer than bitLength reaches the library whole and is refused there
+        int ebytes = Math.max(1, (bitLength + 7) / 8);
+        for (final LargeInteger c : integers) {
+            ebytes = Math.max(ebytes, (c.abs().bitLength() + 7) / 8);
+        }
+        final long[] xs = new long[k];
+        final byte[] abs = new byte[k * ebytes];
+        final int[] negative = new int[k];
+        for (int j = 0; j < k; ++j) {
+            xs[j] = bases[j].handle;
+            negative[j] = integers[j].compareTo(LargeInteger.ZERO) < 0 ? 1 : 0;
+            System.arraycopy(fixed(integers[j].abs(), ebytes), 0, abs, j * ebytes, ebytes);
+        }
+        final long[] out = new long[1];
+        VMNException.check(VMNHip.vmn_garray_expprod_arrays(xs, k, abs, ebytes, negative, bitLength, out));
+        return new PGroupElementArrayGPU(this, out[0]);
+    }
+
     @Override
     public void close() {
         VMNHip.vmn_group_destroy(grp);

@@ -209,7 +209,7 @@ def need_expr(name, ptype, pname, plist):
         if pname == "layout":
             return "(size_t)items"
         if pname == "negative":
-            return "(size_t)threshold"
+            return "(size_t)k" if name == "vmn_garray_expprod_arrays" else "(size_t)threshold"
         if pname == "verdicts5":
             return "5"
         if pname == "pi_out":
@@ -285,6 +285,8 @@ def need_expr(name, ptype, pname, plist):
             return f"vmn_decproof_width({pobj}) * {EB}"
         if pname == "y_be" and name in ("vmn_decproof_set_instance", "vmn_decproof_set_instance_wide"):
             return f"((size_t)vmn_decproof_parties({pobj}) + 1) * {EB}"
+        if pname == "abs_be" and name == "vmn_garray_expprod_arrays":         # a row per array
+            return "(size_t)k * (size_t)ebytes"
         if pname == "abs_be":
             return f"(size_t)threshold * {XB}"
         if pname == "out_be" and name == "vmn_rarray_inner_products":

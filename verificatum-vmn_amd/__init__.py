@@ -343,6 +343,23 @@ class ModPGroup:
             raise ValueError("ArithmFormatException: element out of range")
         return arr
 
+    def expProd(self, bases, integers, bitLength: int = 0) -> "PGroupElementArray":
+        """``pGroup.expProd(bases[], integers[], bitLength)`` (``vmn_garray_expprod_arrays``): ``out[i] = prod_j bases[j][i]^integers[j]``
+        for arrays of this group and one size under signed Python integers, the same for every position, with one chain of
+        squarings for all bases.  ``bitLength`` bounds the integers' absolute values (0: their own width).  Plaintext recovery is
+        the same call with ``v`` as one more base under the integer 1."""
+        k = len(bases)
+        if k == 0 or len(integers) != k:
+            raise ValueError("expProd needs at least one array and one integer per array")
+        ints = [int(c) for c in integers]
+        nb = max(1, (bitLength + 7) // 8, max((abs(c).bit_length() + 7) // 8 for c in ints))
+        hs = (C.c_void_p * k)(*[a._h for a in bases])
+        neg = (C.c_int * k)(*[1 if c < 0 else 0 for c in ints])
+        h = C.c_void_p()
+        _check(lib().vmn_garray_expprod_arrays(hs, C.c_size_t(k), b"".join(int_to_be(abs(c), nb) for c in ints), C.c_size_t(nb), neg,
+                                               C.c_int(bitLength), C.byref(h)))
+        return PGroupElementArray(self, h)
+
     def toElementArrayFromByteTree(self, bt: bytes, size: int = 0) -> "PGroupElementArray":
         """``pGroup.toElementArray(size, byteTreeReader)`` (size 0 = any), the reference's wire format."""
         return self._from_bytetree("vmn_garray_from_bytetree", PGroupElementArray, bt, size)

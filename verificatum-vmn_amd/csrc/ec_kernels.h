@@ -20,6 +20,7 @@
 // and handled exactly (rare wave-divergent path), so every result is the true group element.
 #pragma once
 #include "modp_kernels.h"
+#include "modp_shared_exp.h"      // SlideStep and the table groups of k_ec_expprod
 
 namespace vmn {
 
@@ -1176,6 +1177,86 @@ __global__ void __launch_bounds__(BLOCK, ECfg<S>::MINW) k_ec_mulvar2(u32* __rest
             pt_load<S>(T, ty + (size_t)df * ROW);                    // entry 0 is the identity: no branch per lane
             pt_add<S, KIND>(A, A, T, E);
         }
+        if (live) pt_store<S>(out + el * ROW, A);
+    }
+}
+
+// K3' over arrays: out[i] = sum_j c_j * x_j[i], the c_j the same for every point (pGroup.expProd(bases[], integers[], bitLength),
+// elgamal/DistrElGamalSessionBasic.java:465-503), as ONE chain of doublings for all bases.  The per-lane table in scratch holds,
+// for every group of up to EXPPROD_GROUP bases, the sums of its subsets (rows as in k_modpow_expprod, modp_shared_exp.h); a base
+// whose coefficient is negative (bit j of `negmask`) enters the table as -x_j, so signs cost one field negation per base and no
+// second pass.  The schedule is the host's list of SlideStep: `sq` doublings, then the addition of table row `idx`.  The subset
+// sums go through pt_add like every other sum, which is exact where two bases hold the same point, opposite points or infinity.
+struct ECExpProdArrays {
+    const u32* x[EXPPROD_BASES];
+    int nb;                  // bases of the launch
+    u32 negmask;
+    int trows;               // table rows per lane: EXPPROD_GROUP_ROWS per group
+};
+// (waves per SIMD: with the general formulas over a 10-limb field the kernel needs 38 registers more than two waves leave it,
+// with the run-time prime of the 9-limb NIST fields two more -- one wave there, as above 10 limbs)
+template <int S, int KIND>
+constexpr int EC_EXPPROD_MINW = (S == 10 && KIND == EC_GENERAL) || (S == 9 && KIND == EC_NIST) ? 1 : ECfg<S>::MINW;
+template <int S, int KIND = EC_NIST>
+__global__ void __launch_bounds__(BLOCK, (EC_EXPPROD_MINW<S, KIND>)) k_ec_expprod(u32* __restrict__ out, ECExpProdArrays arrs, const SlideStep* __restrict__ steps,
+                                                      int nsteps, size_t n, ECDev E, u32* tab) {
+    constexpr int ROW = ECfg<S>::ROW;
+    const size_t ntiles = (n + BLOCK - 1) / BLOCK;
+    u32* mytab = tab + ((size_t)blockIdx.x * BLOCK + threadIdx.x) * (size_t)arrs.trows * ROW;
+    for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        size_t el = t * BLOCK + threadIdx.x;
+        bool live = el < n;
+        size_t ec = live ? el : n - 1;
+        // ONE loop over the rows of the table and then the steps of the schedule, so that the addition and the doubling are
+        // laid out once: a table row is (the row without its lowest base) + (that base), a step is doublings and (row idx)
+        const int trows = arrs.trows;
+        Pt<S> A, T;
+#pragma unroll 1
+        for (int it = 0; it < trows + nsteps - 1; ++it) {
+            const bool build = it < trows;                               // (wave-uniform, like everything that steers this loop)
+            bool add = true, keep = false;
+            const u32* src;
+            if (build) {
+                const int g = it / EXPPROD_GROUP_ROWS, g0 = g * EXPPROD_GROUP;
+                const u32 mask = (u32)(it - g * EXPPROD_GROUP_ROWS) + 1;
+                const int gs = arrs.nb - g0 < EXPPROD_GROUP ? arrs.nb - g0 : EXPPROD_GROUP;
+                if (mask >= (1u << gs)) continue;                        // (a last group of fewer bases)
+                const u32* gt = mytab + (size_t)g0 / EXPPROD_GROUP * EXPPROD_GROUP_ROWS * ROW;
+                const u32 low = mask & (0u - mask), rest = mask ^ low;
+                keep = true;
+                if (rest == 0) {
+                    const int j = g0 + (__ffs(low) - 1);
+                    pt_load<S>(A, arrs.x[j] + ec * ROW);
+                    if ((arrs.negmask >> j) & 1u) {
+                        u32 z[S], y[S];
+#pragma unroll
+                        for (int i = 0; i < S; ++i) z[i] = 0;
+                        f_sub<S, true>(y, z, A.Y, E);
+#pragma unroll
+                        for (int i = 0; i < S; ++i) A.Y[i] = y[i];
+                    }
+                    add = false;
+                    src = gt;
+                } else {
+                    pt_load<S>(A, gt + (size_t)(rest - 1) * ROW);
+                    src = gt + (size_t)(low - 1) * ROW;
+                }
+            } else {
+                const int s = it - trows + 1;
+                const int sq = steps[s].sq, idx = steps[s].idx;
+                if (s == 1) pt_load<S>(A, mytab + (size_t)steps[0].idx * ROW);
+#pragma unroll 1
+                for (int d = 0; d < sq; ++d) pt_dbl<S, KIND>(A, A, E);
+                add = idx >= 0;
+                src = mytab + (size_t)(idx >= 0 ? idx : 0) * ROW;
+            }
+            if (add) {
+                pt_load<S>(T, src);
+                pt_add<S, KIND>(A, A, T, E);
+            }
+            if (keep) pt_store<S>(mytab + (size_t)it * ROW, A);
+        }
+        if (nsteps == 1) pt_load<S>(A, mytab + (size_t)steps[0].idx * ROW);
         if (live) pt_store<S>(out + el * ROW, A);
     }
 }

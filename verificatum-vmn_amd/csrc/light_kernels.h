@@ -87,6 +87,19 @@ __global__ void __launch_bounds__(BLOCK) k_gather(uint4* __restrict__ out, const
     }
 }
 
+// out[i] = fill for every row i < n_out (the array of ones resp. of infinity): one thread per 16-byte chunk, as k_gather
+__global__ void __launch_bounds__(BLOCK) k_fill_rows(uint4* __restrict__ out, const uint4* __restrict__ fill, size_t n_out,
+                                                     int chunks_per_row) {
+    size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    size_t total = n_out * (size_t)chunks_per_row;
+    for (; t < total; t += (size_t)gridDim.x * BLOCK) {
+        size_t row;
+        int c;
+        split_chunk(t, chunks_per_row, row, c);
+        out[t] = fill[c];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // K2 fixed base.  Table T[k][d] = base^(d * 2^(w*k)), k < nwin, d < 2^w, rows of W words at
 // (k*2^w + d)*W.  The host supplies sq[j] = base^(2^j) (the sequential squaring chain); level l

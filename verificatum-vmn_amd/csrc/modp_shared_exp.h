@@ -1,6 +1,7 @@
 // modp_shared_exp.h — variants of K1 beside k_modpow: ONE exponent for the whole array (out[i] = x[i]^e, sliding window), for one
 // array or for several arrays of one size in one launch (all under one exponent, or each array under its own), and two
-// independent exponentiations of small arrays in one launch (k_modpow_jobs, at the end).
+// independent exponentiations of small arrays in one launch (k_modpow_jobs, at the end); and the product of several arrays'
+// powers under one exponent each with ONE chain of squarings (k_modpow_expprod).
 //
 // The reference raises whole arrays to a single exponent in the decryption half of the mix-net -- the decryption factors
 // f = u^(-x_j / c), a full-length secret exponent per party (elgamal/DistrElGamalSession.java:365-385) -- and in the
@@ -207,6 +208,90 @@ k_modpow_shared_each_phased(EachArrays arrs, u32 ntiles, u32 total, const SlideS
     extern __shared__ u32 lds[];
     __shared__ u32 s_unit;
     modpow_shared_units<C>(arrs, ntiles, total, steps, 0, tsize, n, nmod, n0inv, tab, phases, queue, done, &s_unit, lds);
+}
+
+// K3' over arrays: out[i] = prod_j x_j[i]^(c_j), the c_j the same for every element (pGroup.expProd(bases[], integers[],
+// bitLength), elgamal/DistrElGamalSessionBasic.java:465-503).  ONE chain of squarings for all bases (Straus): the bases of a
+// product are cut into groups of up to EXPPROD_GROUP, a lane's table holds for every group the 2^g - 1 products of its subsets
+// (row (mask - 1) of the group's EXPPROD_GROUP_ROWS rows = the product of the bases whose bit is set in `mask`; one product per
+// row: the row without the lowest base, times that base), and the host's schedule is a list of SlideStep as above -- `sq`
+// squarings, then the product by the table row `idx` that a column of exponent bits selects (expprod_schedule.h).
+//
+// A launch computes up to two products over the SAME input arrays, the positive and the negative part of a signed exponent
+// vector, as the tiles of two "arrays" with a schedule each, exactly as EachArrays does: global tile T belongs to product
+// T / ntiles.  (Two accumulators in one lane do not fit: the one-lane 2048-bit kernels already sit at ~245 VGPRs.)  The host
+// inverts the negative product with the batched inversion and multiplies.
+//
+// EXPPROD_BASES, the bases of one launch: two groups of four = 30 table rows per lane slot, half of the 64 rows the sliding
+// window of a 2048-bit exponent takes (w = 7), so the launch never asks for more scratch than k_modpow_shared does; every further
+// group adds up to one product per exponent bit, the same as a launch of its own would, while a launch of its own has the
+// squarings and the tail again -- which for the few-bit Lagrange integers this serves costs less than a 45-row table per slot
+// costs every tile.  Beyond the limit the host multiplies the launches' results.
+constexpr int EXPPROD_GROUP = 4;
+constexpr int EXPPROD_GROUP_ROWS = (1 << EXPPROD_GROUP) - 1;
+constexpr int EXPPROD_BASES = 8;
+constexpr int EXPPROD_ROWS = EXPPROD_BASES / EXPPROD_GROUP * EXPPROD_GROUP_ROWS;
+struct ExpProdArrays {
+    const u32* x[EXPPROD_BASES];              // the launch's input arrays
+    u32* out[2];                              // the two products
+    u32 first[2];                             // product s walks count[s] steps from steps[first[s]] on
+    int count[2];
+    int nb[2];                                // bases of product s: x[base[s][0 .. nb[s] - 1]], in groups of EXPPROD_GROUP
+    unsigned char base[2][EXPPROD_BASES];
+    int trows;                                // table rows per lane slot: EXPPROD_GROUP_ROWS per group of the longer product
+};
+// the joint table of product s of the element at index ec, into tb (a: work registers)
+template <class C>
+__device__ __forceinline__ void subset_product_table(u32 (&a)[C::L], u32* tb, const ExpProdArrays& arrs, u32 s, size_t ec, const Lane<C>& ln,
+                                                     const u32 (&nn)[C::L], u32 n0inv) {
+    constexpr int W = C::W;
+    const int nb = arrs.nb[s];
+#pragma unroll 1
+    for (int g0 = 0; g0 < nb; g0 += EXPPROD_GROUP) {
+        u32* gt = tb + (size_t)(g0 / EXPPROD_GROUP * EXPPROD_GROUP_ROWS) * W;
+        const int gs = nb - g0 < EXPPROD_GROUP ? nb - g0 : EXPPROD_GROUP;
+#pragma unroll 1
+        for (u32 mask = 1; mask < (1u << gs); ++mask) {
+            const u32 low = mask & (0u - mask), rest = mask ^ low;
+            if (rest == 0) {
+                load_elem<C>(a, arrs.x[arrs.base[s][g0 + (__ffs(low) - 1)]] + ec * W, ln);
+            } else {
+                load_elem<C>(a, gt + (size_t)(rest - 1) * W, ln);
+                mul_by_row<C>(a, gt + (size_t)(low - 1) * W, ln, nn, n0inv);
+            }
+            store_elem<C>(gt + (size_t)(mask - 1) * W, a, ln);
+        }
+    }
+}
+// `total` global tiles, `ntiles` per product of n elements; a table of arrs.trows rows per lane slot in `tab`
+template <class C>
+__global__ void __launch_bounds__(BLOCK, C::MINW)
+k_modpow_expprod(ExpProdArrays arrs, u32 ntiles, u32 total, const SlideStep* __restrict__ steps, u32 n32, const u32* __restrict__ nmod,
+                 u32 n0inv, u32* tab) {
+    extern __shared__ u32 lds[];
+    constexpr int W = C::W;
+    Lane<C> ln(lds);
+    u32 nn[C::L];
+    load_modulus<C>(nn, nmod, ln);
+    u32* mytab = tab + ((size_t)blockIdx.x * C::EPB + ln.eslot) * (size_t)arrs.trows * W;
+    // 32-bit tile and element indices (n32 elements per product): the host keeps n below 2^31, hence `total` below 2^29, so
+    // T + gridDim.x and a ragged tile's indices cannot wrap.  In Cfg<74, 1> the 74 limbs of the modulus live in scalar registers,
+    // and every scalar held across the loop of steps is one they need: 64-bit counters, a division for the product's number and
+    // an output pointer looked up in front of the loop cost 8 spilled SGPRs, this form none.
+    for (u32 T = blockIdx.x; T < total; T += gridDim.x) {
+        const u32 s = T >= ntiles ? 1u : 0u;                   // (block-uniform; a launch has at most two products)
+        const u32 t = s ? T - ntiles : T;
+        const SlideStep* __restrict__ st = steps + arrs.first[s];
+        const u32 el = t * C::EPB + ln.eslot;
+        const size_t ec = el < n32 ? el : n32 - 1;
+        u32 a[C::L];
+        subset_product_table<C>(a, mytab, arrs, s, ec, ln, nn, n0inv);
+        load_elem<C>(a, mytab + (size_t)st[0].idx * W, ln);
+        slide_steps<C>(a, st, 1, arrs.count[s], mytab, ln, nn, n0inv);
+        canonicalize<C>(a, nn, ln);
+        // (the output pointer and the ragged edge are looked up HERE, behind the loop of steps, for the same reason)
+        if (el < n32) store_elem<C>(arrs.out[s] + (size_t)el * W, a, ln);
+    }
 }
 
 // Two independent exponentiations in ONE launch (small arrays): job 0 = out0[i] = x0[i]^e0 (one exponent for all), job 1 =

@@ -20,6 +20,7 @@
 #include "sha256.h"
 #include "sha512.h"
 #include "hostnum64.h"
+#include "expprod_schedule.h"
 
 // the Cfg-templated kernels are compiled in the instantiation units csrc/inst_*.hip (modp_instances.h); here they are declared
 VMN_UNIT_SMALL(extern template)
@@ -2276,6 +2277,198 @@ extern "C" int vmn_garray_exp_scalars_multi(const vmn_garray* const* xs, size_t 
         }
     }
     return rc;
+}
+
+// ---- K3' over arrays: out[i] = prod_j xs[j][i]^(c_j) -----------------------------------------------------------------
+// One launch over a modular group: the bases xs[0 .. nb) (nb <= EXPPROD_BASES, every exponent non-zero), the product of those
+// with neg[j] == 0 into outP and of the others into outN (either may be absent: then the pointer is not read), each under its
+// own schedule, as the tiles of two arrays of one launch (k_modpow_expprod, modp_shared_exp.h).
+static int modpow_expprod(vmn_ctx* ctx, const vmn_modulus& m0, const uint32_t* const* xs, const Big* es, const int* neg, size_t nb, int bits,
+                          size_t n, uint32_t* outP, uint32_t* outN) {
+    ExpProdArrays arrs{};
+    std::vector<SlideStep> steps;
+    size_t nprod = 0;
+    double products = 0, squares = 0;
+    for (int sign = 0; sign < 2; ++sign) {
+        std::vector<Big> part;
+        unsigned char idx[EXPPROD_BASES];
+        for (size_t j = 0; j < nb; ++j) {
+            if ((neg[j] != 0) != (sign != 0)) continue;
+            idx[part.size()] = (unsigned char)j;
+            part.push_back(es[j]);
+        }
+        if (part.empty()) continue;
+        long mults = 0, squarings = 0;
+        arrs.first[nprod] = (u32)steps.size();
+        arrs.count[nprod] = (int)expprod_schedule(part.data(), part.size(), bits, EXPPROD_GROUP, EXPPROD_GROUP_ROWS, steps, mults, squarings);
+        arrs.nb[nprod] = (int)part.size();
+        for (size_t j = 0; j < part.size(); ++j) arrs.base[nprod][j] = idx[j];
+        arrs.out[nprod] = sign ? outN : outP;
+        const int groups = ((int)part.size() + EXPPROD_GROUP - 1) / EXPPROD_GROUP;
+        arrs.trows = std::max(arrs.trows, groups * EXPPROD_GROUP_ROWS);
+        long table = 0;                                               // one product per row of more than one base
+        for (int g = 0; g < groups; ++g) {
+            const int gs = std::min(EXPPROD_GROUP, (int)part.size() - g * EXPPROD_GROUP);
+            table += (1L << gs) - 1 - gs;
+        }
+        products += (double)n * (double)(mults + table);
+        squares += (double)n * (double)squarings;
+        ++nprod;
+    }
+    for (size_t j = 0; j < nb; ++j) arrs.x[j] = xs[j];
+    DevTmp dsteps(ctx);
+    VMN_TRY(dsteps.alloc(steps.size() * sizeof(SlideStep)));
+    VMN_TRY(h2d(ctx, dsteps.p, steps.data(), steps.size() * sizeof(SlideStep)));
+    const vmn_modulus& m = geom(ctx, m0, nprod * n);
+    PhasePlan pl(ctx, m, n, nprod);
+    VMN_TRY(ensure_scratch(ctx, pl.slot_tables_bytes(m, (size_t)arrs.trows)));
+    note_work(ctx, m, products, squares);
+    const uint32_t ntiles = (uint32_t)(pl.ntiles / nprod), total = (uint32_t)pl.ntiles;
+    return with_cfg(m, [&]<class C, class W>(C, W) {
+        return launch(ctx, "expprod_arrays", k_modpow_expprod<C>, pl.grid, lds_bytes(m), arrs, ntiles, total, (const SlideStep*)dsteps.as<SlideStep>(),
+                      (uint32_t)n, m.d_n, m.n0inv, reinterpret_cast<uint32_t*>(ctx->scratch));
+    });
+}
+// One launch over a curve: out = sum_j (neg[j] ? -1 : 1) es[j] xs[j], nb <= EXPPROD_BASES, every scalar non-zero (k_ec_expprod)
+static int ec_expprod(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* const* xs, const Big* es, const int* neg, size_t nb, int bits, size_t n,
+                      uint32_t* out) {
+    ECExpProdArrays arrs{};
+    std::vector<SlideStep> steps;
+    long mults = 0, squarings = 0;
+    const int nsteps = (int)expprod_schedule(es, nb, bits, EXPPROD_GROUP, EXPPROD_GROUP_ROWS, steps, mults, squarings);
+    arrs.nb = (int)nb;
+    const int groups = ((int)nb + EXPPROD_GROUP - 1) / EXPPROD_GROUP;
+    arrs.trows = groups * EXPPROD_GROUP_ROWS;
+    long table = 0;
+    for (int g = 0; g < groups; ++g) {
+        const int gs = std::min(EXPPROD_GROUP, (int)nb - g * EXPPROD_GROUP);
+        table += (1L << gs) - 1 - gs;
+    }
+    for (size_t j = 0; j < nb; ++j) {
+        arrs.x[j] = xs[j];
+        if (neg[j]) arrs.negmask |= 1u << j;
+    }
+    DevTmp dsteps(ctx);
+    VMN_TRY(dsteps.alloc(steps.size() * sizeof(SlideStep)));
+    VMN_TRY(h2d(ctx, dsteps.p, steps.data(), steps.size() * sizeof(SlideStep)));
+    const unsigned grid = std::min<unsigned>(grid_for(n), (unsigned)(ctx->num_cus * 2));
+    VMN_TRY(ensure_scratch(ctx, (size_t)grid * BLOCK * (size_t)arrs.trows * elem_words(m) * sizeof(uint32_t)));
+    note_work(ctx, m, (double)n * (EC_DBL * (double)squarings + EC_ADD * (double)(mults + table)));
+    return with_curve(m, [&]<class E>(E) {
+        return launch_light(ctx, "expprod_arrays", k_ec_expprod<E::S, E::KIND>, grid, out, arrs, (const SlideStep*)dsteps.as<SlideStep>(), nsteps, n,
+                            ecdev(m.ec), reinterpret_cast<uint32_t*>(ctx->scratch));
+    });
+}
+
+// acc = acc * y (acc empty: acc takes y over); y is released either way
+static int expprod_fold(vmn_garray*& acc, vmn_garray* y) {
+    if (!acc) {
+        acc = y;
+        return VMN_OK;
+    }
+    vmn_garray* prod = nullptr;
+    const int rc = vmn_garray_mul(acc, y, &prod);
+    vmn_garray_free(y);
+    if (rc != VMN_OK) return rc;
+    vmn_garray_free(acc);
+    acc = prod;
+    return VMN_OK;
+}
+
+extern "C" int vmn_garray_expprod_arrays(const vmn_garray* const* xs, size_t k, const uint8_t* abs_be, size_t ebytes, const int* negative,
+                                         int bitlen, vmn_garray** out) {
+    ARG_CHECK(xs && abs_be && negative && out && ebytes > 0, "null argument");
+    ARG_CHECK(k > 0, "no arrays");
+    for (size_t c = 0; c < k; ++c) ARG_CHECK(xs[c], "null array");
+    for (size_t c = 1; c < k; ++c) ARG_CHECK(xs[c]->grp == xs[0]->grp && xs[c]->n == xs[0]->n, "the arrays differ in group or size");
+    ARG_CHECK(bitlen >= 0 && (size_t)bitlen <= 8 * ebytes, "bitlen exceeds the width of the integers");
+    if (bitlen == 0) bitlen = (int)(8 * ebytes);
+    vmn_group* g = xs[0]->grp;
+    vmn_ctx* ctx = LANE(g->ctx);
+    VMN_ENTER(ctx);
+    const vmn_modulus& m = g->P;
+    const size_t n = xs[0]->n;
+    // the bases that take part: those with a non-zero exponent (over a curve: non-zero modulo the group order)
+    std::vector<Big> es;
+    std::vector<int> neg;
+    std::vector<const uint32_t*> xd;
+    int bits = 0;
+    for (size_t c = 0; c < k; ++c) {
+        const uint8_t* row = abs_be + c * ebytes;
+        Big e = hostbig::from_be(row, ebytes, (ebytes + 3) / 4);
+        ARG_CHECK(hostbig::bit_length(e) <= bitlen, "an integer is longer than bitlen");
+        if (m.ec) {                                       // scalars act modulo the group order
+            const vmn_modulus& q = g->Q;
+            std::vector<uint8_t> be((size_t)q.NW * 4);
+            num64::to_be(q.hm64->reduce(row, ebytes), be.data(), be.size());
+            e = hostbig::from_be(be.data(), be.size(), q.NW);
+        }
+        if (hostbig::is_zero(e)) continue;
+        bits = std::max(bits, hostbig::bit_length(e));
+        es.push_back(e);
+        neg.push_back(negative[c] != 0);
+        xd.push_back(xs[c]->d);
+    }
+    vmn_garray* r = nullptr;
+    if (n == 0 || es.empty()) {                           // nothing to raise: the empty array resp. the array of ones
+        VMN_TRY(new_garray(g, n, &r));
+        int rc = VMN_OK;
+        if (n) {
+            const int cpr = (int)(elem_words(m) / 4);
+            rc = launch_light(ctx, "gather", k_fill_rows, light_grid(ctx, n * cpr), reinterpret_cast<uint4*>(r->d),
+                              reinterpret_cast<const uint4*>(m.d_one), n, cpr);
+        }
+        if (rc != VMN_OK) {
+            vmn_garray_free(r);
+            return rc;
+        }
+        *out = r;
+        return VMN_OK;
+    }
+    // (modular groups only: k_modpow_expprod counts tiles and elements in 32 bits: below 2^31 elements the indices of a ragged last tile stay below 2^32
+    // and the tiles of two products below 2^29 in the widest geometry, 16 elements per tile)
+    ARG_CHECK(m.ec || n < ((size_t)1 << 31), "array too long");
+    // a launch per EXPPROD_BASES bases; the launches' positive and negative products are multiplied, the negative one inverted
+    vmn_garray *P = nullptr, *N = nullptr;
+    int rc = VMN_OK;
+    for (size_t b0 = 0; rc == VMN_OK && b0 < es.size(); b0 += EXPPROD_BASES) {
+        const size_t nb = std::min<size_t>(EXPPROD_BASES, es.size() - b0);
+        vmn_garray *p = nullptr, *q = nullptr;
+        if (m.ec) {
+            rc = new_garray(g, n, &p);
+            if (rc == VMN_OK) rc = ec_expprod(ctx, m, &xd[b0], &es[b0], &neg[b0], nb, bits, n, p->d);
+        } else {
+            const bool anyneg = std::count(neg.begin() + b0, neg.begin() + b0 + nb, 0) != (long)nb;
+            const bool anypos = std::count(neg.begin() + b0, neg.begin() + b0 + nb, 0) != 0;
+            if (anypos) rc = new_garray(g, n, &p);
+            if (rc == VMN_OK && anyneg) rc = new_garray(g, n, &q);
+            if (rc == VMN_OK) rc = modpow_expprod(ctx, m, &xd[b0], &es[b0], &neg[b0], nb, bits, n, p ? p->d : nullptr, q ? q->d : nullptr);
+        }
+        if (rc != VMN_OK) {
+            if (p) vmn_garray_free(p);
+            if (q) vmn_garray_free(q);
+            break;
+        }
+        if (p) rc = expprod_fold(P, p);
+        if (q) {
+            if (rc == VMN_OK) rc = expprod_fold(N, q);
+            else vmn_garray_free(q);
+        }
+    }
+    if (rc == VMN_OK && N) {
+        vmn_garray* ninv = nullptr;
+        rc = vmn_garray_inv(N, &ninv);
+        vmn_garray_free(N);
+        N = nullptr;
+        if (rc == VMN_OK) rc = expprod_fold(P, ninv);
+    }
+    if (rc != VMN_OK) {
+        if (P) vmn_garray_free(P);
+        if (N) vmn_garray_free(N);
+        return rc;
+    }
+    *out = P;
+    return VMN_OK;
 }
 
 // out[i] = x[i]^e * y[i]^f[i] over a modular group, exponents in packed words on the device: e one exponent of ewords words,

@@ -3290,6 +3290,13 @@ int vmn_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* 
 int vmn_decryption_factors(vmn_group* grp, const vmn_garray* u, const uint8_t* secret_be, int k, vmn_garray** f_out) {
     return vmn_decryption_factors_wide(grp, 1, &u, secret_be, k, f_out);
 }
+// bits of a big-endian integer
+static int be_bit_length(const Bytes& b) {
+    for (size_t i = 0; i < b.size(); ++i) {
+        if (b[i]) return (int)(8 * (b.size() - 1 - i)) + 32 - __builtin_clz((unsigned)b[i]);
+    }
+    return 0;
+}
 int vmn_combine_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_garray* const* f, const uint8_t* correct, int k, int threshold,
                                         vmn_garray** out) {
     if (!grp || !f || !correct || !out || width < 1) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: null argument");
@@ -3298,7 +3305,11 @@ int vmn_combine_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_
     std::vector<Num> abs;
     std::vector<int> neg, parties;
     TRY(lagrange(G, correct, k, threshold, abs, neg, &parties));
-    std::vector<GA> pos(width), negp(width);        // products of the positive / negative parts (:465-503), per component
+    // pGroup.expProd(factors of the chosen parties, integers, bitLength) (:465-503), per component: one call each
+    std::vector<int> use;                           // the parties with a non-zero integer
+    Bytes rows;
+    std::vector<int> signs;
+    int bitLength = 0;
     for (size_t t = 0; t < parties.size(); ++t) {
         if (vmn::num64::is_zero(abs[t])) continue;
         const vmn_garray* const* base = f + (size_t)parties[t] * width;
@@ -3306,35 +3317,17 @@ int vmn_combine_decryption_factors_wide(vmn_group* grp, size_t width, const vmn_
             if (!base[c]) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: factors of party %d are missing", parties[t]);
         }
         Bytes eb = G.ring_bytes(abs[t]);
-        std::vector<vmn_garray*> raw(width, nullptr);
-        TRY(vmn_garray_exp_scalar_multi(base, width, eb.data(), eb.size(), raw.data()));       // the party's components: one call
-        std::vector<GA> tpow(width);
-        for (size_t c = 0; c < width; ++c) tpow[c].p = raw[c];
-        for (size_t c = 0; c < width; ++c) {
-            GA& acc = neg[t] ? negp[c] : pos[c];
-            if (!acc.p) {
-                acc.p = tpow[c].release();
-            } else {
-                GA prod;
-                TRY(vmn_garray_mul(acc, tpow[c], prod.out()));
-                acc.reset();
-                acc.p = prod.release();
-            }
-        }
+        rows.insert(rows.end(), eb.begin(), eb.end());
+        signs.push_back(neg[t]);
+        use.push_back(parties[t]);
+        bitLength = std::max(bitLength, be_bit_length(eb));
     }
-    if (!pos[0].p && !negp[0].p) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: all coefficients are zero");
+    if (use.empty()) return fail(VMN_ERR_ARG, "vmn_combine_decryption_factors: all coefficients are zero");
     std::vector<GA> res(width);
+    std::vector<const vmn_garray*> bases(use.size());
     for (size_t c = 0; c < width; ++c) {
-        if (negp[c].p) {
-            GA ninv;
-            TRY(vmn_garray_inv(negp[c], ninv.out()));
-            if (!pos[c].p)
-                res[c].p = ninv.release();
-            else
-                TRY(vmn_garray_mul(pos[c], ninv, res[c].out()));
-        } else {
-            res[c].p = pos[c].release();
-        }
+        for (size_t t = 0; t < use.size(); ++t) bases[t] = f[(size_t)use[t] * width + c];
+        TRY(vmn_garray_expprod_arrays(bases.data(), bases.size(), rows.data(), G.xb, signs.data(), bitLength, res[c].out()));
     }
     for (size_t c = 0; c < width; ++c) out[c] = res[c].release();
     return VMN_OK;
