@@ -188,17 +188,20 @@ int vmn_garray_exp_scalar(const vmn_garray* x, const uint8_t* e_be, size_t ebyte
 /* The same for k arrays of one group and one size under ONE exponent: outs[c][i] = xs[c][i]^e, bit for bit what k calls of
  * vmn_garray_exp_scalar give (the omega component arrays of a width-omega list raised to a party's secret:
  * P/elgamal/DistrElGamalSession.java:365-389 over a product group).  Over a modular group, for exponents above 32 bits, up to
- * eight arrays share one launch; VMN_EXP_MULTI_FUSED=0 (read per call) runs them one after the other.  The same array may
- * appear twice.  k = 0, arrays of two groups or of different sizes: VMN_ERR_ARG.  On failure no output stays allocated
+ * eight arrays share one launch; VMN_EXP_MULTI_FUSED=0 (read per call) runs them one after the other.  Over a curve up to
+ * eight arrays share one launch as well, whatever the scalar: it is reduced modulo the group order and recoded into signed odd
+ * digits on the host (VMN_EC_SHARED=0, read per call: the fixed-window kernel for per-point scalars, array by array).  The same
+ * array may appear twice.  k = 0, arrays of two groups or of different sizes: VMN_ERR_ARG.  On failure no output stays allocated
  * (outs[c] = NULL). */
 int vmn_garray_exp_scalar_multi(const vmn_garray* const* xs, size_t k, const uint8_t* e_be, size_t ebytes, vmn_garray** outs);
 /* The same with an exponent per ARRAY: outs[c][i] = xs[c][i]^(e_c), es_be holds k rows of ebytes bytes, row c the exponent of
  * array c; bit for bit what vmn_garray_exp_scalar gives for (xs[c], e_c).  Under a public key of width kappa the component
  * arrays of a party's decryption factors take kappa different secrets (P/elgamal/DistrElGamalSession.java:365-389 over
  * (G^kappa)^omega).  Over a modular group with every exponent above 32 bits up to eight arrays share one launch, each under a
- * schedule of its own; VMN_EXP_MULTI_FUSED=0 (read per call) runs them one after the other.  Over a curve, or with any exponent
- * of at most 32 bits in the call, the arrays run one after the other, each as vmn_garray_exp_scalar runs it.  Arguments and
- * failures as for vmn_garray_exp_scalar_multi. */
+ * schedule of its own; VMN_EXP_MULTI_FUSED=0 (read per call) runs them one after the other.  Over a curve up to eight arrays
+ * share one launch, each under the schedule of its own scalar, zero included (VMN_EC_SHARED=0: array by array, as before).  Over
+ * a modular group with any exponent of at most 32 bits in the call, the arrays run one after the other, each as
+ * vmn_garray_exp_scalar runs it.  Arguments and failures as for vmn_garray_exp_scalar_multi. */
 int vmn_garray_exp_scalars_multi(const vmn_garray* const* xs, size_t k, const uint8_t* es_be, size_t ebytes, vmn_garray** outs);
 /* K2  g.exp(E): out[i] = base^E[i] for one fixed base.  ref: P/mixnet/ShufflerElGamalSession.java:407,
  * 658; P/hvzk/PoSBasicTW.java:447, 606, 608, 644, 646, 1030; P/mixnet/PermutationCommitment.java:200. */
@@ -262,7 +265,8 @@ int vmn_garray_exp2(const vmn_garray* x, const uint8_t* e_be, size_t ebytes, con
                     vmn_garray** out);
 /* out_x[i] = x[i]^e and out_y[i] = y[i]^f[i], the two powers of the same check in its separate form
  * (PoSBasicTW.java:1028-1033: B.exp(v) and B_shift.exp(k_E)), as ONE launch when the arrays are too small to fill
- * the device one after the other; otherwise (and over curves) exactly vmn_garray_exp_scalar + vmn_garray_exp_array.
+ * the device one after the other; otherwise (and over curves, where the shared half takes the signed windows of
+ * vmn_garray_exp_scalar) exactly vmn_garray_exp_scalar + vmn_garray_exp_array.
  * x and y may differ in length; f has y's. */
 int vmn_garray_exp_pair(const vmn_garray* x, const uint8_t* e_be, size_t ebytes, const vmn_garray* y, const vmn_rarray* f, int fbits,
                         vmn_garray** out_x, vmn_garray** out_y);

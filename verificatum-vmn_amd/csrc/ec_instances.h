@@ -15,6 +15,12 @@
     KW __global__ void vmn::k_ec_mulvar2<S_, K_>(vmn::u32*, const vmn::u32*, const vmn::u32*, int, int, const vmn::u32*, const vmn::u32*, int, \
                                              size_t, int, int, size_t, vmn::ECDev, vmn::u32*);                                          \
     KW __global__ void vmn::k_ec_expprod<S_, K_>(vmn::u32*, vmn::ECExpProdArrays, const vmn::SlideStep*, int, size_t, vmn::ECDev, vmn::u32*); \
+    KW __global__ void vmn::k_ec_mulshared<S_, K_, vmn::ECOneArray>(vmn::ECOneArray, vmn::u32, vmn::u32, const vmn::ECSharedStep*, int, int, \
+                                                                    size_t, vmn::ECDev, vmn::u32*);                                     \
+    KW __global__ void vmn::k_ec_mulshared<S_, K_, vmn::ECSharedArrays>(vmn::ECSharedArrays, vmn::u32, vmn::u32, const vmn::ECSharedStep*, int, \
+                                                                        int, size_t, vmn::ECDev, vmn::u32*);                            \
+    KW __global__ void vmn::k_ec_mulshared<S_, K_, vmn::ECEachArrays>(vmn::ECEachArrays, vmn::u32, vmn::u32, const vmn::ECSharedStep*, int, int, \
+                                                                      size_t, vmn::ECDev, vmn::u32*);                                   \
     KW __global__ void vmn::k_ec_chain<S_, K_>(vmn::u32*, const vmn::u32*, int, vmn::ECDev);                                             \
     KW __global__ void vmn::k_ec_fixed_level<S_, K_>(vmn::u32*, int, int, int, vmn::ECDev);                                              \
     KW __global__ void vmn::k_ec_fixed_exp<S_, K_>(vmn::u32*, const vmn::u32*, int, int, const vmn::u32*, int, size_t, vmn::ECDev);      \

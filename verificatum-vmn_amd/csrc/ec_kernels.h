@@ -1261,6 +1261,127 @@ __global__ void __launch_bounds__(BLOCK, (EC_EXPPROD_MINW<S, KIND>)) k_ec_exppro
     }
 }
 
+// K1 with ONE scalar for whole arrays: out[i] = e * x[i], a party's decryption factors over a curve (elgamal/
+// DistrElGamalSession.java:365-389), B.exp(v) of a verifier's check (B) and raisedu = u^rho.  The host recodes the scalar into
+// signed odd digits and hands in a schedule of ECSharedStep (ec_shared_schedule.h): `sq` doublings, then the addition (op = 2 r)
+// or the subtraction (op = 2 r + 1) of table row r, which holds (2 r + 1) P; op < 0: no addition.  Every lane walks the same
+// steps, so the steering is wave-uniform.  The per-lane table in scratch has `trows` = 2^(w-2) rows: P, then 2 P by one doubling
+// -- parked in the LAST row, which is the last to be filled -- then 3 P = P + 2 P, 5 P = 3 P + 2 P, ...; one row (w = 2) needs no
+// doubling.  A subtraction is A - Q = -((-A) + Q): the accumulator's Y is negated in front of the addition and behind it (the
+// f_sub from zero of k_ec_expprod's negative bases, twice S limb operations against the 16 field products of the addition; the
+// flag of infinity is untouched, and negation commutes with every case of pt_add).  Negating the loaded row instead, while both
+// points are live, made the compiler report 4 (15 limbs, a = -3) and 12 (21 limbs, general) spilled registers where this form
+// reports 2 and 0.  Every sum goes through pt_add, exact at infinity and at equal or opposite points.  As in k_ec_expprod the
+// table rows and the steps are ONE loop, so that the addition and the doubling are laid out once.  A result row may leave with
+// Y = 256p - y, the form k_ec_neg stores.
+//
+// The arrays of a launch come as a descriptor in the shape of OneArray / SharedArrays / EachArrays (modp_shared_exp.h): global
+// tile T is tile T % ntiles of array T / ntiles (block-uniform, a scalar pick), every array keeps its own ragged last tile, and
+// with schedules of their own array a walks `count[a]` steps from steps[first[a]] on; an empty schedule (a scalar = 0 modulo the
+// group order) writes infinity.
+struct ECSharedStep {
+    int sq;
+    int op;
+};
+struct ECOneArray {
+    const u32* x;
+    u32* out;
+    __device__ __forceinline__ u32 array_of(size_t, u32) const { return 0; }
+    __device__ __forceinline__ size_t tile_of(size_t T, u32, u32) const { return T; }
+    __device__ __forceinline__ const u32* x_of(u32) const { return x; }
+    __device__ __forceinline__ u32* out_of(u32) const { return out; }
+    __device__ __forceinline__ u32 first_of(u32) const { return 0; }
+    __device__ __forceinline__ int count_of(u32, int nsteps) const { return nsteps; }
+};
+struct ECSharedArrays {
+    const u32* x[SHARED_ARRAYS];
+    u32* out[SHARED_ARRAYS];
+    // the array of global tile T, and T's index among that array's tiles (the host keeps k * ntiles below 2^31)
+    __device__ __forceinline__ u32 array_of(size_t T, u32 ntiles) const { return (u32)T / ntiles; }
+    __device__ __forceinline__ size_t tile_of(size_t T, u32 a, u32 ntiles) const { return (u32)T - a * ntiles; }
+    __device__ __forceinline__ const u32* x_of(u32 a) const { return x[a]; }
+    __device__ __forceinline__ u32* out_of(u32 a) const { return out[a]; }
+    __device__ __forceinline__ u32 first_of(u32) const { return 0; }
+    __device__ __forceinline__ int count_of(u32, int nsteps) const { return nsteps; }
+};
+struct ECEachArrays {
+    const u32* x[SHARED_ARRAYS];
+    u32* out[SHARED_ARRAYS];
+    u32 first[SHARED_ARRAYS];
+    int count[SHARED_ARRAYS];
+    __device__ __forceinline__ u32 array_of(size_t T, u32 ntiles) const { return (u32)T / ntiles; }
+    __device__ __forceinline__ size_t tile_of(size_t T, u32 a, u32 ntiles) const { return (u32)T - a * ntiles; }
+    __device__ __forceinline__ const u32* x_of(u32 a) const { return x[a]; }
+    __device__ __forceinline__ u32* out_of(u32 a) const { return out[a]; }
+    __device__ __forceinline__ u32 first_of(u32 a) const { return first[a]; }
+    __device__ __forceinline__ int count_of(u32 a, int) const { return count[a]; }
+};
+// P <- -P: Y <- 256p - Y (Y < 256p), limb by limb in place; the flag of infinity is untouched
+template <int S>
+__device__ __forceinline__ void pt_neg_y(Pt<S>& P, const ECDev& E) {
+    u32 z[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) z[i] = 0;
+    f_sub<S, true>(P.Y, z, P.Y, E);
+}
+// `total` global tiles, `ntiles` of them per array of n points; `trows` table rows per lane slot in `tab`.  (The tile counter has
+// 32 bits and the point is loaded in front of the loop, so that neither a second counter word nor the input pointer is held
+// across it: over 21 limbs, where the field's constants fill the scalar registers, the 64-bit form spilled one of them.)
+template <int S, int KIND, class Arrays>
+__global__ void __launch_bounds__(BLOCK, (EC_EXPPROD_MINW<S, KIND>)) k_ec_mulshared(Arrays arrs, u32 ntiles, u32 total, const ECSharedStep* __restrict__ steps,
+                                                      int nsteps, int trows, size_t n, ECDev E, u32* tab) {
+    constexpr int ROW = ECfg<S>::ROW;
+    u32* mytab = tab + ((size_t)blockIdx.x * BLOCK + threadIdx.x) * (size_t)trows * ROW;
+    const int build = trows > 1 ? trows + 1 : 1;                         // iterations that fill the table (one of them is 2 P)
+    for (u32 T = blockIdx.x; T < total; T += gridDim.x) {               // (the host keeps `total` below 2^31: T + gridDim.x cannot wrap)
+        const u32 arr = arrs.array_of(T, ntiles);
+        const size_t t = arrs.tile_of(T, arr, ntiles);
+        const u32* __restrict__ x = arrs.x_of(arr);
+        const ECSharedStep* __restrict__ st = steps + arrs.first_of(arr);
+        const int cnt = arrs.count_of(arr, nsteps);
+        const size_t el = t * BLOCK + threadIdx.x;
+        const bool live = el < n;
+        const size_t ec = live ? el : n - 1;
+        Pt<S> A, Q;
+        pt_load<S>(A, x + ec * ROW);
+        if (cnt == 0) {                                                  // (block-uniform)
+            pt_set_inf<S>(A, E);
+        } else {
+#pragma unroll 1
+            for (int it = 0; it < build + cnt - 1; ++it) {
+                int nd = 0, keep = -1, op = -1;                          // (wave-uniform, like everything that steers this loop)
+                if (it >= build) {
+                    const int s = it - build + 1;
+                    if (s == 1) pt_load<S>(A, mytab + (size_t)(st[0].op >> 1) * ROW);
+                    nd = st[s].sq;
+                    op = st[s].op;
+                } else if (it == 0) {
+                    keep = 0;                                            // P itself
+                } else if (it == 1) {
+                    nd = 1;                                              // 2 P, parked in the last row
+                    keep = trows - 1;
+                } else {
+                    if (it == 2) pt_load<S>(A, mytab);                   // (A was 2 P)
+                    op = 2 * (trows - 1);                                // + 2 P
+                    keep = it - 1;
+                }
+#pragma unroll 1
+                for (int d = 0; d < nd; ++d) pt_dbl<S, KIND>(A, A, E);
+                const bool sub = op >= 0 && (op & 1);                    // A - Q = -((-A) + Q)
+                if (sub) pt_neg_y<S>(A, E);
+                if (op >= 0) {
+                    pt_load<S>(Q, mytab + (size_t)(op >> 1) * ROW);
+                    pt_add<S, KIND>(A, A, Q, E);
+                }
+                if (sub) pt_neg_y<S>(A, E);
+                if (keep >= 0) pt_store<S>(mytab + (size_t)keep * ROW, A);
+            }
+            if (cnt == 1) pt_load<S>(A, mytab + (size_t)(st[0].op >> 1) * ROW);
+        }
+        if (live) pt_store<S>(arrs.out_of(arr) + el * ROW, A);
+    }
+}
+
 // sq[j] = 2^j * base, j < count: the doubling chain of a fixed-base table, one lane (count ~ 256-400 doublings)
 // (launch bounds: without them the compiler budgets registers for 1024 threads per block and the point doubling spills --
 // the chain then took 27 us per doubling instead of 5)

@@ -20,6 +20,7 @@
 #include "sha256.h"
 #include "sha512.h"
 #include "hostnum64.h"
+#include "ec_shared_schedule.h"
 #include "expprod_schedule.h"
 
 // the Cfg-templated kernels are compiled in the instantiation units csrc/inst_*.hip (modp_instances.h); here they are declared
@@ -2151,13 +2152,121 @@ extern "C" int vmn_garray_exp_ints(const vmn_garray* x, const uint8_t* exps_be, 
     return VMN_OK;
 }
 
-// outs[c][i] = xs[c][i]^e for k arrays of one group and one size.  Modular groups and exponents above 32 bits: the sliding window
-// with one exponent for all, the arrays of a call in one launch (VMN_EXP_MULTI_FUSED=0, read per call: one launch per array);
-// curves and short exponents: the fixed-window kernel, array by array.  On failure nothing stays allocated.
+// VMN_EXP_MULTI_FUSED=0 (read per call): the arrays of a call one launch each
 static bool exp_multi_fused() {
     const char* env = getenv("VMN_EXP_MULTI_FUSED");
     return !(env && *env && atoi(env) == 0);
 }
+
+// ---- curves under a shared scalar: signed windows, the arrays of a call in one launch (k_ec_mulshared, ec_kernels.h) ----
+// VMN_EC_SHARED=0 (read per call): the fixed-window kernel for per-lane scalars, k_ec_mulvar, array by array -- the A/B arm
+static bool ec_shared_enabled() {
+    const char* env = getenv("VMN_EC_SHARED");
+    return !(env && *env && atoi(env) == 0);
+}
+// a scalar modulo the order of a curve group (scalars act modulo it), in the words of the order
+static Big reduce_mod_order(const vmn_group* g, const uint8_t* e_be, size_t ebytes) {
+    const vmn_modulus& q = g->Q;
+    std::vector<uint8_t> be((size_t)q.NW * 4);
+    num64::to_be(q.hm64->reduce(e_be, ebytes), be.data(), be.size());
+    return hostbig::from_be(be.data(), be.size(), q.NW);
+}
+// n rows of the group's identity
+static int fill_identity(vmn_ctx* ctx, const vmn_modulus& m, uint32_t* d, size_t n) {
+    const int cpr = (int)(elem_words(m) / 4);
+    return launch_light(ctx, "gather", k_fill_rows, light_grid(ctx, n * cpr), reinterpret_cast<uint4*>(d), reinterpret_cast<const uint4*>(m.d_one), n,
+                        cpr);
+}
+// `k` arrays of n > 0 points each, array c under es[c] (`one_scalar`: all under es[0]), the scalars reduced modulo the group order.
+// ONE window width for the call, the cheapest of 2 ... 6 by the library's own prices of a doubling and an addition summed over the
+// scalars' actual recodings (VMN_EC_SHARED_WINDOW=w, read per call, forces it); one schedule per scalar, all in one upload; up to
+// SHARED_ARRAYS arrays share a launch (VMN_EXP_MULTI_FUSED=0: one launch per array).  The grid is that of k_ec_mulvar over the
+// launch's tiles, capped by VMN_MODPOW_MAX_BLOCKS like the modular powers; a table of 2^(w-2) rows per lane slot in the scratch
+// buffer.  An array whose scalar is zero becomes infinity: in the kernel beside the others, without a launch where a launch has
+// no other array.
+static int ec_mulshared(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* const* xs, uint32_t* const* outs, size_t k, const Big* es,
+                        bool one_scalar, size_t n) {
+    int forced = 0;
+    if (const char* env = getenv("VMN_EC_SHARED_WINDOW")) forced = atoi(env);
+    const size_t ns = one_scalar ? 1 : k;
+    const int w = ec_shared_window(es, ns, EC_DBL, EC_ADD, forced);
+    const int trows = ec_shared_rows(w);
+    std::vector<ECSharedStep> steps;
+    std::vector<uint32_t> first(ns);
+    std::vector<int> count(ns);
+    std::vector<long> adds(ns), dbls(ns);
+    for (size_t c = 0; c < ns; ++c) {
+        first[c] = (uint32_t)steps.size();
+        count[c] = (int)ec_shared_schedule(es[c], w, steps, adds[c], dbls[c]);
+    }
+    DevTmp dsteps(ctx);
+    if (!steps.empty()) {
+        VMN_TRY(dsteps.alloc(steps.size() * sizeof(ECSharedStep)));
+        VMN_TRY(h2d(ctx, dsteps.p, steps.data(), steps.size() * sizeof(ECSharedStep)));
+    }
+    const ECSharedStep* d_steps = dsteps.as<ECSharedStep>();
+    const size_t ntiles = (n + BLOCK - 1) / BLOCK;
+    // (the kernel counts global tiles in 32 bits and steps by its grid: k ntiles stays below 2^31)
+    ARG_CHECK(ntiles < ((size_t)1 << 31), "array too long");
+    const size_t group = exp_multi_fused() && ntiles < ((size_t)1 << 31) / SHARED_ARRAYS ? SHARED_ARRAYS : 1;
+    unsigned max_blocks = (unsigned)(ctx->num_cus * 2);
+    if (const char* mb = getenv("VMN_MODPOW_MAX_BLOCKS")) {           // (the test hook of PhasePlan: few workgroup slots walk many tiles)
+        const int v = atoi(mb);
+        if (v >= 1) max_blocks = std::min<unsigned>(max_blocks, (unsigned)v);
+    }
+    for (size_t a0 = 0; a0 < k; a0 += group) {
+        const size_t ga = std::min(group, k - a0);
+        auto scalar_of = [&](size_t a) { return one_scalar ? (size_t)0 : a0 + a; };
+        double work = 0;                                              // every array's own doublings and additions, table included
+        bool any = false;
+        for (size_t a = 0; a < ga; ++a) {
+            const size_t c = scalar_of(a);
+            if (count[c] == 0) continue;
+            any = true;
+            work += (double)n * (EC_DBL * (double)(dbls[c] + (trows > 1 ? 1 : 0)) + EC_ADD * (double)(adds[c] + trows - 1));
+        }
+        if (!any) {                                                   // every scalar of the launch is zero: nothing to launch
+            for (size_t a = 0; a < ga; ++a) VMN_TRY(fill_identity(ctx, m, outs[a0 + a], n));
+            continue;
+        }
+        const uint32_t total = (uint32_t)(ga * ntiles);
+        const unsigned grid = std::min<unsigned>(total, max_blocks);
+        VMN_TRY(ensure_scratch(ctx, (size_t)grid * BLOCK * (size_t)trows * elem_words(m) * sizeof(uint32_t)));
+        note_work(ctx, m, work);
+        uint32_t* tab = reinterpret_cast<uint32_t*>(ctx->scratch);
+        VMN_TRY(with_curve(m, [&]<class E>(E) {
+            if (ga == 1) {
+                const size_t c = scalar_of(0);
+                return launch_light(ctx, "modpow", k_ec_mulshared<E::S, E::KIND, ECOneArray>, grid, ECOneArray{xs[a0], outs[a0]}, (uint32_t)ntiles, total,
+                                    d_steps + first[c], count[c], trows, n, ecdev(m.ec), tab);
+            }
+            if (one_scalar) {
+                ECSharedArrays arrs{};
+                for (size_t a = 0; a < ga; ++a) {
+                    arrs.x[a] = xs[a0 + a];
+                    arrs.out[a] = outs[a0 + a];
+                }
+                return launch_light(ctx, "modpow", k_ec_mulshared<E::S, E::KIND, ECSharedArrays>, grid, arrs, (uint32_t)ntiles, total, d_steps, count[0],
+                                    trows, n, ecdev(m.ec), tab);
+            }
+            ECEachArrays arrs{};
+            for (size_t a = 0; a < ga; ++a) {
+                arrs.x[a] = xs[a0 + a];
+                arrs.out[a] = outs[a0 + a];
+                arrs.first[a] = first[a0 + a];
+                arrs.count[a] = count[a0 + a];
+            }
+            return launch_light(ctx, "modpow", k_ec_mulshared<E::S, E::KIND, ECEachArrays>, grid, arrs, (uint32_t)ntiles, total, d_steps, 0, trows, n,
+                                ecdev(m.ec), tab);
+        }));
+    }
+    return VMN_OK;
+}
+
+// outs[c][i] = xs[c][i]^e for k arrays of one group and one size.  Modular groups and exponents above 32 bits: the sliding window
+// with one exponent for all, the arrays of a call in one launch (VMN_EXP_MULTI_FUSED=0, read per call: one launch per array);
+// curves: the signed windows of ec_mulshared, the arrays of a call in one launch as well (VMN_EC_SHARED=0: as the short exponents);
+// short exponents: the fixed-window kernel, array by array.  On failure nothing stays allocated.
 static int exp_scalar_arrays(vmn_ctx* ctx, vmn_group* g, const vmn_garray* const* xs, size_t k, const uint8_t* e_be, size_t ebytes,
                              vmn_garray** outs) {
     int ewords = (int)((ebytes + 3) / 4);
@@ -2176,6 +2285,17 @@ static int exp_scalar_arrays(vmn_ctx* ctx, vmn_group* g, const vmn_garray* const
     for (size_t c = 0; c < k; ++c) {
         int rc = new_garray(g, n, &outs[c]);
         if (rc != VMN_OK) return fail(rc);
+    }
+    if (g->P.ec && n > 0 && ec_shared_enabled()) {                     // curves: signed windows, the arrays of a call in one launch
+        std::vector<const uint32_t*> xd(k);
+        std::vector<uint32_t*> od(k);
+        for (size_t c = 0; c < k; ++c) {
+            xd[c] = xs[c]->d;
+            od[c] = outs[c]->d;
+        }
+        const Big r = reduce_mod_order(g, e_be, ebytes);
+        const int rc = ec_mulshared(ctx, g->P, xd.data(), od.data(), k, &r, true, n);
+        return rc == VMN_OK ? VMN_OK : fail(rc);
     }
     DevTmp ew(ctx);
     int rc = ew.alloc(ewords * sizeof(uint32_t));
@@ -2225,7 +2345,8 @@ extern "C" int vmn_garray_exp_scalar_multi(const vmn_garray* const* xs, size_t k
 
 // outs[c][i] = xs[c][i]^(e_c), row c of es_be the exponent of array c.  Modular groups with every exponent above 32 bits: one
 // schedule per array and the arrays of a call in one launch per SHARED_ARRAYS (modpow_shared_each; VMN_EXP_MULTI_FUSED=0, read
-// per call: array by array).  Curves, or any exponent of at most 32 bits in the call: every array exactly as
+// per call: array by array).  Curves: a schedule of signed windows per array, one launch per SHARED_ARRAYS (ec_mulshared).  Any
+// exponent of at most 32 bits in a call over a modular group, or VMN_EC_SHARED=0 over a curve: every array exactly as
 // vmn_garray_exp_scalar runs it under its exponent, one after the other.  On failure nothing stays allocated.
 extern "C" int vmn_garray_exp_scalars_multi(const vmn_garray* const* xs, size_t k, const uint8_t* es_be, size_t ebytes, vmn_garray** outs) {
     ARG_CHECK(xs && es_be && outs && ebytes > 0, "null argument");
@@ -2238,6 +2359,27 @@ extern "C" int vmn_garray_exp_scalars_multi(const vmn_garray* const* xs, size_t 
     VMN_ENTER(ctx);
     const size_t n = xs[0]->n;
     std::vector<Big> es(k);
+    if (g->P.ec && n > 0 && ec_shared_enabled()) {                     // curves: a schedule of signed windows per array, one launch
+        std::vector<const uint32_t*> xd(k);
+        std::vector<uint32_t*> od(k);
+        int rc = VMN_OK;
+        for (size_t c = 0; rc == VMN_OK && c < k; ++c) {
+            es[c] = reduce_mod_order(g, es_be + c * ebytes, ebytes);
+            rc = new_garray(g, n, &outs[c]);
+            if (rc == VMN_OK) {
+                xd[c] = xs[c]->d;
+                od[c] = outs[c]->d;
+            }
+        }
+        if (rc == VMN_OK) rc = ec_mulshared(ctx, g->P, xd.data(), od.data(), k, es.data(), false, n);
+        if (rc != VMN_OK) {
+            for (size_t c = 0; c < k; ++c) {
+                if (outs[c]) vmn_garray_free(outs[c]);
+                outs[c] = nullptr;
+            }
+        }
+        return rc;
+    }
     std::vector<int> ebits(k);
     bool sliding = !g->P.ec && n > 0;
     for (size_t c = 0; c < k; ++c) {
