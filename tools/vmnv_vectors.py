@@ -8,11 +8,14 @@ MixNetElGamalVerifyFiatShamir.java:382-388).
     python tools/vmnv_vectors.py --demo <new dir> [-n 100]      write a directory with the C++ prover first (synthetic list)
     python tools/vmnv_vectors.py <nizkp dir> -decrypt [--list FILE]      the decryption branch (:1545-1667): Dec.s, Dec.v
     python tools/vmnv_vectors.py --demo <new dir> -decrypt [--width 3] [--parties 3] [--threshold 2]
+    python tools/vmnv_vectors.py --demo <new dir> --curve P-256 [--precomputed N_0 | -decrypt]     the same over a named curve
 
 The directory layout is the reference's (verificatum-vmn_amd/proofdir.py); what `vmnv` reads from the protocol-info XML is
 in <dir>/params.json.  THE diff that would pin parity: on a machine with a JDK + VCR, run `vmnv -t der.rho,PoS ...` on a proof
 directory the Java mix-net wrote, run this tool on the same directory, and compare the values name by name (VCR's
-toString() of group elements is not part of the reference tree; this tool prints hexadecimal)."""
+toString() of group elements is not part of the reference tree; this tool prints hexadecimal, a curve point as (x, y)).  Over
+a curve, params.json's "pgroup" (the group's description string that goes into der.rho) is a placeholder: VCR's own description
+string of an ECqPGroup is not in the reference tree and must be pasted in by whoever diffs against `vmnv`."""
 import argparse
 import os
 import sys
@@ -56,20 +59,40 @@ def group_of(vmn, ctx, params):
     return vmn.ECqPGroup(ctx, params["group"]["curve"], java_widths=True)
 
 
+def key_elements(tree, points):
+    """The encodings of the 2 * width elements of a public key's tree node(u-half, v-half), in order.  An element is a leaf, over
+    a curve (`points`) the node of its two coordinate leaves."""
+    if isinstance(tree, list) and not (points and len(tree) == 2 and all(isinstance(c, bytes) for c in tree)):
+        return [e for child in tree for e in key_elements(child, points)]
+    return [b"".join(tree) if isinstance(tree, list) else tree]
+
+
+def demo_params(args, stdgroups, **more):
+    """params.json of a demo directory: the 2^(--bits) safe-prime group, or the curve --curve."""
+    params = {"version": "3.1.0", "sid": "MyDemo", "auxsid": "default", "rbitlen": 100, "vbitlenro": 256, "ebitlenro": 256,
+              "prg": "SHA-256", "rohash": "SHA-256", "rohash_name": "SHA-256"}
+    params.update(more)
+    if args.curve:
+        params["pgroup"] = f"ECqPGroup({args.curve})"        # a placeholder: see the module's docstring
+        params["group"] = {"kind": "ec", "curve": args.curve}
+    else:
+        p, q, g = stdgroups.modp_group(args.bits)
+        params["pgroup"] = f"ModPGroup(safe-prime modulus=2*order+1. order bit-length = {args.bits - 1})"
+        params["group"] = {"kind": "modp", "p": format(p, "x"), "q": format(q, "x"), "g": format(g, "x")}
+    return params
+
+
 def demo_decryption(args, vmn, ctx, proofdir, randomsource, stdgroups):
     """A synthetic list of width --width under a key shared among --parties parties (threshold --threshold), decrypted by
     proofdir.write_decryption with every party played here."""
-    p, q, g = stdgroups.modp_group(args.bits)
     k, thr, width = args.parties, args.threshold, args.width
-    params = {"version": "3.1.0", "sid": "MyDemo", "auxsid": "default", "rbitlen": 100, "vbitlenro": 256, "ebitlenro": 256,
-              "prg": "SHA-256", "rohash": "SHA-256", "rohash_name": "SHA-256", "width": width, "k": k, "threshold": thr,
-              "pgroup": f"ModPGroup(safe-prime modulus=2*order+1. order bit-length = {args.bits - 1})",
-              "group": {"kind": "modp", "p": format(p, "x"), "q": format(q, "x"), "g": format(g, "x")}}
+    params = demo_params(args, stdgroups, width=width, k=k, threshold=thr)
     grp = group_of(vmn, ctx, params)
+    q, g = grp.q, grp.g
     rnd = randomsource.InsecureShaRandomSource(b"vmnv-demo-decrypt", q)
     coeffs = rnd.ring_array(thr)
     shares = [None] + [sum(c * pow(l, d, q) for d, c in enumerate(coeffs)) % q for l in range(1, k + 1)]
-    poly = [pow(g, c, p) for c in coeffs]
+    poly = [grp.k_exp(g, c) for c in coeffs]
     pkey = [g] * width + [poly[0]] * width
     T = [grp.ringArray(rnd.ring_array(args.n)) for _ in range(width)]
     M = [grp.exp(g, grp.ringArray(rnd.ring_array(args.n))) for _ in range(width)]
@@ -91,8 +114,12 @@ def main():
                     help="the directory holds a PRECOMPUTED shuffle for N_0 ciphertexts (PoSC + keep list + CCPoS files) instead of a PoS; "
                          "with --demo: write one (N_0 >= n)")
     ap.add_argument("--bits", type=int, default=2048)
+    ap.add_argument("--curve", default=None, metavar="NAME",
+                    help="--demo: write the directory over this named curve (P-256, secp256k1, P-521, ...) instead of a modular group; "
+                         "params.json then records {kind: ec, curve: NAME}.  Its \"pgroup\" string is a placeholder: VCR's own "
+                         "description string of an ECqPGroup is not in the reference tree and must be pasted in by whoever diffs against vmnv")
     ap.add_argument("-decrypt", "--decrypt", dest="decrypt", action="store_true",
-                    help="verify the threshold decryption of a list (modular groups) instead of a shuffle; with --demo: write one")
+                    help="verify the threshold decryption of a list instead of a shuffle; with --demo: write one")
     ap.add_argument("--list", default=None, help="-decrypt: the decrypted list (default: Ciphertexts.bt of the directory)")
     ap.add_argument("--width", type=int, default=1, help="--demo -decrypt: width of the ciphertexts")
     ap.add_argument("--parties", type=int, default=3, help="--demo -decrypt: number of parties k")
@@ -106,14 +133,11 @@ def main():
     if args.demo and args.decrypt:
         demo_decryption(args, vmn, ctx, proofdir, randomsource, stdgroups)
     elif args.demo:
-        p, q, g = stdgroups.modp_group(args.bits)
-        params = {"version": "3.1.0", "sid": "MyDemo", "auxsid": "default", "rbitlen": 100, "vbitlenro": 256, "ebitlenro": 256,
-                  "prg": "SHA-256", "rohash": "SHA-256", "rohash_name": "SHA-256", "width": 1,
-                  "pgroup": f"ModPGroup(safe-prime modulus=2*order+1. order bit-length = {args.bits - 1})",
-                  "group": {"kind": "modp", "p": format(p, "x"), "q": format(q, "x"), "g": format(g, "x")}}
+        params = demo_params(args, stdgroups, width=1)
         grp = group_of(vmn, ctx, params)
+        q, g = grp.q, grp.g
         rnd = randomsource.InsecureShaRandomSource(b"vmnv-demo", q)
-        y = pow(g, rnd.ring_element(), p)
+        y = grp.k_exp(g, rnd.ring_element())
         pkey = [g, y]
         T = grp.ringArray(rnd.ring_array(args.n))
         M = grp.exp(g, grp.ringArray(rnd.ring_array(args.n)))
@@ -133,8 +157,7 @@ def main():
     from verificatum_vmn_amd import eio
     with open(proofdir.pk_file(args.nizkp), "rb") as f:
         tree, _ = eio.decode(f.read())
-    flat = [leaf for part in tree for leaf in (part if isinstance(part, list) else [part])]
-    pkey = [grp.dec_el(b) for b in flat]
+    pkey = [grp.dec_el(b) for b in key_elements(tree, grp.coord_bytes is not None)]
     vectors = {}
     n0 = args.precomputed or int(params.get("N_0", 0))
     if args.decrypt:

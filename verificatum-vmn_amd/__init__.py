@@ -260,6 +260,28 @@ class ModPGroup:
     def dec_els(self, buf: bytes) -> list:
         return be_to_ints(buf, self.nbytes)
 
+    # -- byte trees of single elements and sizes of array trees (what proofdir.py needs to stay group-agnostic) --
+    coord_bytes = None          # a curve group: the width of one coordinate leaf
+
+    def element_tree(self, el) -> bytes:
+        """Byte tree of one element: a leaf of ``nbytes`` bytes; over a curve node(leaf(x), leaf(y)), infinity as (-1, -1)."""
+        from . import fiatshamir as fs
+        return fs.group_element_tree(self.enc_el(el), self.coord_bytes)
+
+    def array_tree_size(self, n: int) -> int:
+        """Bytes of ``toByteTree()`` of an array of n elements of this group."""
+        from . import fiatshamir as fs
+        return fs.array_tree_size(n, self.elem_bytes, self.coord_bytes)
+
+    def element_from_tree(self, buf: bytes, pos: int = 0):
+        """(element, next position) of the element tree at ``buf[pos:]``; None when the framing is wrong (no leaf of
+        ``nbytes`` bytes there)."""
+        nb = self.nbytes
+        end = pos + 5 + nb
+        if len(buf) < end or bytes(buf[pos:pos + 5]) != b"\x01" + nb.to_bytes(4, "big"):
+            return None
+        return self.dec_el(bytes(buf[pos + 5:end])), end
+
     # Single elements: through the host arithmetic of libvmnproofs.so (vmn_element_*: 64-bit Montgomery / Jacobian
     # curve code, several times faster than Python integers / the affine Python curve code for the ~20
     # exponentiations of a proof) when that library is there, else plain Python.
@@ -475,6 +497,28 @@ class ECqPGroup(ModPGroup):
     def dec_els(self, buf: bytes) -> list:
         w = 2 * self.nbytes
         return [self.dec_el(buf[i:i + w]) for i in range(0, len(buf), w)]
+
+    @property
+    def coord_bytes(self) -> int:
+        return self.nbytes
+
+    def element_from_tree(self, buf: bytes, pos: int = 0):
+        """(point, next position) of the point node at ``buf[pos:]`` (the point may be None = infinity, written (-1, -1)); None
+        when there is no node(leaf, leaf) of this group's coordinate width there, or the leaves hold no point of the curve
+        (the import of a one-element array decides: coordinates below p, on the curve)."""
+        cw = self.nbytes
+        end = pos + 15 + 2 * cw
+        node = bytes(buf[pos:end])
+        leaf_hdr = b"\x01" + cw.to_bytes(4, "big")
+        if len(buf) < end or node[:5] != b"\x00\x00\x00\x00\x02" or node[5:10] != leaf_hdr or node[10 + cw:15 + cw] != leaf_hdr:
+            return None
+        try:
+            arr = self.toElementArrayFromByteTree(b"\x00\x00\x00\x00\x01" + node, 1)
+        except (ValueError, VmnError):
+            return None
+        el = arr.get(0)
+        arr.free()
+        return el, end
 
     def _py_mul(self, a, b):
         return self._ec.add(a, b, self.p, self.a)

@@ -77,6 +77,46 @@ def element_tree(group, els: Sequence) -> bytes:
     return _hdr(0, 2) + _hdr(0, half) + b"".join(enc[:half]) + _hdr(0, half) + b"".join(enc[half:])
 
 
+def group_element_tree(enc: bytes, cw: Optional[int] = None) -> bytes:
+    """Byte tree of ONE group element given as its fixed-width encoding (``group.enc_el``).  ``cw`` = None: an element of a
+    modular group, a leaf.  ``cw`` = the coordinate width of a curve group (``ECqPGroup.nbytes``): enc = x || y and the tree is
+    node(leaf(x), leaf(y)) -- what the C++ message container and the array export write for a point; the point at infinity
+    (enc = 2 cw bytes 0xff) comes out as two leaves of 0xff bytes, (-1, -1)."""
+    if cw is None:
+        return leaf(enc)
+    if len(enc) != 2 * cw:
+        raise ValueError("a point is two coordinates of %d bytes" % cw)
+    return _hdr(0, 2) + leaf(enc[:cw]) + leaf(enc[cw:])
+
+
+def array_tree_size(n: int, elem_bytes: int, cw: Optional[int] = None) -> int:
+    """Bytes of the byte tree of an array of n group elements: node(n leaves of elem_bytes) over a modular group, node(n point
+    nodes) = 5 + n (15 + 2 cw) over a curve with coordinate width cw (``vmn_garray_bytetree_size``)."""
+    return 5 + n * (5 + elem_bytes if cw is None else 15 + 2 * cw)
+
+
+def product_element_tree(group, els: Sequence) -> bytes:
+    """``element_tree`` for any kind of group: the same shapes (one element alone: its own tree; node(a, b) at width 1;
+    node(node(w trees), node(w trees)) otherwise) over the trees of the single elements, which are leaves for a modular group
+    and point nodes for a curve (``group.coord_bytes``: the coordinate width, None / absent for a modular group).  Over a
+    modular group the bytes are those of ``element_tree``."""
+    cw = getattr(group, "coord_bytes", None)
+    enc = [group_element_tree(group.enc_el(e), cw) for e in els]
+    if len(enc) == 1:
+        return enc[0]
+    if len(enc) == 2:
+        return _hdr(0, 2) + enc[0] + enc[1]
+    half = len(enc) // 2
+    return _hdr(0, 2) + _hdr(0, half) + b"".join(enc[:half]) + _hdr(0, half) + b"".join(enc[half:])
+
+
+def wide_element_tree(group, els: Sequence) -> bytes:
+    """An element of G^omega given as its omega components: node(omega element trees), the element's own tree at omega = 1."""
+    cw = getattr(group, "coord_bytes", None)
+    enc = [group_element_tree(group.enc_el(e), cw) for e in els]
+    return enc[0] if len(enc) == 1 else _hdr(0, len(enc)) + b"".join(enc)
+
+
 class InstanceHasher(threading.Thread):
     """Streams byte strings and the byte trees of device arrays into one digest, on the context's helper lane.
 

@@ -113,8 +113,9 @@ def _ciphertexts_tree(comps: Sequence[PGroupElementArray]) -> bytes:
 def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0) -> Optional[List[PGroupElementArray]]:
     """The 2w component arrays of a ciphertext list file, parsed (range + membership) on the GPU; None when the file is not
     such a list (the verifier then fails the party, :1446-1460)."""
-    with open(path, "rb") as f:
-        buf = f.read()
+    buf = _read_file(path)
+    if buf is None:
+        return None
     pos = 0
 
     def header(tag, count=None):
@@ -134,15 +135,24 @@ def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0) -> Optiona
                 header(0, width)
             for _ in range(width):
                 n = int.from_bytes(buf[pos + 1:pos + 5], "big")
-                if buf[pos] != 0 or (expected_n and n != expected_n):
+                if len(buf) < pos + 5 or buf[pos] != 0 or (expected_n and n != expected_n):
                     raise ValueError("array node")
-                size = 5 + n * (5 + grp.elem_bytes)
+                size = grp.array_tree_size(n)
                 comps.append(grp.toElementArrayFromByteTree(buf[pos:pos + size], n))
                 pos += size
         if pos != len(buf) or len({c.size() for c in comps}) != 1:
             raise ValueError("trailing bytes")
         return comps
     except (ValueError, native.VmnError):
+        return None
+
+
+def _read_file(path: str) -> Optional[bytes]:
+    """The bytes of a file of the directory; None when it is missing."""
+    try:
+        with open(path, "rb") as f:
+            return f.read()
+    except OSError:
         return None
 
 
@@ -187,10 +197,10 @@ def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequ
     with open(pc_file(nizkp, l), "wb") as f:                                     # "PermutationCommitment" :107-112
         f.write(u_bt)
     d = chal.start(8 * hashlib.new(hn).digest_size)                            # the seed of the batching vector :114-129
-    d.update(fs._hdr(0, 6) + fs.leaf(grp.enc_el(g)))
+    d.update(fs._hdr(0, 6) + grp.element_tree(g))
     d.update(H.toByteTree())
     d.update(u_bt)
-    d.update(fs.element_tree(grp, pkey))
+    d.update(fs.product_element_tree(grp, pkey))
     for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
         with open(path, "rb") as f:
             d.update(f.read())
@@ -219,7 +229,7 @@ def write_inputs(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGro
     with open(_p(nizkp, PARAMS), "w") as f:
         json.dump(params, f, indent=1)
     with open(pk_file(nizkp), "wb") as f:
-        f.write(fs.element_tree(grp, pkey))
+        f.write(fs.product_element_tree(grp, pkey))
     write_ciphertexts(l_file(nizkp, 0), W)
 
 
@@ -251,9 +261,10 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     V = native.PoSBasicTW(grp, NV, NE, NR)
     V.precompute(g, H)                                                         # :857
     V.setInstance(pkey, W, WP)
-    with open(pc_file(nizkp, l), "rb") as f:                                   # :861-866
-        u_bt = f.read()
+    u_bt = _read_file(pc_file(nizkp, l))                                       # :861-866
     try:
+        if u_bt is None:
+            raise ValueError("no permutation commitment")
         U = grp.toElementArrayFromByteTree(u_bt, n)
         if not U.isMember():
             raise ValueError("u outside the group")
@@ -261,10 +272,10 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
         return False
     V.setPermutationCommitment(U)
     d = chal.start(8 * hashlib.new(hn).digest_size)                            # :869-879
-    d.update(fs._hdr(0, 6) + fs.leaf(grp.enc_el(g)))
+    d.update(fs._hdr(0, 6) + grp.element_tree(g))
     d.update(H.toByteTree())
     d.update(u_bt)
-    d.update(fs.element_tree(grp, pkey))
+    d.update(fs.product_element_tree(grp, pkey))
     for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
         with open(path, "rb") as f:
             d.update(f.read())
@@ -274,9 +285,8 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     V.computeAF()                                                              # :886
     tv["PoS.A"] = _hex(V.getA())                                               # :888-889
     tv["PoS.F"] = "(" + ", ".join(_hex(x) for x in V.getF()) + ")"
-    with open(posc_file(nizkp, l), "rb") as f:                                 # :892-895
-        com_bt = f.read()
-    com = V.readCommitment(com_bt, n, width)
+    com_bt = _read_file(posc_file(nizkp, l))                                   # :892-895
+    com = V.readCommitment(com_bt, n, width) if com_bt is not None else None
     if com is None:
         return False
     V.setCommitment(com)
@@ -287,8 +297,8 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     vch = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")      # :905-913
     tv["PoS.v"] = format(vch, "x")                                             # :915
     V.setChallenge(vch)
-    with open(posr_file(nizkp, l), "rb") as f:                                 # :921-925
-        rep = V.readReply(f.read(), n, width)
+    rep_bt = _read_file(posr_file(nizkp, l))                                   # :921-925
+    rep = V.readReply(rep_bt, n, width) if rep_bt is not None else None
     if rep is None:
         return False
     verdict = V.verify(rep)
@@ -396,7 +406,7 @@ def write_precomputation(nizkp: str, l: int, grp, params: dict, n_max: int, rand
         with open(poscc_file(nizkp, l), "wb") as f:
             f.write(bt)
         return bt
-    _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 3) + fs.leaf(grp.enc_el(g)), [H.toByteTree(), u_bt], commit, NV)
+    _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 3) + grp.element_tree(g), [H.toByteTree(), u_bt], commit, NV)
     rep = P.reply(v)
     with open(poscr_file(nizkp, l), "wb") as f:
         f.write(rep.native.toByteTree())
@@ -434,8 +444,8 @@ def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequenc
         with open(ccposc_file(nizkp, l), "wb") as f:
             f.write(bt)
         return bt
-    _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 6) + fs.leaf(grp.enc_el(g)),
-                                  [H_s.toByteTree(), U_s.toByteTree(), fs.element_tree(grp, pkey), l_file(nizkp, l - 1), l_file(nizkp, l)],
+    _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 6) + grp.element_tree(g),
+                                  [H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey), l_file(nizkp, l - 1), l_file(nizkp, l)],
                                   commit, NV)
     rep = P.reply(v)
     with open(ccposr_file(nizkp, l), "wb") as f:
@@ -464,9 +474,10 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     bits = 8 * hashlib.new(hn).digest_size
     g = grp.g
     H = derive_generators(grp, params, rho, n_max)
-    with open(pc_file(nizkp, l), "rb") as f:                                     # readPermutationCommitment :618-636
-        u_bt = f.read()
+    u_bt = _read_file(pc_file(nizkp, l))                                         # readPermutationCommitment :618-636
     try:
+        if u_bt is None:
+            raise ValueError("no permutation commitment")
         U = grp.toElementArrayFromByteTree(u_bt, n_max)
         if not U.isMember():
             raise ValueError("u outside the group")
@@ -475,20 +486,19 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     # ---- verifyPoSC :652-703
     V = native.PoSCBasicTW(grp, NV, NE, NR)
     V.setInstance(g, H, U)
-    seed = chal.challenge(fs._hdr(0, 3) + fs.leaf(grp.enc_el(g)) + H.toByteTree() + u_bt, bits)
+    seed = chal.challenge(fs._hdr(0, 3) + grp.element_tree(g) + H.toByteTree() + u_bt, bits)
     tv["PoSC.s"] = seed.hex()
     V.setBatchVectorSeed(seed)
-    with open(poscc_file(nizkp, l), "rb") as f:
-        com_bt = f.read()
-    com = native.Message.fromByteTree(grp, com_bt, native.PoSCBasicTW._com_kinds, [n_max, 1, n_max, 1, 1])
+    com_bt = _read_file(poscc_file(nizkp, l))
+    com = native.Message.fromByteTree(grp, com_bt, native.PoSCBasicTW._com_kinds, [n_max, 1, n_max, 1, 1]) if com_bt is not None else None
     if com is None:
         return False
     V.setCommitment(com)
     v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")
     tv["PoSC.v"] = format(v, "x")
     V.setChallenge(v)
-    with open(poscr_file(nizkp, l), "rb") as f:
-        rep = native.Message.fromByteTree(grp, f.read(), native.PoSCBasicTW._rep_kinds, [1, n_max, 1, 1, n_max])
+    rep_bt = _read_file(poscr_file(nizkp, l))
+    rep = native.Message.fromByteTree(grp, rep_bt, native.PoSCBasicTW._rep_kinds, [1, n_max, 1, 1, n_max]) if rep_bt is not None else None
     if rep is None:
         return False
     ok_posc = V.verify(rep)
@@ -505,17 +515,17 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     WP = read_ciphertexts(grp, l_file(nizkp, l), width, n)
     if WP is None:
         return False
-    keep = _read_booleans(kl_file(nizkp, l), n_max)
+    keep = _read_booleans(kl_file(nizkp, l), n_max) if os.path.exists(kl_file(nizkp, l)) else None
     if keep is None or sum(keep) != n:                                           # shrinkPermComm :714-746 fails the party
         return False
     U_s, H_s = U.extract(keep), H.copyOfRange(0, n)
     C = native.CCPoSBasicW(grp, NV, NE, NR)
     C.setInstance(g, H_s, U_s, pkey, W, WP)
     d = chal.start(bits)
-    d.update(fs._hdr(0, 6) + fs.leaf(grp.enc_el(g)))
+    d.update(fs._hdr(0, 6) + grp.element_tree(g))
     d.update(H_s.toByteTree())
     d.update(U_s.toByteTree())
-    d.update(fs.element_tree(grp, pkey))
+    d.update(fs.product_element_tree(grp, pkey))
     for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
         with open(path, "rb") as f:
             d.update(f.read())
@@ -525,17 +535,16 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     C.computeAB()
     A, B = C.getAB()
     tv["CCPoS.A"], tv["CCPoS.B"] = _hex(A), "(" + ", ".join(_hex(x) for x in B) + ")"
-    with open(ccposc_file(nizkp, l), "rb") as f:
-        com_bt = f.read()
-    com = native.Message.fromByteTree(grp, com_bt, native.CCPoSBasicW._com_kinds, [1, 2 * width])
+    com_bt = _read_file(ccposc_file(nizkp, l))
+    com = native.Message.fromByteTree(grp, com_bt, native.CCPoSBasicW._com_kinds, [1, 2 * width]) if com_bt is not None else None
     if com is None:
         return False
     C.setCommitment(com)
     v2 = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed2) + com_bt, NV), "big")
     tv["CCPoS.v"] = format(v2, "x")
     C.setChallenge(v2)
-    with open(ccposr_file(nizkp, l), "rb") as f:
-        rep = native.Message.fromByteTree(grp, f.read(), native.CCPoSBasicW._rep_kinds, [1, width, n])
+    rep_bt = _read_file(ccposr_file(nizkp, l))
+    rep = native.Message.fromByteTree(grp, rep_bt, native.CCPoSBasicW._rep_kinds, [1, width, n]) if rep_bt is not None else None
     if rep is None:
         return False
     verdict = C.verify(rep)
@@ -547,7 +556,7 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
 
 
 # =============================================================================================================================
-# Verifiable threshold decryption of the last list (row A6), widths >= 1 over a modular group
+# Verifiable threshold decryption of the last list (row A6), widths >= 1 over a modular group or a curve
 #     <nizkp>/proofs/PolynomialInExponent.bt      the coefficients g^(a_d) of the key's polynomial in the exponent
 #     <nizkp>/proofs/DecryptionFactors%02d.bt     f_l = u^(-x_l / c) of party l     elgamal/DistrElGamalSession.java:574-577
 #     <nizkp>/proofs/DecrFactCommitment%02d.bt    node(y'_l, B'_l)                  :586-589
@@ -557,8 +566,8 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
 # Prover side: DistrElGamalSession.decrypt (:344-545) with every party played here; verifier: the decryption branch of
 # MixNetElGamalVerifyFiatShamirSession.verify (:1545-1667, helpers :1098-1297).  An array of G^omega (the factors, the plaintexts)
 # is node(omega array trees), the array's own tree at omega = 1 -- a part of a ciphertext list file; an element of G^omega (B')
-# is node(omega leaves), a leaf at omega = 1.  Curve sessions are not covered: the directory code hashes a curve point as one
-# leaf, which is not the reference's tree of a point.
+# is node(omega element trees), the element's own tree at omega = 1.  An element's tree is a leaf over a modular group and
+# node(leaf(x), leaf(y)) over a curve (infinity: both leaves 0xff), as in the arrays and messages the library writes.
 # =============================================================================================================================
 def poly_file(nizkp):
     return _p(nizkp, "proofs", "PolynomialInExponent.bt")
@@ -605,7 +614,7 @@ def _read_wide_array(grp, path: str, width: int, n: int) -> Optional[List[PGroup
             if buf[:5] != fs._hdr(0, width):
                 return None
             pos = 5
-        size = 5 + n * (5 + grp.elem_bytes)
+        size = grp.array_tree_size(n)
         comps = []
         for _ in range(width):
             comps.append(grp.toElementArrayFromByteTree(buf[pos:pos + size], n))
@@ -618,24 +627,22 @@ def _read_wide_array(grp, path: str, width: int, n: int) -> Optional[List[PGroup
 
 
 def _wide_element_tree(grp, els) -> bytes:
-    enc = [fs.leaf(grp.enc_el(e)) for e in els]
-    return enc[0] if len(enc) == 1 else fs._hdr(0, len(enc)) + b"".join(enc)
+    return fs.wide_element_tree(grp, els)
 
 
 def _commitment_tree(grp, yp, Bp) -> bytes:
-    return fs._hdr(0, 2) + fs.leaf(grp.enc_el(yp)) + _wide_element_tree(grp, Bp)
+    return fs._hdr(0, 2) + grp.element_tree(yp) + _wide_element_tree(grp, Bp)
 
 
 def _read_commitment(grp, path: str, width: int):
-    """(y', (B'_0 .. B'_(omega-1))) of a commitment file as integers; None when the framing is wrong."""
-    eb = grp.elem_bytes
+    """(y', (B'_0 .. B'_(omega-1))) of a commitment file as group elements; None when the framing is wrong (over a curve also:
+    a leaf that is not of the coordinate width, a point that is not on the curve)."""
     try:
         with open(path, "rb") as f:
             buf = f.read()
     except OSError:
         return None
-    want = 5 + (5 + eb) + ((5 + eb) if width == 1 else 5 + width * (5 + eb))
-    if len(buf) != want or buf[:5] != fs._hdr(0, 2):
+    if buf[:5] != fs._hdr(0, 2):
         return None
     pos, els = 5, []
     for i in range(1 + width):
@@ -643,18 +650,21 @@ def _read_commitment(grp, path: str, width: int):
             if buf[pos:pos + 5] != fs._hdr(0, width):
                 return None
             pos += 5
-        if buf[pos:pos + 5] != fs._hdr(1, eb):
+        got = grp.element_from_tree(buf, pos)
+        if got is None:
             return None
-        els.append(grp.dec_el(buf[pos + 5:pos + 5 + eb]))
-        pos += 5 + eb
+        els.append(got[0])
+        pos = got[1]
+    if pos != len(buf):
+        return None
     return els[0], tuple(els[1:])
 
 
-def eval_polynomial_in_exponent(grp, coeffs: Sequence[int], l: int) -> int:
+def eval_polynomial_in_exponent(grp, coeffs: Sequence, l: int):
     """y_l = prod_d coeffs[d]^(l^d): the public key share of party l (PolynomialInExponent.evaluate)."""
-    acc, power = 1, 1
+    acc, power = grp.ONE, 1
     for c in coeffs:
-        acc = acc * pow(c, power, grp.p) % grp.p
+        acc = grp.k_mul(acc, grp.k_exp(c, power))
         power = power * l % grp.q
     return acc
 
@@ -663,7 +673,7 @@ def _decryption_seed(chal, grp, params, list_bytes: bytes, poly_bt: bytes, facto
     """challenge(node(node(g, ciphertexts), node(polynomial, node(factors of parties 1..k))), 8 * minNoSeedBytes)  :434-461"""
     bits = _prg_seed_bits(params)
     d = chal.start(bits)
-    d.update(fs._hdr(0, 2) + fs._hdr(0, 2) + fs.leaf(grp.enc_el(grp.g)))
+    d.update(fs._hdr(0, 2) + fs._hdr(0, 2) + grp.element_tree(grp.g))
     d.update(list_bytes)
     d.update(fs._hdr(0, 2) + poly_bt + fs._hdr(0, len(factor_trees)))
     for t in factor_trees:
