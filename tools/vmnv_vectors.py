@@ -9,6 +9,16 @@ MixNetElGamalVerifyFiatShamir.java:382-388).
     python tools/vmnv_vectors.py <nizkp dir> -decrypt [--list FILE]      the decryption branch (:1545-1667): Dec.s, Dec.v
     python tools/vmnv_vectors.py --demo <new dir> -decrypt [--width 3] [--parties 3] [--threshold 2]
     python tools/vmnv_vectors.py --demo <new dir> --curve P-256 [--precomputed N_0 | -decrypt]     the same over a named curve
+    python tools/vmnv_vectors.py <nizkp dir> -session [-mix | -shuffle | -decrypt] [-auxsid SID] [-width W] [-nopos | -noposc | -noccpos]
+                                 [-nodec] [-t par,der,bas,PoS] [--arrays]        the WHOLE directory, as `vmnv` verifies it
+    python tools/vmnv_vectors.py --demo <new dir> -session [-mix | -shuffle | -decrypt] [--parties 3] [--threshold 2] [--active 2]
+                                 [--width 1] [--precomputed N_0] [--curve NAME]
+
+-session is MixNetElGamalVerifyFiatShamirSession.verify (:1318-1670) through proofdir.verify_session; the options have the meaning of
+MixNetElGamalVerifyFiatShamirTool.java:562-640, 1015-1044 (expected auxsid "default", expected width 0 = the width of params.json,
+unless given; without -mix / -shuffle / -decrypt the type is taken from the proof).  It prints the TEST VECTOR blocks in the order
+of the session, the per-party ones between the reference's BEGIN PARTY / END PARTY banners, one line per party and the result;
+exit status 0: accepted, 1: rejected, 2: the directory is not a session that can be verified (SessionFormatError).
 
 The directory layout is the reference's (verificatum-vmn_amd/proofdir.py); what `vmnv` reads from the protocol-info XML is
 in <dir>/params.json.  THE diff that would pin parity: on a machine with a JDK + VCR, run `vmnv -t der.rho,PoS ...` on a proof
@@ -42,6 +52,19 @@ DESCRIPTIONS = {                      # MixNetElGamalVerifyFiatShamirTool.java:8
     "PoSC.D": "[not in the reference] PoSC. Derived intermediate values.", "CCPoS.A": "[not in the reference] CCPoS. Batched permutation commitment.",
     "CCPoS.B": "[not in the reference] CCPoS. Batched input ciphertexts.",
     "Dec.s": "Dec. Seed to derive batching vector in hexadecimal notation.", "Dec.v": "Dec. Integer challenge in decimal notation."}
+DESCRIPTIONS.update({             # MixNetElGamalVerifyFiatShamirTool.java:82-150
+    "par.version": "Version.", "par.sid": "Session identifier of mix-net.", "par.k": "Number of mix-servers.",
+    "par.lambda": "Threshold number of parties needed to decrypt.",
+    "par.n_e": "Bit length of components in random vectors used for batching.", "par.n_r": "Bit length of random paddings.",
+    "par.n_v": "Bit length of challenges.", "par.s_PRG": "Description of PRG used for batching.",
+    "par.s_Gq": "Description of underlying group.", "par.s_H": "Description of hash function used to implement random oracles.",
+    "par.omega": "Width of ciphertexts.", "par.N_0": "Number of ciphertexts for which precomputation is done.",
+    "bas.pk": "Joint public key.", "bas.y_l": "Public keys of threshold number of mix-servers.",
+    "bas.L_0": "Original list of ciphertexts.", "bas.L_l": "Intermediate list of ciphertexts.", "u": "Permutation commitment."})
+# the order in which MixNetElGamalVerifyFiatShamirSession.verify prints (:1322-1389); the active threshold is printed under the
+# name par.lambda a second time (:498)
+SESSION_HEAD = ["par.k", "par.lambda", "par.n_e", "par.n_r", "par.n_v", "par.s_PRG", "par.s_Gq", "par.s_H", "par.version", "par.omega",
+                "bas.pk", "bas.y_l", "par.sid", "der.rho", "par.lambda.active", "bas.L_0", "par.N_0", "bas.h"]
 ORDER = ["der.rho", "bas.h", "PoSC.s", "PoSC.v", "PoSC.A", "PoSC.C", "PoSC.D", "CCPoS.s", "CCPoS.A", "CCPoS.B", "CCPoS.v",
          "PoS.s", "PoS.A", "PoS.F", "PoS.B", "PoS.Ap", "PoS.Bp", "PoS.Cp", "PoS.Dp", "PoS.Fp", "PoS.v", "PoS.C",
          "PoS.D", "PoS.k_A", "PoS.k_B", "PoS.k_C", "PoS.k_D", "PoS.k_E", "PoS.k_F", "Dec.s", "Dec.v"]
@@ -102,6 +125,78 @@ def demo_decryption(args, vmn, ctx, proofdir, randomsource, stdgroups):
     print(f"wrote {args.nizkp}: {args.n} ciphertexts of width {width}, {k} parties, threshold {thr}", file=sys.stderr)
 
 
+def block(name, value, printed_as=None):
+    print(f"\nTEST VECTOR\n{printed_as or name} - {DESCRIPTIONS[name]}\n{value}")
+
+
+def demo_session(args, vmn, ctx, proofdir, randomsource, stdgroups):
+    """A synthetic list of -n ciphertexts of width --width, mixed / shuffled / decrypted by --parties parties (threshold
+    --threshold, --active of them shuffling) through proofdir.write_session."""
+    k, thr, width = args.parties, args.threshold, args.width
+    params = demo_params(args, stdgroups)
+    grp = group_of(vmn, ctx, params)
+    q, g = grp.q, grp.g
+    rnd = randomsource.InsecureShaRandomSource(b"vmnv-demo-session", q)
+    coeffs = rnd.ring_array(thr)
+    shares = [None] + [sum(c * pow(l, d, q) for d, c in enumerate(coeffs)) % q for l in range(1, k + 1)]
+    poly = [grp.k_exp(g, c) for c in coeffs]
+    T = [grp.ringArray(rnd.ring_array(args.n)) for _ in range(width)]
+    M = [grp.exp(g, grp.ringArray(rnd.ring_array(args.n))) for _ in range(width)]
+    W = [grp.exp(g, t) for t in T] + [m.mul(grp.exp(poly[0], t)) for m, t in zip(M, T)]
+    typ = proofdir.SHUFFLE_TYPE if args.shuffle else proofdir.DECRYPT_TYPE if args.decrypt else proofdir.MIX_TYPE
+    proofdir.write_session(args.nizkp, grp, params, typ, W, poly[0], randomsource.SecureRandomSource(q), k, thr,
+                           active=args.active or thr, n0=args.precomputed, poly=poly, shares=shares)
+    print(f"wrote {args.nizkp}: a {typ} session, {args.n} ciphertexts of width {width}, {k} parties, threshold {thr}", file=sys.stderr)
+
+
+def session_main(args, vmn, ctx, proofdir):
+    import json
+    with open(os.path.join(args.nizkp, proofdir.PARAMS)) as f:
+        params = json.load(f)
+    grp = group_of(vmn, ctx, params)
+    pos = not args.nopos
+    expected = proofdir.SessionParams(
+        type=proofdir.MIX_TYPE if args.mix else proofdir.SHUFFLE_TYPE if args.shuffle else proofdir.DECRYPT_TYPE if args.decrypt else None,
+        auxsid=args.auxsid, width=args.expected_width, dec=not args.nodec, posc=pos and not args.noposc, ccpos=pos and not args.noccpos)
+    wanted = set(("par,der,bas,PoS,PoSC,CCPoS,Dec" if args.t == "der,PoS" else args.t).split(","))
+    vectors = {}
+    try:
+        verdict = proofdir.verify_session(args.nizkp, grp, params, expected, vectors, with_arrays=args.arrays)
+    except proofdir.SessionFormatError as err:
+        print(f"\nthe directory can not be verified: {err}")
+        sys.exit(2)
+    for name in SESSION_HEAD:
+        if name in vectors and selected(name, wanted):
+            if name == "par.lambda.active":
+                block("par.lambda", vectors[name])
+            else:
+                block(name, vectors[name])
+    for l in range(1, verdict.active_threshold + 1 if verdict.parties else 1):
+        tv = vectors.get("party", {}).get(l)
+        if tv is not None:
+            if "PoS" in wanted:                   # checkPrintTestShuffleBegin("PoS", l)  MixNetElGamalVerifyFiatShamir.java:346-351
+                print(f"\n###################### BEGIN PARTY {l} ######################")
+            for name in ["u"] + [n for n in ORDER if n.startswith("PoSC.")] + ["bas.L_l"] + [n for n in ORDER if n.startswith(("CCPoS.", "PoS."))]:
+                if name in tv and selected(name, wanted):
+                    block(name, tv[name], f"bas.L_{l}" if name == "bas.L_l" else None)
+        if "PoS" in wanted:                       # printTestShuffleEnd, for every l (:1515-1517)
+            print(f"\n####################### END PARTY {l} #######################")
+    for name in ("Dec.s", "Dec.v"):
+        if name in vectors and selected(name, wanted):
+            block(name, vectors[name])
+    print()
+    for p in verdict.parties:
+        failed = [n for n, ok in (("PoSC", p.posc), ("CCPoS", p.ccpos), ("PoS", p.pos)) if ok is False]
+        print(f"party {p.l}: {'valid' if p.verdict else 'INVALID (' + ', '.join(failed) + ')'}" +
+              ("; its output was replaced by its input" if p.replaced else ""))
+    if verdict.params.posc or verdict.params.ccpos:
+        print(f"valid proofs: {verdict.valid_proofs} (threshold {params['threshold']})")
+    if verdict.decryption is not None:
+        print(f"decryption: {'valid' if verdict.decryption else 'INVALID'}; correct indices {verdict.correct}")
+    print(f"verdict of the {verdict.params.type} session: {'accepted' if verdict.accepted else 'REJECTED'}")
+    sys.exit(0 if verdict.accepted else 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("nizkp")
@@ -124,12 +219,30 @@ def main():
     ap.add_argument("--width", type=int, default=1, help="--demo -decrypt: width of the ciphertexts")
     ap.add_argument("--parties", type=int, default=3, help="--demo -decrypt: number of parties k")
     ap.add_argument("--threshold", type=int, default=2, help="--demo -decrypt: parties needed to decrypt")
+    ap.add_argument("-session", "--session", dest="session", action="store_true",
+                    help="verify the whole directory as `vmnv` does: session files, keys, every active party, the decryption")
+    ap.add_argument("-mix", dest="mix", action="store_true", help="-session: check a proof of mixing")
+    ap.add_argument("-shuffle", dest="shuffle", action="store_true", help="-session: check a proof of a shuffle")
+    ap.add_argument("-auxsid", dest="auxsid", default="default", help="-session: the expected auxiliary session identifier")
+    ap.add_argument("-width", dest="expected_width", type=int, default=0,
+                    help="-session: the expected width (default: the width of params.json; negative: the width of the proof)")
+    ap.add_argument("-nopos", dest="nopos", action="store_true", help="-session: do not verify the shuffles")
+    ap.add_argument("-noposc", dest="noposc", action="store_true", help="-session: do not verify the proofs of shuffles of commitments")
+    ap.add_argument("-noccpos", dest="noccpos", action="store_true", help="-session: do not verify the commitment-consistent proofs")
+    ap.add_argument("-nodec", dest="nodec", action="store_true", help="-session: do not verify the decryption")
+    ap.add_argument("--active", type=int, default=0, help="--demo -session: parties that shuffle (default: --threshold)")
     args = ap.parse_args()
+    if args.session and args.nopos and (args.noposc or args.noccpos):
+        ap.error('the option "-nopos" is incompatible with both "-noposc" and "-noccpos"')
     import json
     import __graft_entry__ as entry
     vmn = entry.load_package()
     from verificatum_vmn_amd import proofdir, randomsource, stdgroups
     ctx = vmn.Context(0)
+    if args.session:
+        if args.demo:
+            demo_session(args, vmn, ctx, proofdir, randomsource, stdgroups)
+        session_main(args, vmn, ctx, proofdir)
     if args.demo and args.decrypt:
         demo_decryption(args, vmn, ctx, proofdir, randomsource, stdgroups)
     elif args.demo:

@@ -16,16 +16,27 @@ each message also written to its file); ``verify_shuffle`` is ``MixNetElGamalVer
 PoS.Ap ... PoS.Fp, PoS.v, PoS.C, PoS.D, PoS.k_A ... PoS.k_F).  Both run the proof on the GPU through
 ``native.PoSBasicTW``; the hashing is hashlib on the host over the files' own bytes (they ARE the byte trees).
 
+Above the single links: ``verify_session`` is the standalone verifier itself (MixNetElGamalVerifyFiatShamirSession.verify
+:1318-1670 -- session files, keys, the chain of parties with its replacement rules, the decryption of the last list) and
+``write_session`` plays all parties of a mixing, shuffling or decryption session; see the last part of this file.
+
 What the reference takes from its protocol-info XML (session id, bit lengths, the descriptions of group / PRG / hash
 that go into the global prefix, :158-189) is kept here in ``params.json`` next to the files; the XML itself and the
 bulletin board are out of scope.
 """
 from __future__ import annotations
 
+import dataclasses
 import hashlib
 import json
 import os
-from typing import Dict, List, Optional, Sequence
+import re
+import shutil
+import tempfile
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
+from typing import Callable, Dict, List, Optional, Sequence
 
 from . import PGroupElementArray
 from . import fiatshamir as fs
@@ -116,6 +127,11 @@ def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0) -> Optiona
     buf = _read_file(path)
     if buf is None:
         return None
+    return parse_ciphertexts(grp, buf, width, expected_n)
+
+
+def parse_ciphertexts(grp, buf: bytes, width: int, expected_n: int = 0) -> Optional[List[PGroupElementArray]]:
+    """read_ciphertexts for a list file whose bytes the caller already holds."""
     pos = 0
 
     def header(tag, count=None):
@@ -172,10 +188,12 @@ def _arr(a) -> str:
 
 # ---- prover: PoSTW.prove with nizkp != null ----------------------------------------------------------------------------
 def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], rand,
-                  H: Optional[PGroupElementArray] = None) -> List[PGroupElementArray]:
+                  H: Optional[PGroupElementArray] = None, out_file: Optional[str] = None) -> List[PGroupElementArray]:
     """Party l shuffles the list in l_file(nizkp, l - 1) (given as W) and proves it: re-encryption + permutation
     (ShufflerElGamalSession.java:400-409, 273-278), then PoSTW.prove (:95-165).  Returns w'; writes L_l and the three
-    proof files.  `rand`: the prover's random source (native.RandomSource semantics)."""
+    proof files.  `rand`: the prover's random source (native.RandomSource semantics).  `out_file`: where L_l goes instead of
+    l_file(nizkp, l) (a session's last list, write_session)."""
+    out_file = out_file or l_file(nizkp, l)
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
     NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
     n, width = W[0].size(), len(W) // 2
@@ -191,7 +209,7 @@ def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequ
     prover = native.PoSBasicTW(grp, NV, NE, NR, rand=rand)
     prover.precompute(g, H, pi)
     WP = native.reencrypt_native(grp, pkey, W, S, pi)
-    write_ciphertexts(l_file(nizkp, l), WP)
+    write_ciphertexts(out_file, WP)
     prover.setInstance(pkey, W, WP, S)
     u_bt = prover.u.toByteTree()
     with open(pc_file(nizkp, l), "wb") as f:                                     # "PermutationCommitment" :107-112
@@ -201,7 +219,7 @@ def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequ
     d.update(H.toByteTree())
     d.update(u_bt)
     d.update(fs.product_element_tree(grp, pkey))
-    for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
+    for path in (l_file(nizkp, l - 1), out_file):
         with open(path, "rb") as f:
             d.update(f.read())
     seed = chal.finish(d, 8 * hashlib.new(hn).digest_size)
@@ -241,7 +259,6 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     PoS.k_B, PoS.k_E, bas.h).  A file that cannot be parsed makes the verdict False (the reference substitutes trivial values
     and the equations then fail)."""
     tv = vectors if vectors is not None else {}
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
     width = len(pkey) // 2
     hn = _hashname(params)
     rho = global_prefix(params)
@@ -257,29 +274,61 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     H = derive_generators(grp, params, rho, n)                                 # :557-566
     if with_arrays:
         tv["bas.h"] = _arr(H)
-    g = grp.g
-    V = native.PoSBasicTW(grp, NV, NE, NR)
-    V.precompute(g, H)                                                         # :857
-    V.setInstance(pkey, W, WP)
     u_bt = _read_file(pc_file(nizkp, l))                                       # :861-866
+    U = parse_commitment(grp, u_bt, n)
+    if U is None:
+        return False
+
+    def seed():                                                                # :869-879
+        d = chal.start(8 * hashlib.new(hn).digest_size)
+        d.update(fs._hdr(0, 6) + grp.element_tree(grp.g))
+        d.update(H.toByteTree())
+        d.update(u_bt)
+        d.update(fs.product_element_tree(grp, pkey))
+        for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
+            with open(path, "rb") as f:
+                d.update(f.read())
+        return chal.finish(d, 8 * hashlib.new(hn).digest_size)
+    verdict = pos_core(nizkp, l, grp, params, pkey, W, WP, H, U, seed, tv, with_arrays)
+    for a in W + WP + [H, U]:
+        a.free()
+    return verdict
+
+
+def parse_commitment(grp, u_bt: Optional[bytes], n: int) -> Optional[PGroupElementArray]:
+    """The permutation commitment of a PermutationCommitment%02d.bt file's bytes: n elements of the group; None when the file
+    is missing or is no such array."""
     try:
         if u_bt is None:
             raise ValueError("no permutation commitment")
         U = grp.toElementArrayFromByteTree(u_bt, n)
         if not U.isMember():
             raise ValueError("u outside the group")
+        return U
     except (ValueError, native.VmnError):
-        return False
+        return None
+
+
+def pos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W, WP, H, U, seed, tv: dict, with_arrays: bool = False) -> bool:
+    """verifyPoS on loaded inputs: the lists W and WP, the generators H and the permutation commitment U as device arrays,
+    `seed()` -> the seed of the batching vector (the one value that depends on the lists' and the generators' BYTES).  Reads
+    the party's commitment and reply files; frees nothing it was given."""
+    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
+    n, width = W[0].size(), len(pkey) // 2
+    chal = fs.Challenger(global_prefix(params), _hashname(params))
+    g = grp.g
+    V = native.PoSBasicTW(grp, NV, NE, NR)
+    try:
+        return _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays)
+    finally:
+        V.free()
+
+
+def _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays) -> bool:
+    V.precompute(g, H)                                                         # :857
+    V.setInstance(pkey, W, WP)
     V.setPermutationCommitment(U)
-    d = chal.start(8 * hashlib.new(hn).digest_size)                            # :869-879
-    d.update(fs._hdr(0, 6) + grp.element_tree(g))
-    d.update(H.toByteTree())
-    d.update(u_bt)
-    d.update(fs.product_element_tree(grp, pkey))
-    for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
-        with open(path, "rb") as f:
-            d.update(f.read())
-    seed = chal.finish(d, 8 * hashlib.new(hn).digest_size)
+    seed = seed()
     tv["PoS.s"] = seed.hex()                                                   # :881
     V.setBatchVectorSeed(seed)                                                 # :883
     V.computeAF()                                                              # :886
@@ -308,10 +357,6 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     if with_arrays:
         tv["PoS.k_B"], tv["PoS.k_E"] = _arr(rep.item(1)), _arr(rep.item(4))
     tv["verdicts(A,B,C,D,F)"] = str(V.verdicts)
-    com = rep = None
-    V.free()
-    for a in W + WP + [H, U]:
-        a.free()
     return bool(verdict)
 
 
@@ -417,10 +462,11 @@ def write_precomputation(nizkp: str, l: int, grp, params: dict, n_max: int, rand
 
 
 def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], rand,
-                            pi, R, U, H) -> List[PGroupElementArray]:
+                            pi, R, U, H, out_file: Optional[str] = None) -> List[PGroupElementArray]:
     """The online phase for the N <= N_0 ciphertexts that arrived (W = the list in l_file(nizkp, l - 1)): shrink
     (PermutationCommitment.java:390-471, keep list to its file), re-encrypt and permute (ShufflerElGamalSession.java:789-792),
-    CCPoSW.prove (:75-158).  Returns w'."""
+    CCPoSW.prove (:75-158).  Returns w'.  `out_file`: where L_l goes instead of l_file(nizkp, l)."""
+    out_file = out_file or l_file(nizkp, l)
     NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
     n, width = W[0].size(), len(W) // 2
     hn = _hashname(params)
@@ -432,7 +478,7 @@ def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequenc
     U_s, R_s, H_s = U.extract(keep), R.copyOfRange(0, n), H.copyOfRange(0, n)
     S = [native.random_ring_array_native(grp, rand, n, NR) for _ in range(width)]
     WP = native.reencrypt_native(grp, pkey, W, S, pi_s)
-    write_ciphertexts(l_file(nizkp, l), WP)
+    write_ciphertexts(out_file, WP)
     P = native.CCPoSBasicW(grp, NV, NE, NR, rand=rand)
     P.setInstance(g, H_s, U_s, pkey, W, WP, R_s, pi_s, S)
     box = {}
@@ -445,7 +491,7 @@ def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequenc
             f.write(bt)
         return bt
     _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 6) + grp.element_tree(g),
-                                  [H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey), l_file(nizkp, l - 1), l_file(nizkp, l)],
+                                  [H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey), l_file(nizkp, l - 1), out_file],
                                   commit, NV)
     rep = P.reply(v)
     with open(ccposr_file(nizkp, l), "wb") as f:
@@ -465,7 +511,6 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     `vectors` receives der.rho, PoSC.s, PoSC.v, CCPoS.s, CCPoS.v (the names the reference registers, Tool.java:155-175) and the
     verifiers' intermediates (PoSC.A/C/D, CCPoS.A, CCPoS.B: not printed by the reference; for diffing two builds of this code)."""
     tv = vectors if vectors is not None else {}
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
     width = len(pkey) // 2
     hn = _hashname(params)
     rho = global_prefix(params)
@@ -475,18 +520,62 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     g = grp.g
     H = derive_generators(grp, params, rho, n_max)
     u_bt = _read_file(pc_file(nizkp, l))                                         # readPermutationCommitment :618-636
-    try:
-        if u_bt is None:
-            raise ValueError("no permutation commitment")
-        U = grp.toElementArrayFromByteTree(u_bt, n_max)
-        if not U.isMember():
-            raise ValueError("u outside the group")
-    except (ValueError, native.VmnError):
+    U = parse_commitment(grp, u_bt, n_max)
+    if U is None:
         return False
-    # ---- verifyPoSC :652-703
+    if not posc_core(nizkp, l, grp, params, H, U, n_max,
+                     lambda: chal.challenge(fs._hdr(0, 3) + grp.element_tree(g) + H.toByteTree() + u_bt, bits), tv):
+        return False           # (the reference then takes the generators for u and goes on; a harness stops with the verdict)
+    # ---- the lists, the keep list, verifyCCPoS :757-830
+    W = read_ciphertexts(grp, l_file(nizkp, l - 1), width)
+    if W is None:
+        return False
+    n = W[0].size()
+    WP = read_ciphertexts(grp, l_file(nizkp, l), width, n)
+    if WP is None:
+        return False
+    keep = read_keep_list(nizkp, l, n_max, n)
+    if keep is None:                                                             # shrinkPermComm :714-746 fails the party
+        return False
+    U_s, H_s = U.extract(keep), H.copyOfRange(0, n)
+
+    def seed2():
+        d = chal.start(bits)
+        d.update(fs._hdr(0, 6) + grp.element_tree(g))
+        d.update(H_s.toByteTree())
+        d.update(U_s.toByteTree())
+        d.update(fs.product_element_tree(grp, pkey))
+        for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
+            with open(path, "rb") as f:
+                d.update(f.read())
+        return chal.finish(d, bits)
+    verdict = ccpos_core(nizkp, l, grp, params, pkey, H_s, U_s, W, WP, seed2, tv)
+    for a in W + WP + [H, U, U_s, H_s]:
+        a.free()
+    return verdict
+
+
+def read_keep_list(nizkp: str, l: int, n_max: int, n: int):
+    """The keep list of party l: n_max booleans of which n are set; None when the file is missing or is no such list."""
+    keep = _read_booleans(kl_file(nizkp, l), n_max) if os.path.exists(kl_file(nizkp, l)) else None
+    return keep if keep is not None and sum(keep) == n else None
+
+
+def posc_core(nizkp: str, l: int, grp, params: dict, H, U, n_max: int, seed, tv: dict) -> bool:
+    """verifyPoSC (:652-703) on loaded inputs: the generators H and the permutation commitment U (n_max elements each) as device
+    arrays, `seed()` -> the seed of the batching vector.  Frees nothing it was given."""
+    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
+    chal = fs.Challenger(global_prefix(params), _hashname(params))
     V = native.PoSCBasicTW(grp, NV, NE, NR)
-    V.setInstance(g, H, U)
-    seed = chal.challenge(fs._hdr(0, 3) + grp.element_tree(g) + H.toByteTree() + u_bt, bits)
+    try:
+        return _posc_core(V, nizkp, l, grp, chal, NV, H, U, n_max, seed, tv)
+    finally:
+        V.free()
+
+
+def _posc_core(V, nizkp, l, grp, chal, NV, H, U, n_max, seed, tv) -> bool:
+    V.setInstance(grp.g, H, U)
+    seed = seed()
     tv["PoSC.s"] = seed.hex()
     V.setBatchVectorSeed(seed)
     com_bt = _read_file(poscc_file(nizkp, l))
@@ -503,33 +592,25 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
         return False
     ok_posc = V.verify(rep)
     tv["PoSC.A"], tv["PoSC.C"], tv["PoSC.D"] = _hex(V.getA()), _hex(V.getC()), _hex(V.getD())
-    com = rep = None
-    V.free()
-    if not ok_posc:            # (the reference then takes the generators for u and goes on; a harness stops with the verdict)
-        return False
-    # ---- the lists, the keep list, verifyCCPoS :757-830
-    W = read_ciphertexts(grp, l_file(nizkp, l - 1), width)
-    if W is None:
-        return False
-    n = W[0].size()
-    WP = read_ciphertexts(grp, l_file(nizkp, l), width, n)
-    if WP is None:
-        return False
-    keep = _read_booleans(kl_file(nizkp, l), n_max) if os.path.exists(kl_file(nizkp, l)) else None
-    if keep is None or sum(keep) != n:                                           # shrinkPermComm :714-746 fails the party
-        return False
-    U_s, H_s = U.extract(keep), H.copyOfRange(0, n)
+    return bool(ok_posc)
+
+
+def ccpos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, H_s, U_s, W, WP, seed, tv: dict) -> bool:
+    """verifyCCPoS (:757-830) on loaded inputs: the shrunk generators and permutation commitment and the two lists as device
+    arrays, `seed()` -> the seed of the batching vector.  Frees nothing it was given."""
+    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
+    chal = fs.Challenger(global_prefix(params), _hashname(params))
     C = native.CCPoSBasicW(grp, NV, NE, NR)
-    C.setInstance(g, H_s, U_s, pkey, W, WP)
-    d = chal.start(bits)
-    d.update(fs._hdr(0, 6) + grp.element_tree(g))
-    d.update(H_s.toByteTree())
-    d.update(U_s.toByteTree())
-    d.update(fs.product_element_tree(grp, pkey))
-    for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
-        with open(path, "rb") as f:
-            d.update(f.read())
-    seed2 = chal.finish(d, bits)
+    try:
+        return _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv)
+    finally:
+        C.free()
+
+
+def _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv) -> bool:
+    n, width = W[0].size(), len(pkey) // 2
+    C.setInstance(grp.g, H_s, U_s, pkey, W, WP)
+    seed2 = seed()
     tv["CCPoS.s"] = seed2.hex()
     C.setBatchVectorSeed(seed2)
     C.computeAB()
@@ -547,12 +628,7 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     rep = native.Message.fromByteTree(grp, rep_bt, native.CCPoSBasicW._rep_kinds, [1, width, n]) if rep_bt is not None else None
     if rep is None:
         return False
-    verdict = C.verify(rep)
-    com = rep = None
-    C.free()
-    for a in W + WP + [H, U, U_s, H_s]:
-        a.free()
-    return bool(verdict)
+    return bool(C.verify(rep))
 
 
 # =============================================================================================================================
@@ -764,24 +840,38 @@ def verify_decryption(nizkp: str, grp, params: dict, pkey: Sequence, list_file: 
     (decimal: integerChallenge.toString()) and the public key shares Dec.y_l = poly(l).  A missing file, a file that cannot be
     parsed or too few correct indices give False."""
     tv = vectors if vectors is not None else {}
+    list_bytes = _read_file(list_file)
+    if list_bytes is None or not os.path.exists(poly_file(nizkp)) or not os.path.exists(cr_file(nizkp)):
+        return False
+    W = parse_ciphertexts(grp, list_bytes, len(pkey) // 2)
+    if W is None:
+        return False
+    ok, _ = dec_core(nizkp, grp, params, pkey, W, list_bytes, tv)
+    for a in W:
+        a.free()
+    return ok
+
+
+def dec_core(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], list_bytes, tv: dict):
+    """The decryption branch on a loaded list: its 2 omega component arrays W and the bytes of its tree (what the seed is
+    hashed over).  Returns (verdict, the correct indices read from CorrectIndices.bt or None); frees nothing it was given."""
     NV, NE = int(params["vbitlenro"]), int(params["ebitlenro"])
     k, threshold = int(params["k"]), int(params["threshold"])
     width = len(pkey) // 2
     hn = _hashname(params)
     chal = fs.Challenger(global_prefix(params), hn)
     try:
-        with open(list_file, "rb") as f:
-            list_bytes = f.read()
         with open(poly_file(nizkp), "rb") as f:
             poly_bt = f.read()
         correct = _read_booleans(cr_file(nizkp), k + 1)
     except OSError:
-        return False
+        return False, None
     if correct is None or sum(1 for l in range(1, k + 1) if correct[l]) < threshold:
-        return False
-    W = read_ciphertexts(grp, list_file, width)
-    if W is None:
-        return False
+        return False, correct
+    return _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct), correct
+
+
+def _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct) -> bool:
     n = W[0].size()
     try:
         P = grp.toElementArrayFromByteTree(poly_bt, threshold)
@@ -841,6 +931,705 @@ def verify_decryption(nizkp: str, grp, params: dict, pkey: Sequence, list_file: 
     plain = _read_wide_array(grp, plaintexts_file(nizkp), width, n)
     ok = bool(verdict) and plain is not None and all(a.equals(b) for a, b in zip(plain, computed))
     basic.free()
-    for a in W + comb + computed + (plain or []) + [c for fl in F[1:] for c in fl] + [P]:
+    for a in comb + computed + (plain or []) + [c for fl in F[1:] for c in fl] + [P]:
         a.free()
     return ok
+
+
+# =============================================================================================================================
+# The session: what `vmnv` verifies -- MixNetElGamalVerifyFiatShamirSession.verify (:1318-1670) over a whole directory
+#     <nizkp>/version                  package version                           mixnet/MixNetElGamalSession.java:444
+#     <nizkp>/type                     mixing | shuffling | decryption           :53-63, :423
+#     <nizkp>/auxsid                   auxiliary session identifier              :381
+#     <nizkp>/width                    width of the ciphertexts                  :434
+#     <nizkp>/ShuffledCiphertexts.bt   output of a shuffling session             :403
+#     <nizkp>/proofs/activethreshold   parties active in the shuffle             mixnet/ShufflerElGamalSession.java:1099
+#     <nizkp>/proofs/maxciph           N_0; there iff precomputation was used    :1089, verifier :946
+# The small files are written by VCR's ExtIO (unsafeWriteString / unsafeWriteInt), which is not part of the reference tree:
+# [NOT-IN-REF].  Here: strings as UTF-8 text without a trailing newline, integers in decimal; surrounding whitespace is
+# stripped on read.
+# =============================================================================================================================
+MIX_TYPE, SHUFFLE_TYPE, DECRYPT_TYPE = "mixing", "shuffling", "decryption"
+
+
+class SessionFormatError(Exception):
+    """The reference's failStop: the directory is not a session this verifier can check (a missing or inconsistent session
+    file, a key that does not fit).  Not a verdict: a proof that does not verify gives a SessionVerdict, never this."""
+
+
+def version_file(nizkp):
+    return _p(nizkp, "version")
+
+
+def type_file(nizkp):
+    return _p(nizkp, "type")
+
+
+def auxsid_file(nizkp):
+    return _p(nizkp, "auxsid")
+
+
+def width_file(nizkp):
+    return _p(nizkp, "width")
+
+
+def ls_file(nizkp):
+    return _p(nizkp, "ShuffledCiphertexts.bt")
+
+
+def at_file(nizkp):
+    return _p(nizkp, "proofs", "activethreshold")
+
+
+def mc_file(nizkp):
+    return _p(nizkp, "proofs", "maxciph")
+
+
+def write_string(path: str, value: str) -> None:
+    """A small session file ([NOT-IN-REF]: ExtIO's own format is VCR code): UTF-8 text, no trailing newline."""
+    with open(path, "wb") as f:
+        f.write(value.encode("utf-8"))
+
+
+def write_int(path: str, value: int) -> None:
+    write_string(path, "%d" % value)
+
+
+def read_string(path: str) -> str:
+    """The text of a small session file without surrounding whitespace.  Raises FileNotFoundError / OSError / UnicodeError."""
+    with open(path, "rb") as f:
+        return f.read().decode("utf-8").strip()
+
+
+def _small(path: str, missing: str, unreadable: str) -> str:
+    try:
+        return read_string(path)
+    except FileNotFoundError:
+        raise SessionFormatError(missing) from None
+    except (OSError, UnicodeError):
+        raise SessionFormatError(unreadable) from None
+
+
+def _small_int(path: str, missing: str, unreadable: str, unparsable: str) -> int:
+    text = _small(path, missing, unreadable)
+    if not re.fullmatch(r"[+-]?[0-9]+", text):              # Integer.parseInt
+        raise SessionFormatError(unparsable)
+    return int(text)
+
+
+@dataclasses.dataclass(frozen=True)
+class SessionParams:
+    """mixnet/SessionParams.java: what the caller expects of a session (type None / auxsid None: take the proof's; width -1:
+    take the proof's, 0: it must be the default width, > 0: it must be this) and which parts are verified."""
+    type: Optional[str] = None
+    auxsid: Optional[str] = None
+    width: int = -1
+    dec: bool = True
+    posc: bool = True
+    ccpos: bool = True
+
+
+def verify_version(nizkp: str, params: dict, tv: dict) -> str:
+    """verifyVersion (:295-318) against params["version"]."""
+    version = _small(version_file(nizkp), "Can not find version file in proof directory!", "Can not read version from file!")
+    if version != params["version"]:
+        raise SessionFormatError("Expected package version %s but the proof was created by a package with version %s!"
+                                 % (params["version"], version))
+    tv["par.version"] = version
+    return version
+
+
+def determine_type(nizkp: str, expected: Optional[str]) -> str:
+    """determineType (:327-358)."""
+    actual = _small(type_file(nizkp), "Can not find type file in proof directory!", "Can not read type from type file!")
+    if actual not in (MIX_TYPE, SHUFFLE_TYPE, DECRYPT_TYPE):
+        raise SessionFormatError("Unknown type of proof! (%s)" % actual)
+    if expected is not None and actual != expected:
+        raise SessionFormatError("Attempting to verify proof of %s, but proof is a proof of %s!" % (expected, actual))
+    return actual
+
+
+def determine_auxsid(nizkp: str, expected: Optional[str]) -> str:
+    """determineAuxsid (:369-396); Protocol.validateSid is VCR code ([NOT-IN-REF]): letters, digits and underscore."""
+    actual = _small(auxsid_file(nizkp), "Can not find auxsid file in proof directory!", "Can not read auxsid from file!")
+    if not re.fullmatch(r"[A-Za-z0-9_]+", actual):
+        raise SessionFormatError("Invalid auxiliary session identifier in the proof! (%s)" % actual)
+    if expected is not None and actual != expected:
+        raise SessionFormatError("The given auxiliary session identifier does not match the one in the proof!")
+    return actual
+
+
+def determine_width(nizkp: str, expected: int, default: int, tv: dict) -> int:
+    """determineWidth (:409-457): expected < 0 takes the proof's width, 0 matches it against the default, > 0 against itself."""
+    actual = _small_int(width_file(nizkp), "Can not find width file in proof directory!", "Can not read width from file!",
+                        "Can not parse width given in file!")
+    if expected > 0:
+        if actual != expected:
+            raise SessionFormatError("The given width does not match the width in the proof!")
+    elif expected == 0 and actual != default:
+        raise SessionFormatError("The width in proof does not match the width in the protocol info file! Use the \"-width\" "
+                                 "option to specify the width for which verification is performed.")
+    if actual <= 0:
+        raise SessionFormatError("Width is not positive!")
+    tv["par.omega"] = str(actual)
+    return actual
+
+
+def determine_active_threshold(nizkp: str, threshold: int, k: int, tv: dict) -> int:
+    """determineActiveThreshold (:465-501).  The reference prints it under the name par.lambda, which :1323 has already used for
+    the threshold; here the threshold keeps par.lambda and the active threshold goes to vectors["par.lambda.active"]."""
+    active = _small_int(at_file(nizkp), "Can not find active threshold file in proof directory!",
+                        "Can not read active threshold from file!", "Can not parse active threshold given in file!")
+    if active > k:
+        raise SessionFormatError("Active threshold is larger than the number of mix-servers!")
+    if active < threshold:
+        raise SessionFormatError("Active threshold is smaller than threshold!")
+    tv["par.lambda.active"] = str(active)
+    return active
+
+
+def read_maxciph(nizkp: str, tv: dict) -> int:
+    """readMaxciph (:509-530)."""
+    n0 = _small_int(mc_file(nizkp), "Can not find maxciph file in proof directory!", "Can not read from maxciph file!",
+                    "Can not parse maxciph file!")
+    tv["par.N_0"] = str(n0)
+    return n0
+
+
+def determine_session_params(nizkp: str, params: dict, expected: SessionParams, tv: dict) -> SessionParams:
+    """determineSessionParams (:984-1006): a shuffling session has no decryption, a decryption session no shuffle; the width is
+    only looked at when ciphertexts are."""
+    typ = determine_type(nizkp, expected.type)
+    auxsid = determine_auxsid(nizkp, expected.auxsid)
+    width, dec, posc, ccpos = expected.width, expected.dec, expected.posc, expected.ccpos
+    if typ == SHUFFLE_TYPE:
+        dec = False
+    elif typ == DECRYPT_TYPE:
+        posc = ccpos = False
+    if ccpos or dec:
+        width = determine_width(nizkp, expected.width, int(params.get("width", 1)), tv)
+    return SessionParams(typ, auxsid, width, dec, posc, ccpos)
+
+
+@dataclasses.dataclass
+class PartyVerdict:
+    """One active party of the shuffle: its verdict as the loop (:1397-1518) computes it and the proofs behind it (None: not
+    part of this flow or not looked at)."""
+    l: int
+    verdict: bool = True
+    posc: Optional[bool] = None
+    ccpos: Optional[bool] = None
+    pos: Optional[bool] = None
+    replaced: bool = False
+
+
+@dataclasses.dataclass
+class SessionVerdict:
+    """What verify_session found.  `params`: the determined SessionParams; `parties`: one PartyVerdict per ACTIVE party, in
+    order; `replaced`: the parties whose output was replaced by their input; `valid_proofs`: validProofs of :1394-1512;
+    `decryption` / `correct`: the decryption's verdict and the correct indices it read (None when not verified).
+    `accepted` is THIS LIBRARY's summary, not a value of the reference (which prints "Too few proofs are valid" as information
+    and goes on, :1531-1534): enough valid proofs where shuffles were verified, and a valid decryption where it was."""
+    params: SessionParams
+    active_threshold: int
+    precomp: bool
+    parties: List[PartyVerdict]
+    replaced: frozenset
+    valid_proofs: int
+    decryption: Optional[bool]
+    correct: Optional[List[bool]]
+    accepted: bool
+
+    @property
+    def verdicts(self) -> List[bool]:
+        return [p.verdict for p in self.parties]
+
+
+@dataclasses.dataclass
+class SessionEngines:
+    """The proof engines run_session drives.  Every one takes the session context `ctx` (nizkp, grp, params with the proof's
+    auxsid, pkey = the widened key) first; device arrays are opaque to the control flow.
+        read_pkey(ctx, path) -> [g', y] | None                 read_poly(ctx, path, threshold) -> coefficients | None
+        read_list(ctx, path, data, width, n) -> list | None     (n = 0: any size)      list_size(ctx, list) -> N
+        derive_generators(ctx, rho, n) -> (H, bytes of H's tree)                        copy_range(ctx, array, n) -> array
+        read_commitment(ctx, data, n) -> U | None               shrink(ctx, l, U, n_max, n) -> U_s | None
+        verify_posc(ctx, l, H, U, n_max, seed, tv) -> bool      verify_ccpos(ctx, l, H_s, U_s, W, WP, seed, tv) -> bool
+        verify_pos(ctx, l, H, U, W, WP, seed, tv, with_arrays) -> bool
+        verify_dec(ctx, W, data, tv) -> (bool, correct indices | None)
+        hash_seed(ctx, kind, l, parts) -> seed bytes            (kind: "PoS" | "PoSC" | "CCPoS"; runs on worker threads)
+        show(ctx, array) -> text                                free(ctx, arrays) -> None
+    `seed` is a function without arguments: the engine calls it where the reference derives the seed."""
+    read_pkey: Callable
+    read_poly: Callable
+    read_list: Callable
+    list_size: Callable
+    derive_generators: Callable
+    copy_range: Callable
+    read_commitment: Callable
+    shrink: Callable
+    verify_posc: Callable
+    verify_ccpos: Callable
+    verify_pos: Callable
+    verify_dec: Callable
+    hash_seed: Callable
+    show: Callable
+    free: Callable
+
+
+# ---- the engines on the GPU ---------------------------------------------------------------------------------------------------
+def _gpu_read_pkey(ctx, path):
+    buf = _read_file(path)
+    if buf is None or buf[:5] != fs._hdr(0, 2):
+        return None
+    pos, els = 5, []
+    for _ in range(2):
+        got = ctx.grp.element_from_tree(buf, pos)
+        if got is None:
+            return None
+        els.append(got[0])
+        pos = got[1]
+    return els if pos == len(buf) else None
+
+
+def _gpu_read_poly(ctx, path, threshold):
+    buf = _read_file(path)
+    try:
+        if buf is None:
+            return None
+        P = ctx.grp.toElementArrayFromByteTree(buf, threshold)
+        coeffs = P.toInts() if P.isMember() else None
+        P.free()
+        return coeffs
+    except (ValueError, native.VmnError):
+        return None
+
+
+def _gpu_derive_generators(ctx, rho, n):
+    H = derive_generators(ctx.grp, ctx.params, rho, n)
+    return H, H.toByteTree()
+
+
+def _gpu_shrink(ctx, l, U, n_max, n):
+    keep = read_keep_list(ctx.nizkp, l, n_max, n)
+    return U.extract(keep) if keep is not None else None
+
+
+def _gpu_hash_seed(ctx, kind, l, parts):
+    hn = _hashname(ctx.params)
+    chal = fs.Challenger(global_prefix(ctx.params), hn)
+    bits = 8 * hashlib.new(hn).digest_size
+    d = chal.start(bits)
+    for part in parts:
+        d.update(part)
+    return chal.finish(d, bits)
+
+
+def _gpu_free(ctx, arrays):
+    for a in arrays:
+        a.free()
+
+
+GPU_ENGINES = SessionEngines(
+    read_pkey=_gpu_read_pkey, read_poly=_gpu_read_poly,
+    read_list=lambda ctx, path, data, width, n: parse_ciphertexts(ctx.grp, data, width, n),
+    list_size=lambda ctx, comps: comps[0].size(),
+    derive_generators=_gpu_derive_generators,
+    copy_range=lambda ctx, a, n: a.copyOfRange(0, n),
+    read_commitment=lambda ctx, data, n: parse_commitment(ctx.grp, data, n),
+    shrink=_gpu_shrink,
+    verify_posc=lambda ctx, l, H, U, n_max, seed, tv: posc_core(ctx.nizkp, l, ctx.grp, ctx.params, H, U, n_max, seed, tv),
+    verify_ccpos=lambda ctx, l, H_s, U_s, W, WP, seed, tv: ccpos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, H_s, U_s, W, WP, seed, tv),
+    verify_pos=lambda ctx, l, H, U, W, WP, seed, tv, with_arrays: pos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, W, WP, H, U, seed, tv, with_arrays),
+    verify_dec=lambda ctx, W, data, tv: dec_core(ctx.nizkp, ctx.grp, ctx.params, ctx.pkey, W, data, tv),
+    hash_seed=_gpu_hash_seed,
+    show=lambda ctx, a: "(" + ", ".join(_arr(c) for c in a) + ")" if isinstance(a, list) else _arr(a),
+    free=_gpu_free)
+
+
+# ---- files read once, seeds hashed ahead ------------------------------------------------------------------------------------------
+class _Files:
+    """The bytes of the directory's big files, each read once, for the protocol thread and the hashing threads alike."""
+
+    def __init__(self):
+        self._lock, self._data = threading.Lock(), {}
+
+    def get(self, path: str) -> Optional[bytes]:
+        with self._lock:
+            if path not in self._data:
+                self._data[path] = _read_file(path)
+            return self._data[path]
+
+    def drop(self, path: str) -> None:
+        with self._lock:
+            self._data.pop(path, None)
+
+
+class _List:
+    """One list file of the session: its bytes (what seeds are hashed over) and, once imported, its arrays.  The SAME object is
+    the output of party l and the input of party l + 1, and the input object itself stands in for an output that is replaced."""
+
+    def __init__(self, path: str, files: _Files):
+        self.path, self.files, self.comps, self._tried = path, files, None, False
+
+    def data(self) -> Optional[bytes]:
+        return self.files.get(self.path)
+
+    def load(self, ctx, eng, width: int, n: int):
+        if not self._tried:
+            self._tried = True
+            data = self.data()
+            self.comps = eng.read_list(ctx, self.path, data, width, n) if data is not None else None
+        return self.comps
+
+    def release(self, ctx, eng) -> None:
+        if self.comps is not None:
+            eng.free(ctx, self.comps)
+        self.comps = None
+        self.files.drop(self.path)
+
+
+HASH_THREADS = 4
+
+
+class _SeedsAhead:
+    """Seeds of later parties, hashed on worker threads (hashlib releases the GIL) while the GPU verifies the party before them.
+    A seed depends on files alone, except that the input of party l + 1 is party l's input when party l fails: every job records
+    what it assumed, and `take` throws the job's result away unless that is what the party is verified with."""
+
+    def __init__(self, enabled: bool, stats: Optional[dict]):
+        self.pool = ThreadPoolExecutor(max_workers=HASH_THREADS) if enabled else None
+        self.jobs, self.stats = {}, stats if stats is not None else {}
+        self.stats.setdefault("ahead", [])
+        self.stats.setdefault("used", [])
+        self.stats.setdefault("discarded", [])
+
+    def submit(self, key, assumed: tuple, job: Callable) -> None:
+        if self.pool is not None and key not in self.jobs:
+            self.stats["ahead"].append(key)
+            self.jobs[key] = (assumed, self.pool.submit(job))
+
+    def take(self, key, actual: tuple, job: Callable) -> bytes:
+        got = self.jobs.pop(key, None)
+        if got is not None:
+            assumed, fut = got
+            if len(assumed) == len(actual) and all(a is b for a, b in zip(assumed, actual)):
+                seed = fut.result()
+                if seed is not None:
+                    self.stats["used"].append(key)
+                    return seed
+            else:
+                fut.cancel()
+                self.stats["discarded"].append(key)
+        return job()
+
+    def close(self) -> None:
+        if self.pool is not None:
+            self.pool.shutdown(wait=True, cancel_futures=True)
+
+
+def _tree_prefix(grp, bt: bytes, n: int) -> bytes:
+    """toByteTree() of copyOfRange(0, n) of the array whose tree is bt."""
+    size = grp.array_tree_size(1) - 5
+    return fs._hdr(0, n) + bt[5:5 + n * size]
+
+
+def _tree_extract(grp, bt: bytes, keep: Sequence[bool]) -> bytes:
+    """toByteTree() of extract(keep) of the array whose tree is bt."""
+    size = grp.array_tree_size(1) - 5
+    return fs._hdr(0, sum(keep)) + b"".join(bt[5 + i * size:5 + (i + 1) * size] for i, kept in enumerate(keep) if kept)
+
+
+_FROM_FILE, _FROM_GENERATORS = object(), object()
+
+
+def run_session(nizkp: str, grp, params: dict, expected: SessionParams, eng: SessionEngines,
+                vectors: Optional[dict] = None, with_arrays: bool = False, stats: Optional[dict] = None) -> SessionVerdict:
+    """The control flow of MixNetElGamalVerifyFiatShamirSession.verify (:1318-1670) over the engines `eng`: session files, keys,
+    generators once, the chain of parties with its replacement rules, the decryption of the list the chain ends in.  See
+    verify_session.  `stats` (a dict) receives which seeds were hashed ahead, used and discarded."""
+    tv = vectors if vectors is not None else {}
+    k, threshold = int(params["k"]), int(params["threshold"])
+    tv["par.k"], tv["par.lambda"] = str(k), str(threshold)                         # :1322-1331
+    tv["par.n_e"], tv["par.n_r"], tv["par.n_v"] = str(int(params["ebitlenro"])), str(int(params["rbitlen"])), str(int(params["vbitlenro"]))
+    tv["par.s_PRG"], tv["par.s_Gq"], tv["par.s_H"] = params["prg"], params["pgroup"], params["rohash"]
+    verify_version(nizkp, params, tv)                                              # :1335
+    sp = determine_session_params(nizkp, params, expected, tv)                     # :1338
+    params = dict(params, auxsid=sp.auxsid)
+    width = sp.width
+    ctx = SimpleNamespace(nizkp=nizkp, grp=grp, params=params, pkey=None)
+    # ---- readFullPKey :194-234
+    if not os.path.exists(pk_file(nizkp)):
+        raise SessionFormatError("Joint public key file %s can not be found!" % pk_file(nizkp))
+    pk = eng.read_pkey(ctx, pk_file(nizkp))
+    if pk is None:
+        raise SessionFormatError("Could not read full El Gamal public key from file! (%s)" % pk_file(nizkp))
+    tv["bas.pk"] = "(" + _hex(pk[0]) + ", " + _hex(pk[1]) + ")"
+    if pk[0] != grp.g:
+        raise SessionFormatError("Basic public key is not the standard generator!")
+    if width > 0:
+        ctx.pkey = [pk[0]] * width + [pk[1]] * width                               # ProtocolElGamal.getWidePublicKey
+    # ---- readMixServerPKeys :239-287
+    if sp.dec:
+        poly = eng.read_poly(ctx, poly_file(nizkp), threshold)
+        if poly is None:
+            raise SessionFormatError("Unable to read polynomial in exponent from file! (%s)" % poly_file(nizkp))
+        ys = [None] + [eval_polynomial_in_exponent(grp, poly, l) for l in range(1, k + 1)]
+        if pk[1] != poly[0]:
+            raise SessionFormatError("Mismatching public keys!")
+        tv["bas.y_l"] = "(" + ",".join(_hex(ys[l]) for l in range(1, threshold + 1)) + ")"
+    # ---- the global prefix :158-189, :1351
+    tv["par.sid"] = params["sid"]
+    rho = global_prefix(params)
+    tv["der.rho"] = rho.hex()
+    precomp = os.path.exists(mc_file(nizkp))                                       # :946
+    active = determine_active_threshold(nizkp, threshold, k, tv)                   # :1357
+    files = _Files()
+    # ---- readCiphertexts :1017-1046
+    first = None
+    if sp.ccpos or sp.dec:
+        original = sp.ccpos or sp.type == DECRYPT_TYPE
+        # otherwise the decryption alone of a directory that was mixed: start from the end of the shuffling
+        path = l_file(nizkp, 0 if original else active)
+        if original and not os.path.exists(path):
+            raise SessionFormatError("Can not find array file! (%s)" % path)
+        if os.path.exists(path):
+            first = _List(path, files)
+            if first.load(ctx, eng, width, 0) is None:
+                raise SessionFormatError("Unable to read array %s!" % os.path.basename(path))
+            if with_arrays:
+                tv["bas.L_0"] = eng.show(ctx, first.comps)
+    parties: List[PartyVerdict] = []
+    replaced = set()
+    valid = 0
+    inp = first
+    if sp.posc or sp.ccpos:
+        if precomp:
+            maxciph = read_maxciph(nizkp, tv)                                      # getMaxciph :541-548
+        elif first is None:
+            raise SessionFormatError("No ciphertexts to take the number of generators from!")   # (the reference dereferences null)
+        else:
+            maxciph = eng.list_size(ctx, first.comps)
+        n = eng.list_size(ctx, first.comps) if first is not None else 0
+        if n > maxciph:
+            raise SessionFormatError("Too few generators have been derived!")      # :572-574
+        H, H_bt = eng.derive_generators(ctx, rho, maxciph)                         # deriveGenerators :556-576, once
+        if with_arrays:
+            tv["bas.h"] = eng.show(ctx, H)
+        H_s = eng.copy_range(ctx, H, n) if sp.ccpos and precomp else None          # getShrunkGenerators :1059-1068
+        env = os.environ.get("VMN_SESSION_HASH_AHEAD", "1")
+        ahead = _SeedsAhead(env != "0", stats)
+        g_tree = grp.element_tree(grp.g)
+        pk_tree = fs.product_element_tree(grp, ctx.pkey) if ctx.pkey else None
+        posc_active = lambda l: os.path.exists(pc_file(nizkp, l))                  # :958-962
+        ccpos_active = lambda l: os.path.exists(ccposc_file(nizkp, l)) or os.path.exists(posc_file(nizkp, l))      # :972-976
+        is_active = lambda l: (sp.posc and precomp and not sp.ccpos and posc_active(l)) or ccpos_active(l)
+
+        def out_list(l):
+            path = l_file(nizkp, l)
+            if l == active and not os.path.exists(path):                           # :1446-1449
+                path = ls_file(nizkp)
+            return _List(path, files)
+        outs = {l: out_list(l) for l in range(1, active + 1)} if sp.ccpos else {}
+
+        def commitment_bytes(l, source):
+            return files.get(pc_file(nizkp, l)) if source is _FROM_FILE else H_bt
+
+        def posc_job(l):
+            def job():
+                u_bt = files.get(pc_file(nizkp, l))
+                return eng.hash_seed(ctx, "PoSC", l, [fs._hdr(0, 3) + g_tree, H_bt, u_bt]) if u_bt is not None else None
+            return job
+
+        def shuffle_job(l, src, dst, source):
+            """The seed of party l's PoS / CCPoS over the lists src -> dst and the commitment read from `source`."""
+            def job():
+                u_bt, a, b = commitment_bytes(l, source), src.data(), dst.data()
+                if u_bt is None or a is None or b is None:
+                    return None
+                if not precomp:
+                    return eng.hash_seed(ctx, "PoS", l, [fs._hdr(0, 6) + g_tree, H_bt, u_bt, pk_tree, a, b])
+                keep = read_keep_list(nizkp, l, maxciph, n)
+                if keep is None:
+                    return None
+                return eng.hash_seed(ctx, "CCPoS", l, [fs._hdr(0, 6) + g_tree, _tree_prefix(grp, H_bt, n), _tree_extract(grp, u_bt, keep),
+                                                       pk_tree, a, b])
+            return job
+
+        def hash_ahead(l, src):
+            """Start on party l's seeds, assuming the party before it is valid (its input is then `src`)."""
+            if l <= active and is_active(l):
+                if sp.posc and precomp:
+                    ahead.submit(("PoSC", l), (), posc_job(l))
+                if sp.ccpos:
+                    ahead.submit(("shuffle", l), (src, outs[l], _FROM_FILE), shuffle_job(l, src, outs[l], _FROM_FILE))
+        try:
+            hash_ahead(1, inp)
+            for l in range(1, active + 1):                                         # :1397-1518
+                verdict = True
+                if is_active(l):
+                    ptv = tv.setdefault("party", {}).setdefault(l, {})
+                    pv = PartyVerdict(l)
+                    source = _FROM_FILE
+                    U = eng.read_commitment(ctx, files.get(pc_file(nizkp, l)), maxciph)      # readPermutationCommitment :626-641
+                    if with_arrays and U is not None:
+                        ptv["u"] = eng.show(ctx, U)
+                    hash_ahead(l + 1, outs.get(l))
+                    if sp.posc and precomp:                                        # :1416-1437
+                        pv.posc = U is not None and bool(eng.verify_posc(ctx, l, H, U, maxciph,
+                                                                         lambda: ahead.take(("PoSC", l), (), posc_job(l)), ptv))
+                        if not pv.posc:
+                            verdict = False
+                            if U is not None:
+                                eng.free(ctx, [U])
+                            U, source = eng.copy_range(ctx, H, maxciph), _FROM_GENERATORS
+                    if sp.ccpos:
+                        out = outs[l]
+                        WP = out.load(ctx, eng, width, n)                          # :1446-1451
+                        if with_arrays and WP is not None:
+                            ptv["bas.L_l"] = eng.show(ctx, WP)
+                        seed = lambda: ahead.take(("shuffle", l), (inp, out, source), shuffle_job(l, inp, out, source))
+                        if precomp:                                                # :1457-1477
+                            U_s = eng.shrink(ctx, l, U, maxciph, n) if U is not None and WP is not None else None
+                            pv.ccpos = U_s is not None and bool(eng.verify_ccpos(ctx, l, H_s, U_s, inp.comps, WP, seed, ptv))
+                            verdict = verdict and pv.ccpos
+                            if U_s is not None:
+                                eng.free(ctx, [U_s])
+                        else:                                                      # :1481-1487
+                            pv.pos = U is not None and WP is not None and \
+                                bool(eng.verify_pos(ctx, l, H, U, inp.comps, WP, seed, ptv, with_arrays))
+                            verdict = pv.pos
+                        if verdict:
+                            inp.release(ctx, eng)
+                            inp = out
+                        else:                                                      # :1494-1502: the input itself, not a re-read
+                            out.release(ctx, eng)
+                            pv.replaced = True
+                            replaced.add(l)
+                    if U is not None:
+                        eng.free(ctx, [U])
+                    if verdict:
+                        valid += 1
+                    pv.verdict = verdict
+                    parties.append(pv)
+        finally:
+            ahead.close()
+        eng.free(ctx, [H] + ([H_s] if H_s is not None else []))
+    accepted = not (sp.posc or sp.ccpos) or valid >= threshold                     # :1531-1534 prints and goes on
+    dec_verdict = correct = None
+    if sp.dec:                                                                     # :1537-1667
+        if inp is None:
+            raise SessionFormatError("Can not find array file! (%s)" % l_file(nizkp, active))
+        dec_verdict, correct = eng.verify_dec(ctx, inp.comps, inp.data(), tv)
+        dec_verdict = bool(dec_verdict)
+        accepted = accepted and dec_verdict
+    if inp is not None:
+        inp.release(ctx, eng)
+    return SessionVerdict(sp, active, precomp, parties, frozenset(replaced), valid, dec_verdict, correct, accepted)
+
+
+def verify_session(nizkp: str, grp, params: dict, expected: SessionParams = SessionParams(), vectors: Optional[dict] = None,
+                   with_arrays: bool = False) -> SessionVerdict:
+    """What `vmnv` does with a proof directory (MixNetElGamalVerifyFiatShamirSession.verify :1318-1670), on the GPU:
+    the session files (version, type, auxsid, width, proofs/activethreshold, proofs/maxciph), the keys (FullPublicKey.bt =
+    (g, y) at width 1, widened here; with a decryption the polynomial in the exponent, whose element 0 is y), the generators
+    derived ONCE for maxciph, the chain L_0 -> L_1 -> ... of the active parties -- a failed PoSC sets the commitment to the
+    generators and costs the verdict, a failed shuffle replaces the party's output by its input, the last output falls back to
+    ShuffledCiphertexts.bt -- the count of valid proofs, the decryption of the list the chain ends in, Plaintexts.bt.
+
+    A violated session check (the reference's failStop) raises SessionFormatError.  A per-party file that is missing or cannot
+    be parsed (commitment, list, keep list, proof message) FAILS THAT PARTY, as verify_shuffle / verify_precomputed_shuffle do;
+    the reference stops at some of these (readArray :588-616).  k, threshold, version, the default width and what goes into
+    der.rho come from `params` (params.json); the auxsid is the proof's.
+
+    Every list file is read and imported once; the generators' tree is exported once; the seeds of party l + 1 are hashed on up
+    to HASH_THREADS worker threads while party l is verified (VMN_SESSION_HASH_AHEAD=0, read per call, turns that off: same
+    verdicts, same vectors).  Two parts of the reference's output are not produced: bas.C_omega / bas.R_omega / bas.M_omega
+    (VCR's toString() of groups, [NOT-IN-REF]).
+
+    `vectors` receives, in the reference's names: par.k, par.lambda (the threshold), par.lambda.active (the active threshold,
+    which the reference prints under par.lambda a second time, :498), par.n_e, par.n_r, par.n_v, par.s_PRG, par.s_Gq, par.s_H,
+    par.version, par.omega, par.N_0, par.sid, bas.pk, bas.y_l, der.rho, Dec.*; with `with_arrays` bas.h and bas.L_0; and
+    vectors["party"][l] = the PoS.* / PoSC.* / CCPoS.* vectors of party l (with `with_arrays` also u and bas.L_l)."""
+    return run_session(nizkp, grp, params, expected, GPU_ENGINES, vectors, with_arrays)
+
+
+# ---- the writer: all k parties of a session -----------------------------------------------------------------------------------------
+def write_session(nizkp: str, grp, params: dict, session_type: str, W: Sequence, y, rand, k: int, threshold: int,
+                  active: Optional[int] = None, n0: int = 0, failing=(), poly: Optional[Sequence] = None,
+                  shares: Optional[Sequence] = None, writers=None):
+    """Every party of a session of `session_type` (mixing / shuffling / decryption) on the list W (2 * width component arrays)
+    under the key (g, y), y = poly[0]: write_inputs, then for the active parties l = 1 .. `active` (default: threshold)
+    write_shuffle, or with n0 > 0 write_precomputation for N_0 = n0 and write_committed_shuffle, then write_decryption with `poly`
+    and `shares` (as write_decryption takes them).  Returns (params as written to params.json, the plaintexts or None).
+
+    Files as the reference places them: version, auxsid, width (MixNetElGamalSession.java:219-223, 287-290),
+    proofs/activethreshold and proofs/maxciph (ShufflerElGamalSession.java:394, 520, 593); proofs/Ciphertexts%02d.bt for
+    l <= active in the plain flow (:225-235) and for l < active in the committed flow (:821, :953); ShuffledCiphertexts.bt and
+    type = shuffling (MixNetElGamalSession.java:236-243); a mixing session renames ShuffledCiphertexts.bt into proofs/ and sets
+    type = mixing (:294-303); a decryption-only session has Ciphertexts.bt and type = decryption (:305-310).  FullPublicKey.bt
+    is (g, y) at width 1 (readFullPKey :205-212).  Two places where this writer does not follow the letter of the reference:
+    the renamed list goes to proofs/Ciphertexts<active>.bt -- the reference names it by its `threshold` field, which is the same
+    file when active = threshold and would otherwise overwrite the output of party `threshold`, while the verifier looks for
+    the last list under the ACTIVE threshold (:1035, :1446); and a decryption-only session also gets proofs/activethreshold,
+    which the verifier reads for every type (:1357).
+
+    `failing`: parties that publish an invalid proof -- the party's honest commitment with the reply of a second, unrelated run
+    on the same input.  The honest parties then go on as ShufflerElGamalSession.java:317-329: the party's output is replaced by
+    its input (also in the file they keep for the verifier) and the next party shuffles that."""
+    wr = writers if writers is not None else SimpleNamespace(
+        write_inputs=write_inputs, write_shuffle=write_shuffle, write_precomputation=write_precomputation,
+        write_committed_shuffle=write_committed_shuffle, write_decryption=write_decryption)
+    if session_type not in (MIX_TYPE, SHUFFLE_TYPE, DECRYPT_TYPE):
+        raise ValueError("unknown session type %r" % (session_type,))
+    active = threshold if active is None else active
+    if not threshold <= active <= k:
+        raise ValueError("threshold <= active <= k")
+    width = len(W) // 2
+    params = dict(params, k=k, threshold=threshold, width=width, N_0=n0)
+    g = grp.g
+    wide = [g] * width + [y] * width
+    os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
+    wr.write_inputs(nizkp, grp, params, [g, y], W)
+    write_string(version_file(nizkp), params["version"])
+    write_string(auxsid_file(nizkp), params["auxsid"])
+    write_int(width_file(nizkp), width)
+    write_int(at_file(nizkp), active)
+    last = list(W)
+    if session_type != DECRYPT_TYPE:
+        if n0:
+            write_int(mc_file(nizkp), n0)
+        pre, H = {}, None
+        for l in range(1, active + 1) if n0 else ():
+            pre[l] = wr.write_precomputation(nizkp, l, grp, params, n0, rand, H)
+            H = pre[l][3]
+
+        def play(where, l, inp, out_file, secrets):
+            if n0:
+                return wr.write_committed_shuffle(where, l, grp, params, wide, inp, rand, *secrets, out_file=out_file)
+            return wr.write_shuffle(where, l, grp, params, wide, inp, rand, out_file=out_file)
+        for l in range(1, active + 1):
+            out_file = ls_file(nizkp) if n0 and l == active else l_file(nizkp, l)
+            out = play(nizkp, l, last, out_file, pre.get(l))
+            if l in failing:
+                with tempfile.TemporaryDirectory(dir=nizkp) as other:
+                    os.makedirs(_p(other, "proofs"))
+                    shutil.copyfile(l_file(nizkp, l - 1), l_file(other, l - 1))
+                    secrets = wr.write_precomputation(other, l, grp, params, n0, rand, H) if n0 else None
+                    play(other, l, last, l_file(other, l), secrets)
+                    reply = ccposr_file if n0 else posr_file
+                    shutil.copyfile(reply(other, l), reply(nizkp, l))
+                shutil.copyfile(l_file(nizkp, l - 1), out_file)
+            else:
+                last = out
+        if not n0:
+            shutil.copyfile(l_file(nizkp, active), ls_file(nizkp))
+        write_string(type_file(nizkp), SHUFFLE_TYPE)
+    plain = None
+    if session_type != SHUFFLE_TYPE:
+        if os.path.exists(ls_file(nizkp)):
+            write_string(type_file(nizkp), MIX_TYPE)
+            os.replace(ls_file(nizkp), l_file(nizkp, active))
+        else:
+            write_string(type_file(nizkp), DECRYPT_TYPE)
+        plain = wr.write_decryption(nizkp, grp, params, wide, last, poly, shares, rand, k, threshold)
+    return params, plain
