@@ -168,6 +168,27 @@ size_t vmn_rarray_bytetree_size(const vmn_rarray* a);
 int vmn_rarray_to_bytetree(const vmn_rarray* a, uint8_t* out);
 int vmn_rarray_from_bytetree(vmn_group* grp, const uint8_t* bt, size_t len, size_t expected_n, vmn_rarray** out,
                              int* format_ok, int* all_in_range);
+/* Ciphertext lists in the reference's `native` interface (its default: ProtocolElGamalInterfaceNative / ...SeqHex,
+ * CiphertextReaderLine / CiphertextWriterLine; `vmnc -ciphs -ini native -outi raw` is the first command of an election): one
+ * ciphertext per line, the line being the hexadecimal byte tree of that ciphertext alone -- node(u, v) with u, v element trees
+ * at width 1 and node(width element trees) above; an element tree is leaf(elem_bytes) resp. node(leaf(x), leaf(y)).  B bytes
+ * = 2 B digits per line, B = vmn_hexlines_line_bytes (0 for a null group or a width of 0 or above 65536): 527 for a 2048-bit
+ * group at 256-byte leaves and width 1, 501 for P-256 at 33-byte coordinates and width 3.  The widths are the group's wire widths.
+ * Lines end as Java's readLine ends them (\n, \r, or \r\n counted once; text behind the last terminator is a line if it is
+ * not empty); they are found, decoded and checked on the GPU and converted by the import kernels of the byte trees.
+ * from_hexlines: out receives the 2 * width component arrays u_1..u_width, v_1..v_width of *n_out elements each.  *format_ok = 0,
+ * every out[] slot NULL and *first_bad_line = the zero-based index of the first defective line when a line has not exactly 2 B
+ * digits 0-9a-fA-F or its framing is not this group's and width's; a line count that differs from a non-zero expected_n is the
+ * same with *first_bad_line = min(lines, expected_n).  [NOT-IN-REF: the reference rejects the whole file as well, without naming
+ * the line; it is silent on the case of the digits (either is read, lowercase written), and fails on a blank line, as here.]
+ * Values >= p, zero, or off the curve: as vmn_garray_from_bytetree (arrays created, entries replaced, *all_in_range = 0,
+ * may be NULL); subgroup membership is vmn_garray_is_member.  A text without lines gives 2 * width empty arrays.
+ * to_hexlines writes vmn_garrays_hexlines_size = n (2 B + 1) bytes: lowercase digits, every line ended by \n, no NUL. */
+size_t vmn_hexlines_line_bytes(const vmn_group* grp, size_t width);
+int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const char* text, size_t len, size_t expected_n, vmn_garray** out,
+                              size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range);
+size_t vmn_garrays_hexlines_size(const vmn_garray* const* comps, size_t width);
+int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t width, char* out);
 size_t vmn_garray_size(const vmn_garray* a);
 /* the group an array belongs to (PGroupElementArray.getPGroup(), PRingElementArray.getPRing()): a binding sizes the host
  * buffers of vmn_*_to_be / _get / _prod ... from it (jni/: every byte[] is checked against the bytes the callee touches) */

@@ -78,6 +78,51 @@ final class GPUArrays {
         return out;
     }
 
+    /** A list in the reference's {@code native} interface (one ciphertext per line, the line the hexadecimal byte tree of that
+     *  ciphertext: CiphertextReaderLine) as its 2w component arrays [u_1..u_w, v_1..v_w], parsed on the GPU.  {@code text}: a
+     *  direct buffer holding the file, {@code len} its bytes; {@code expectedSize} 0 accepts any number of lines.  A malformed
+     *  line, a value out of range or an element outside the group is the reference's ArithmFormatException / EIOException;
+     *  {@code firstBadLine} (may be null) receives the zero-based index of the first malformed line. */
+    static PGroupElementArrayGPU[] readCiphertextsNative(final GPUGroup group, final ByteBuffer text, final long len, final int width,
+                                                         final long expectedSize, final long[] firstBadLine) {
+        final long[] out = new long[2 * width];
+        final long[] lines = new long[1];
+        final long[] bad = new long[1];
+        final int[] formatOk = new int[1];
+        final int[] inRange = new int[1];
+        VMNException.check(VMNHip.vmn_garrays_from_hexlinesDirect(group.grp, width, text, len, expectedSize, out, lines, formatOk, bad, inRange));
+        if (firstBadLine != null) {
+            firstBadLine[0] = bad[0];
+        }
+        if (formatOk[0] == 0) {
+            throw new VMNException(VMNException.ERR_FORMAT);
+        }
+        final PGroupElementArrayGPU[] comps = new PGroupElementArrayGPU[2 * width];
+        for (int c = 0; c < comps.length; c++) {
+            comps[c] = new PGroupElementArrayGPU(group, out[c]);
+        }
+        boolean ok = inRange[0] != 0;
+        for (int c = 0; ok && c < comps.length; c++) {
+            ok = comps[c].isMember();
+        }
+        if (!ok) {
+            free(comps);
+            throw new VMNException(VMNException.ERR_FORMAT);
+        }
+        return comps;
+    }
+
+    /** The reverse (CiphertextWriterLine): lowercase digits, every line ended by a newline, into a fresh direct buffer. */
+    static ByteBuffer writeCiphertextsNative(final PGroupElementArrayGPU[] comps) {
+        final long[] h = handles(comps);
+        final int width = comps.length / 2;
+        final long size = VMNHip.vmn_garrays_hexlines_size(h, width);
+        final ByteBuffer buf = ByteBuffer.allocateDirect((int) Math.max(1L, size));
+        VMNException.check(VMNHip.vmn_garrays_to_hexlinesDirect(h, width, buf));
+        buf.limit((int) size);
+        return buf;
+    }
+
     static long[] handles(final PGroupElementArrayGPU[] arrays) {
         final long[] h = new long[arrays.length];
         for (int i = 0; i < h.length; i++) {

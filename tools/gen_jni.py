@@ -12,6 +12,7 @@ The wrappers are mechanical (the C ABI was designed for it: opaque pointers, pla
     vmn_X**  (result handles)           long[]      (one slot per result; vmn_shuffle_reencrypt fills 2 * width)
     const vmn_Xarray* const*            long[]
     const uint8_t* / uint8_t*           byte[]      (big-endian rows, byte trees; results are written back)
+    const char* text, size_t len        byte[]      (a whole text file: vmn_garrays_from_hexlines)
     const uint32_t* / uint32_t*         int[]       (permutation tables)
     int* / size_t* / long* / double*    int[] / long[] / long[] / double[]   (verdicts, counts, timings)
     const char* / char*                 String / byte[]
@@ -46,10 +47,13 @@ HANDLES = ("vmn_ctx", "vmn_group", "vmn_garray", "vmn_rarray", "vmn_msg", "vmn_p
            "vmn_igen", "vmn_pending")
 BULK = {"vmn_garray_from_be": ["be"], "vmn_rarray_from_be": ["be"], "vmn_garray_to_be": ["be_out"], "vmn_rarray_to_be": ["be_out"],
         "vmn_garray_to_bytetree": ["out"], "vmn_rarray_to_bytetree": ["out"], "vmn_garray_from_bytetree": ["bt"],
-        "vmn_rarray_from_bytetree": ["bt"], "vmn_msg_to_bytetree": ["out"], "vmn_msg_from_bytetree": ["bt"]}
+        "vmn_rarray_from_bytetree": ["bt"], "vmn_msg_to_bytetree": ["out"], "vmn_msg_from_bytetree": ["bt"],
+        "vmn_garrays_from_hexlines": ["text"], "vmn_garrays_to_hexlines": ["out"]}
 # objects created with a random source keep calling it: the bridge lives until the object's _free
 RS_OWNERS = {"vmn_pos_create": "vmn_pos_free", "vmn_posc_create": "vmn_posc_free", "vmn_ccpos_create": "vmn_ccpos_free",
              "vmn_decproof_create": "vmn_decproof_free", "vmn_igen_create": "vmn_igen_free"}
+# `const char*` is a String elsewhere (a curve name, a family); these are whole files of `len` bytes: byte[] / direct buffers, sized
+TEXT_AS_BYTES = {("vmn_garrays_from_hexlines", "text"): "bytes_in"}
 HAND_WRITTEN = {"vmn_msg_item_bytes"}          # const uint8_t** result: returns a byte[] (see the template below)
 
 
@@ -97,6 +101,11 @@ def kind(ptype):
     if k in ("bytes", "ints", "longs", "doubles", "chars"):
         return k + ("_in" if const else "_out")
     return k
+
+
+def pkind(name, ptype, pname):
+    """kind() of a parameter, with the few parameters whose C type says less than the header does."""
+    return TEXT_AS_BYTES.get((name, pname)) or kind(ptype)
 
 
 JAVA_T = {"handle": "long", "handles_in": "long[]", "handles_out": "long[]", "bytes_in": "byte[]", "bytes_out": "byte[]",
@@ -163,7 +172,7 @@ def first_of(plist, *types):
 def need_expr(name, ptype, pname, plist):
     """Number of ELEMENTS (bytes for byte[], ints for int[], ...) the callee touches through this parameter, as a C
     expression over the wrapper's locals; None when it cannot be known here."""
-    k = kind(ptype)
+    k = pkind(name, ptype, pname)
     names = [pn for _, pn in plist]
     G = group_expr(name, plist)
     EB, XB = (f"vmnjni_eb({G})", f"vmnjni_xb({G})") if G else (None, None)
@@ -179,11 +188,13 @@ def need_expr(name, ptype, pname, plist):
             return "(size_t)keywidth * (size_t)width"
         if pname == "outs":
             return "(size_t)k"
+        if name == "vmn_garrays_from_hexlines" and pname == "out":
+            return "2 * (size_t)width"
         return {"wp_out": "2 * (size_t)width", "factors_out": "2 * (size_t)width", "s_out": "(size_t)width"}.get(pname, "1")
     if k == "handles_in":
         if pname in ("xs", "ys"):
             return "(size_t)k"
-        if pname in ("w", "wp", "w_full", "factors"):
+        if pname in ("w", "wp", "w_full", "factors", "comps"):
             return "2 * (size_t)width"
         if pname in ("s", "s_full"):
             return "(size_t)width"
@@ -230,7 +241,7 @@ def need_expr(name, ptype, pname, plist):
     if k == "doubles_out":
         return "1"
     if k in ("bytes_in", "bytes_out", "chars_out"):
-        explicit = {"seed": "seedlen", "v_be": "vbytes", "e_be": "ebytes", "rho_be": "rho_bytes", "data": "len", "bt": "len", "buf": "len",
+        explicit = {"seed": "seedlen", "v_be": "vbytes", "e_be": "ebytes", "rho_be": "rho_bytes", "data": "len", "bt": "len", "buf": "len", "text": "len",
                     "keep": "keep_len"}
         if name == "vmn_keep_list_sanitize" and pname == "keep":
             return "(size_t)(keep_len > n_max ? keep_len : n_max)"       # the trivial list is written over n_max entries
@@ -249,6 +260,8 @@ def need_expr(name, ptype, pname, plist):
             return f"vmn_decproof_keywidth({pobj}) * {EB}"
         if pname == "y_be" and name == "vmn_decproof_set_instance_keyed":
             return f"((size_t)vmn_decproof_parties({pobj}) + 1) * (size_t)keywidth * {EB}"
+        if name == "vmn_garrays_to_hexlines" and pname == "out":
+            return "vmn_garrays_hexlines_size((const vmn_garray* const*)c_comps, (size_t)width)"
         if name == "vmn_prg_bytes" and pname == "out":
             return "(size_t)nbytes"
         if name.startswith("vmn_random_oracle") and pname == "out":
@@ -315,7 +328,7 @@ def c_wrapper(cls, ret, name, plist, direct=()):
     jname = name + ("Direct" if direct else "")
     args, pre, call, post = [], [], [], []
     for ptype, pname in plist:
-        k = kind(ptype)
+        k = pkind(name, ptype, pname)
         ctype = ptype
         if pname in direct:
             args.append(f"jobject {pname}")
@@ -384,7 +397,7 @@ def c_wrapper(cls, ret, name, plist, direct=()):
     # every array / direct buffer against the elements the callee touches through it
     checks = []
     for ptype, pname in plist:
-        k = kind(ptype)
+        k = pkind(name, ptype, pname)
         if k not in ("bytes_in", "bytes_out", "chars_out", "ints_in", "ints_out", "longs_in", "longs_out", "doubles_out", "handles_in",
                      "handles_out"):
             continue
@@ -433,7 +446,7 @@ def java_decl(ret, name, plist, direct=()):
     jret, _ = ret_types(ret)
     ps = []
     for ptype, pname in plist:
-        t = "java.nio.ByteBuffer" if pname in direct else JAVA_T[kind(ptype)]
+        t = "java.nio.ByteBuffer" if pname in direct else JAVA_T[pkind(name, ptype, pname)]
         ps.append(f"{t} {pname}")
     return f"    public static native {jret} {name}{'Direct' if direct else ''}({', '.join(ps)});"
 

@@ -362,4 +362,173 @@ __global__ void __launch_bounds__(BLOCK) k_set_segment_heads(uint4* __restrict__
     a[s * seglen * cpr + ch] = one_row[ch];
 }
 
+// ---------------------------------------------------------------------------------------------
+// The `native` ciphertext interface (csrc/hexlines_layout.h): a text of one ciphertext per line, each line the hex digits of
+// that ciphertext's byte tree, <-> records of B bytes, one per line, on which the import / export kernels work component by
+// component (be = rec + offset, stride = B, leaf headers on).
+// Lines end as Java's readLine ends them: at \n, at \r, or at \r\n, which counts once; text behind the last terminator is a
+// line only if it is not empty.  Terminators are mixed freely, so line k does not start at k (H + 1): the starts are found
+// -- a count of the terminators per chunk of the text, the u32 scan above over the counts, a second walk that writes where
+// every line begins and ends.  Offsets are 64-bit (10^6 lines of an 8192-bit group pass 4 GB), the line count is below 2^32.
+// The text buffer is padded by 48 bytes: a thread reads its 16 bytes whole and the byte behind them.
+// ---------------------------------------------------------------------------------------------
+constexpr int HEXLINES_SEG = 16;                              // bytes of text per thread
+constexpr int HEXLINES_CHUNK = BLOCK * HEXLINES_SEG;          // bytes of text per workgroup
+constexpr int HEXLINES_LANES = 32;                            // lanes per line in the two conversions
+constexpr int HEXLINES_PAD = 48;
+
+// bit k: a line ends with the byte at base + k (a \n, or a \r that no \n follows); base is a multiple of 16
+__device__ __forceinline__ u32 hexlines_term_mask(const uint8_t* __restrict__ text, size_t len, size_t base) {
+    if (base >= len) return 0;
+    const uint4 v = *reinterpret_cast<const uint4*>(text + base);
+    const u32 w[5] = {v.x, v.y, v.z, v.w, (u32)text[base + HEXLINES_SEG]};
+    u32 m = 0;
+#pragma unroll
+    for (int k = 0; k < HEXLINES_SEG; ++k) {
+        const u32 c = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+        const u32 nx = (w[(k + 1) >> 2] >> (8 * ((k + 1) & 3))) & 0xffu;
+        const bool lf_follows = base + k + 1 < len && nx == '\n';
+        if (base + k < len && (c == '\n' || (c == '\r' && !lf_follows))) m |= 1u << k;
+    }
+    return m;
+}
+
+// counts[chunk] = terminators of the chunk; *total += the same (64-bit: a text of 2^32 lines or more is refused by the host)
+__global__ void __launch_bounds__(BLOCK) k_hexlines_count(u32* __restrict__ counts, unsigned long long* __restrict__ total,
+                                                          const uint8_t* __restrict__ text, size_t len) {
+    __shared__ u32 sum;
+    if (threadIdx.x == 0) sum = 0;
+    __syncthreads();
+    const size_t base = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * HEXLINES_SEG;
+    u32 c = (u32)__builtin_popcount(hexlines_term_mask(text, len, base));
+    for (int o = 32; o > 0; o >>= 1) c += (u32)__shfl_xor((int)c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&sum, c);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        counts[blockIdx.x] = sum;
+        if (sum) atomicAdd(total, (unsigned long long)sum);
+    }
+}
+
+// start[k], end[k] = where the digits of line k begin and end (end exclusive: the terminator is not part of the line), k < nlines;
+// first[chunk] = terminators in front of the chunk (the scan of the counts)
+__global__ void __launch_bounds__(BLOCK) k_hexlines_walk(u64* __restrict__ start, u64* __restrict__ end, const uint8_t* __restrict__ text,
+                                                         size_t len, const u32* __restrict__ first, u32 nlines) {
+    __shared__ u32 wave_total[BLOCK / 64];
+    const size_t base = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * HEXLINES_SEG;
+    const u32 terms = hexlines_term_mask(text, len, base);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 mine = (u32)__builtin_popcount(terms);
+    u32 inc = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 below = (u32)__shfl_up((int)inc, o);
+        if (lane >= o) inc += below;
+    }
+    if (lane == 63) wave_total[wave] = inc;
+    __syncthreads();
+    u32 rank = first[blockIdx.x] + inc - mine;
+    for (int k = 0; k < wave; ++k) rank += wave_total[k];
+    if (base == 0 && nlines) start[0] = 0;
+    for (u32 m = terms; m; m &= m - 1) {
+        const size_t j = base + (size_t)__builtin_ctz(m);
+        const bool crlf = text[j] == '\n' && j > 0 && text[j - 1] == '\r';
+        if (rank < nlines) end[rank] = crlf ? j - 1 : j;
+        if (j + 1 < len && rank + 1 < nlines) start[rank + 1] = j + 1;
+        ++rank;
+    }
+    // text behind the last terminator: a line that the end of the text closes
+    if (len && nlines && len - 1 >= base && len - 1 - base < (size_t)HEXLINES_SEG && !((terms >> (len - 1 - base)) & 1u)) end[nlines - 1] = len;
+}
+
+__device__ __forceinline__ u32 hex_nibble(u32 c, u32& err) {          // 0-9 a-f A-F, nothing else
+    const u32 d = c - '0', a = (c | 0x20u) - 'a';
+    err |= (u32)!(d < 10u || a < 6u);
+    return d < 10u ? d : (a + 10u) & 15u;
+}
+__device__ __forceinline__ u32 hex_digit(u32 n) { return n + '0' + (n > 9u ? (u32)('a' - '0' - 10) : 0u); }
+// which bytes of a record are framing, eight at a time, as 0xff / 0x00 from the mask's 0 / 1 / 2 (hexlines_layout.h)
+__device__ __forceinline__ u64 hexlines_any_framing(u64 m) { return ((m | (m >> 1)) & 0x0101010101010101ull) * 0xffull; }
+__device__ __forceinline__ u64 hexlines_outer_framing(u64 m) { return (m & 0x0101010101010101ull) * 0xffull; }
+
+// rec + line * B = the B bytes that the H = 2 B digits of line `line` spell; HEXLINES_LANES lanes per line, 16 digits -> 8 bytes per
+// step.  A line whose length is not H, a character that is no hex digit, a framing byte that differs from the template:
+// *first_bad = min(*first_bad, line).  The digits are read only when the line has H of them inside the text, so nothing that the
+// text says becomes an address.  The leaf headers are compared here too -- the line is to be named -- and again by the import kernels.
+__global__ void __launch_bounds__(BLOCK) k_hexlines_decode(uint8_t* __restrict__ rec, const uint8_t* __restrict__ text, size_t len,
+                                                           const u64* __restrict__ start, const u64* __restrict__ end, u32 nlines, u32 B,
+                                                           const uint8_t* __restrict__ tmpl, const uint8_t* __restrict__ mask,
+                                                           u32* __restrict__ first_bad) {
+    const size_t line = ((size_t)blockIdx.x * BLOCK + threadIdx.x) / HEXLINES_LANES;
+    const u32 sub = threadIdx.x % HEXLINES_LANES;
+    if (line >= nlines) return;
+    const u64 s = start[line], e = end[line];
+    u32 bad = !(s <= e && e <= (u64)len && e - s == 2ull * B);
+    if (!bad) {
+        const uint8_t* __restrict__ src = text + s;
+        uint8_t* __restrict__ dst = rec + line * B;
+        for (u32 c = sub * 8; c < B; c += HEXLINES_LANES * 8) {
+            if (c + 8 <= B) {
+                uint4 d;
+                __builtin_memcpy(&d, src + 2 * (size_t)c, 16);
+                const u32 w[4] = {d.x, d.y, d.z, d.w};
+                u64 out = 0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const u32 pair = w[k >> 1] >> (16 * (k & 1));
+                    const u32 byte = (hex_nibble(pair & 0xffu, bad) << 4) | hex_nibble((pair >> 8) & 0xffu, bad);
+                    out |= (u64)byte << (8 * k);
+                }
+                u64 t, m;
+                __builtin_memcpy(&t, tmpl + c, 8);
+                __builtin_memcpy(&m, mask + c, 8);
+                bad |= (u32)(((out ^ t) & hexlines_any_framing(m)) != 0);
+                __builtin_memcpy(dst + c, &out, 8);
+            } else {
+                for (u32 k = c; k < B; ++k) {
+                    const u32 byte = (hex_nibble(src[2 * (size_t)k], bad) << 4) | hex_nibble(src[2 * (size_t)k + 1], bad);
+                    bad |= (u32)(mask[k] != 0 && byte != tmpl[k]);
+                    dst[k] = (uint8_t)byte;
+                }
+            }
+        }
+    }
+    if (bad) atomicMin(first_bad, (u32)line);
+}
+
+// The reverse: line `line` of the text = the 2 B lowercase digits of the record at rec + line * B and a \n.  The export kernels have
+// written the components with their leaf headers into the records; the framing of the outer nodes comes from the template.
+__global__ void __launch_bounds__(BLOCK) k_hexlines_encode(uint8_t* __restrict__ text, const uint8_t* __restrict__ rec, u32 nlines, u32 B,
+                                                           const uint8_t* __restrict__ tmpl, const uint8_t* __restrict__ mask) {
+    const size_t line = ((size_t)blockIdx.x * BLOCK + threadIdx.x) / HEXLINES_LANES;
+    const u32 sub = threadIdx.x % HEXLINES_LANES;
+    if (line >= nlines) return;
+    const uint8_t* __restrict__ src = rec + line * B;
+    uint8_t* __restrict__ dst = text + line * (2 * (size_t)B + 1);
+    for (u32 c = sub * 8; c < B; c += HEXLINES_LANES * 8) {
+        if (c + 8 <= B) {
+            u64 r, t, m;
+            __builtin_memcpy(&r, src + c, 8);
+            __builtin_memcpy(&t, tmpl + c, 8);
+            __builtin_memcpy(&m, mask + c, 8);
+            const u64 outer = hexlines_outer_framing(m);
+            r = (r & ~outer) | (t & outer);
+            u32 w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const u32 b0 = (u32)(r >> (16 * k)) & 0xffu, b1 = (u32)(r >> (16 * k + 8)) & 0xffu;
+                w[k] = hex_digit(b0 >> 4) | (hex_digit(b0 & 15u) << 8) | (hex_digit(b1 >> 4) << 16) | (hex_digit(b1 & 15u) << 24);
+            }
+            const uint4 o = make_uint4(w[0], w[1], w[2], w[3]);
+            __builtin_memcpy(dst + 2 * (size_t)c, &o, 16);
+        } else {
+            for (u32 k = c; k < B; ++k) {
+                const u32 byte = mask[k] == 1 ? tmpl[k] : src[k];
+                dst[2 * (size_t)k] = (uint8_t)hex_digit(byte >> 4);
+                dst[2 * (size_t)k + 1] = (uint8_t)hex_digit(byte & 15u);
+            }
+        }
+    }
+    if (sub == 0) dst[2 * (size_t)B] = '\n';
+}
+
 }  // namespace vmn

@@ -22,6 +22,7 @@
 #include "hostnum64.h"
 #include "ec_shared_schedule.h"
 #include "expprod_schedule.h"
+#include "hexlines_layout.h"
 
 // the Cfg-templated kernels are compiled in the instantiation units csrc/inst_*.hip (modp_instances.h); here they are declared
 VMN_UNIT_SMALL(extern template)
@@ -1447,6 +1448,22 @@ static int alloc_elems(vmn_ctx* ctx, const vmn_modulus& m, size_t n, uint32_t** 
     return pool_alloc(ctx, elems_bytes(m, n), reinterpret_cast<void**>(d));
 }
 
+// The conversion kernel alone, over rows that are on the device already, `stride` bytes apart (mode: see k_import_be; curves take
+// its bit 0 alone): a verdict, if any, is OR-ed into ctx->flags, which the caller has cleared and reads back.
+static int import_rows_launch(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const uint8_t* d_rows, size_t stride, int mode, size_t n,
+                              uint32_t* d_out) {
+    if (m.ec) {
+        return with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "import", k_ec_import<E::S, E::NW, E::KIND>, grid_for(n), d_out, d_rows, nbytes, stride, mode & 1, n,
+                                ecdev(m.ec), ctx->flags);
+        });
+    }
+    return with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+        return launch(ctx, "import", k_import_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), d_out, d_rows, nbytes, stride, mode, n, mg.d_n,
+                      mg.n0inv, mg.d_rr, ctx->flags);
+    });
+}
+
 // leaf_hdr: every value is preceded by its 5-byte byte-tree leaf header (checked on the device; *format_ok)
 // (checked_on_host: the caller has validated the values itself -- the conversion is only queued, no verdict is read back)
 static int import_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const uint8_t* be, size_t n, uint32_t* d_out,
@@ -1462,19 +1479,7 @@ static int import_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const ui
     else VMN_HIP(hipMemcpyAsync(raw.p, be, n * stride, hipMemcpyHostToDevice, ctx->stream));
     VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
     note_work(ctx, m, (m.ec ? 7.0 : 1.0) * (double)n);
-    int rc;
-    if (m.ec) {
-        rc = with_curve(m, [&]<class E>(E) {
-            return launch_light(ctx, "import", k_ec_import<E::S, E::NW, E::KIND>, grid_for(n), d_out, (const uint8_t*)raw.as<uint8_t>(),
-                                nbytes, stride, leaf_hdr, n, ecdev(m.ec), ctx->flags);
-        });
-    } else {
-        rc = with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
-            return launch(ctx, "import", k_import_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), d_out, raw.as<uint8_t>(), nbytes, stride,
-                          leaf_hdr, n, mg.d_n, mg.n0inv, mg.d_rr, ctx->flags);
-        });
-    }
-    VMN_TRY(rc);
+    VMN_TRY(import_rows_launch(ctx, m, nbytes, raw.as<uint8_t>(), stride, leaf_hdr, n, d_out));
     if (checked_on_host) return VMN_OK;
     uint32_t fl = 0;
     VMN_TRY(read_flag(ctx, &fl));
@@ -1531,16 +1536,10 @@ static int ec_export_few_host(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes,
     return VMN_OK;
 }
 
-// (pinned_async: `be` is pinned host memory and the copy is only queued -- the caller orders itself behind it)
 static int ec_normalize(vmn_ctx* ctx, const vmn_modulus& m, const uint32_t* const* ins, size_t k, size_t n, uint32_t* out);
-static int export_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const uint32_t* d_in, size_t n, uint8_t* be,
-                     int leaf_hdr = 0, bool pinned_async = false) {
-    if (n == 0) return VMN_OK;
-    // a curve point in a byte tree is node(leaf(x), leaf(y)): 15 framing bytes around the two coordinates
-    const size_t stride = m.ec ? 2 * nbytes + (leaf_hdr ? 15 : 0) : nbytes + (leaf_hdr ? 5 : 0);
-    if (m.ec && n <= 4 && !leaf_hdr && !pinned_async && !getenv("VMN_EC_EXPORT_DEVICE")) return ec_export_few_host(ctx, m, nbytes, d_in, n, be);
-    DevTmp raw(ctx);
-    VMN_TRY(raw.alloc(n * stride + 8));
+// The conversion kernel alone: value i goes to d_dst + i * stride on the device (leaf_hdr: behind its byte-tree framing).
+static int export_rows_launch(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const uint32_t* d_in, size_t n, uint8_t* d_dst, size_t stride,
+                              int leaf_hdr) {
     // Curves: the export kernel inverts Z per point -- a Fermat power of ~380 products, 25 times the rest of a point's export.
     // One chain of them lasts 0.16 ms whatever the array (up to a device full of lanes); from there on the rows are normalised
     // first by the batched inversion of the multi-exponentiations (~8 products per point) and exported as they are.
@@ -1559,19 +1558,27 @@ static int export_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const ui
     }
     if (ec_rows_affine) note_work(ctx, m, 2.0 * (double)n);
     else note_work(ctx, m, m.ec ? 8.0 * (double)n : (double)n, m.ec ? (double)m.nbits * (double)n : 0.0);     // curves: one Fermat inversion per point
-    int rc;
     if (m.ec) {
-        rc = with_curve(m, [&]<class E>(E) {
-            return launch_light(ctx, "export", k_ec_export<E::S, E::NW, E::KIND>, grid_for(n), raw.as<uint8_t>(), nbytes, stride,
-                                leaf_hdr | ec_rows_affine, d_in, n, ecdev(m.ec));
-        });
-    } else {
-        rc = with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
-            return launch(ctx, "export", k_export_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), raw.as<uint8_t>(), nbytes, stride, leaf_hdr,
-                          d_in, n, mg.d_n, mg.n0inv);
+        return with_curve(m, [&]<class E>(E) {
+            return launch_light(ctx, "export", k_ec_export<E::S, E::NW, E::KIND>, grid_for(n), d_dst, nbytes, stride, leaf_hdr | ec_rows_affine,
+                                d_in, n, ecdev(m.ec));
         });
     }
-    VMN_TRY(rc);
+    return with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
+        return launch(ctx, "export", k_export_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), d_dst, nbytes, stride, leaf_hdr, d_in, n, mg.d_n,
+                      mg.n0inv);
+    });
+}
+// (pinned_async: `be` is pinned host memory and the copy is only queued -- the caller orders itself behind it)
+static int export_be(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const uint32_t* d_in, size_t n, uint8_t* be,
+                     int leaf_hdr = 0, bool pinned_async = false) {
+    if (n == 0) return VMN_OK;
+    // a curve point in a byte tree is node(leaf(x), leaf(y)): 15 framing bytes around the two coordinates
+    const size_t stride = m.ec ? 2 * nbytes + (leaf_hdr ? 15 : 0) : nbytes + (leaf_hdr ? 5 : 0);
+    if (m.ec && n <= 4 && !leaf_hdr && !pinned_async && !getenv("VMN_EC_EXPORT_DEVICE")) return ec_export_few_host(ctx, m, nbytes, d_in, n, be);
+    DevTmp raw(ctx);
+    VMN_TRY(raw.alloc(n * stride + 8));
+    VMN_TRY(export_rows_launch(ctx, m, nbytes, d_in, n, raw.as<uint8_t>(), stride, leaf_hdr));
     if (pinned_async) {
         VMN_HIP(hipMemcpyAsync(be, raw.p, n * stride, hipMemcpyDeviceToHost, ctx->stream));    // (raw: reuse is ordered on this stream)
         return VMN_OK;
@@ -2070,6 +2077,159 @@ extern "C" int vmn_rarray_from_bytetree(vmn_group* grp, const uint8_t* bt, size_
     *out = a;
     return VMN_OK;
 }
+// ---- the `native` ciphertext interface: one ciphertext per line, the line the hex digits of its byte tree -------------------
+// (csrc/hexlines_layout.h for the bytes of a line, csrc/light_kernels.h for the kernels)
+static bool hexlines_width_ok(const vmn_group* grp, size_t width) {
+    return width >= 1 && width <= 65536 && hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, width) < ((size_t)1 << 30);
+}
+// template and mask of a line on the device: the mask behind the template, each padded to a multiple of eight bytes
+static int hexlines_upload_layout(vmn_ctx* ctx, const hexlines::Layout& L, DevTmp& dev, const uint8_t** d_tmpl, const uint8_t** d_mask) {
+    const size_t padded = (L.B + 7) & ~(size_t)7;
+    std::vector<uint8_t> host(2 * padded, 0);
+    std::copy(L.tmpl.begin(), L.tmpl.end(), host.begin());
+    std::copy(L.mask.begin(), L.mask.end(), host.begin() + padded);
+    VMN_TRY(dev.alloc(2 * padded));
+    VMN_TRY(h2d(ctx, dev.p, host.data(), host.size()));              // (h2d has left `host` when it returns)
+    *d_tmpl = dev.as<uint8_t>();
+    *d_mask = dev.as<uint8_t>() + padded;
+    return VMN_OK;
+}
+static unsigned hexlines_grid(size_t nlines) { return (unsigned)((nlines * HEXLINES_LANES + BLOCK - 1) / BLOCK); }
+
+extern "C" size_t vmn_hexlines_line_bytes(const vmn_group* grp, size_t width) {
+    return grp && hexlines_width_ok(grp, width) ? hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, width) : 0;
+}
+extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const char* text, size_t len, size_t expected_n, vmn_garray** out,
+                                         size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range) {
+    ARG_CHECK(grp && out && n_out && format_ok && first_bad_line && (text || len == 0), "null argument");
+    ARG_CHECK(hexlines_width_ok(grp, width), "width out of range");
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    for (size_t c = 0; c < 2 * width; ++c) out[c] = nullptr;
+    *n_out = 0;
+    *format_ok = 0;
+    *first_bad_line = 0;
+    if (all_in_range) *all_in_range = 1;
+    const hexlines::Layout L = hexlines::make_layout(grp->curve != nullptr, grp->nbytes, width);
+    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
+
+    // where the lines are: terminators per chunk, their scan, then the starts and ends
+    size_t nlines = 0;
+    DevTmp dtext(ctx), counts(ctx), first(ctx), bsum(ctx), misc(ctx), starts(ctx), ends(ctx);
+    const size_t nchunks = (len + HEXLINES_CHUNK - 1) / HEXLINES_CHUNK;
+    ARG_CHECK(nchunks < ((size_t)1 << 31), "text too long");
+    if (len) {
+        VMN_TRY(dtext.alloc(len + HEXLINES_PAD));
+        VMN_TRY(h2d(ctx, dtext.p, utext, len));
+        const size_t scan_blocks = (nchunks + (size_t)BLOCK * SCAN_ITEMS - 1) / ((size_t)BLOCK * SCAN_ITEMS);
+        VMN_TRY(counts.alloc(nchunks * sizeof(uint32_t)));
+        VMN_TRY(first.alloc((nchunks + 1) * sizeof(uint32_t)));
+        VMN_TRY(bsum.alloc((scan_blocks + 1) * sizeof(uint32_t)));
+        VMN_TRY(misc.alloc(16));                               // u64 terminators | u32 first bad line | u32 scan total
+        const uint32_t misc_init[4] = {0, 0, 0xffffffffu, 0};
+        VMN_TRY(h2d(ctx, misc.p, misc_init, sizeof(misc_init)));
+        VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_count, (unsigned)nchunks, counts.as<uint32_t>(), (unsigned long long*)misc.p,
+                             (const uint8_t*)dtext.as<uint8_t>(), len));
+        VMN_TRY(launch_light(ctx, "hexlines", k_u32_blocksum, (unsigned)scan_blocks, bsum.as<uint32_t>(), (const uint32_t*)counts.as<uint32_t>(),
+                             nchunks));
+        hipLaunchKernelGGL(k_u32_scan_top, dim3(1), dim3(64), 0, ctx->stream, bsum.as<uint32_t>(), scan_blocks, misc.as<uint32_t>() + 3);
+        VMN_HIP(hipGetLastError());
+        VMN_TRY(launch_light(ctx, "hexlines", k_u32_scan_apply, (unsigned)scan_blocks, first.as<uint32_t>(), (uint32_t*)nullptr,
+                             (const uint32_t*)counts.as<uint32_t>(), (const uint32_t*)bsum.as<uint32_t>(), nchunks));
+        uint32_t got[4];
+        VMN_TRY(d2h(ctx, got, misc.p, sizeof(got)));
+        const uint64_t terms = (uint64_t)got[0] | ((uint64_t)got[1] << 32);
+        const bool open_end = utext[len - 1] != '\n' && utext[len - 1] != '\r';        // text behind the last terminator: one more line
+        ARG_CHECK(terms + (open_end ? 1 : 0) < 0xffffffffull, "2^32 lines or more");
+        nlines = (size_t)terms + (open_end ? 1 : 0);
+    }
+    if (expected_n != 0 && nlines != expected_n) {
+        *first_bad_line = std::min(nlines, expected_n);
+        return VMN_OK;
+    }
+
+    // digits -> records, the text and the outer framing judged on the way
+    DevTmp rec(ctx), layout(ctx);
+    if (nlines) {
+        const uint8_t *d_tmpl = nullptr, *d_mask = nullptr;
+        VMN_TRY(hexlines_upload_layout(ctx, L, layout, &d_tmpl, &d_mask));
+        VMN_TRY(starts.alloc(nlines * sizeof(uint64_t)));
+        VMN_TRY(ends.alloc(nlines * sizeof(uint64_t)));
+        VMN_TRY(rec.alloc(nlines * L.B + 16));
+        VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_walk, (unsigned)nchunks, (u64*)starts.p, (u64*)ends.p, (const uint8_t*)dtext.as<uint8_t>(),
+                             len, (const uint32_t*)first.as<uint32_t>(), (uint32_t)nlines));
+        VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_decode, hexlines_grid(nlines), rec.as<uint8_t>(), (const uint8_t*)dtext.as<uint8_t>(), len,
+                             (const u64*)starts.p, (const u64*)ends.p, (uint32_t)nlines, (uint32_t)L.B, d_tmpl, d_mask, misc.as<uint32_t>() + 2));
+        uint32_t bad = 0;
+        VMN_TRY(d2h(ctx, &bad, misc.as<uint32_t>() + 2, sizeof(bad)));
+        if (bad != 0xffffffffu) {
+            *first_bad_line = bad;
+            return VMN_OK;
+        }
+    }
+
+    // the records, component by component, through the import kernels (leaf headers on, one record apart)
+    std::vector<vmn_garray*> arrays(2 * width, nullptr);
+    auto drop = [&] {
+        for (vmn_garray* a : arrays) vmn_garray_free(a);
+    };
+    int rc = VMN_OK;
+    for (size_t c = 0; c < 2 * width && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    uint32_t fl = 0;
+    if (rc == VMN_OK && nlines) {
+        rc = dev_zero(ctx, ctx->flags, sizeof(uint32_t));
+        for (size_t c = 0; c < 2 * width && rc == VMN_OK; ++c) {
+            note_work(ctx, grp->P, (grp->P.ec ? 7.0 : 1.0) * (double)nlines);
+            rc = import_rows_launch(ctx, grp->P, grp->nbytes, rec.as<uint8_t>() + L.offset[c], L.B, 1, nlines, arrays[c]->d);
+        }
+        if (rc == VMN_OK) rc = read_flag(ctx, &fl);
+    }
+    if (rc != VMN_OK || (fl & 4u)) {            // (a leaf header the decode passed and the import refuses: cannot happen, and is no array)
+        drop();
+        return rc;
+    }
+    for (size_t c = 0; c < 2 * width; ++c) out[c] = arrays[c];
+    *n_out = nlines;
+    *format_ok = 1;
+    if (all_in_range) *all_in_range = (fl & 1u) ? 0 : 1;
+    return VMN_OK;
+}
+
+// the arrays of a ciphertext list: 2 * width of them, of one group and one size
+static bool hexlines_comps_ok(const vmn_garray* const* comps, size_t width) {
+    if (!comps || !comps[0] || !hexlines_width_ok(comps[0]->grp, width)) return false;
+    for (size_t c = 0; c < 2 * width; ++c)
+        if (!comps[c] || comps[c]->grp != comps[0]->grp || comps[c]->n != comps[0]->n) return false;
+    return true;
+}
+extern "C" size_t vmn_garrays_hexlines_size(const vmn_garray* const* comps, size_t width) {
+    if (!hexlines_comps_ok(comps, width)) return 0;
+    return comps[0]->n * (2 * vmn_hexlines_line_bytes(comps[0]->grp, width) + 1);
+}
+extern "C" int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t width, char* out) {
+    ARG_CHECK(comps && width >= 1 && comps[0], "null argument");
+    ARG_CHECK(hexlines_comps_ok(comps, width), "2 * width arrays of one group and one size are needed");
+    vmn_group* grp = comps[0]->grp;
+    const size_t n = comps[0]->n;
+    ARG_CHECK(out || n == 0, "null argument");
+    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    if (n == 0) return VMN_OK;
+    const hexlines::Layout L = hexlines::make_layout(grp->curve != nullptr, grp->nbytes, width);
+    DevTmp rec(ctx), layout(ctx), dtext(ctx);
+    const uint8_t *d_tmpl = nullptr, *d_mask = nullptr;
+    VMN_TRY(hexlines_upload_layout(ctx, L, layout, &d_tmpl, &d_mask));
+    VMN_TRY(rec.alloc(n * L.B + 16));
+    const size_t text_bytes = n * (2 * L.B + 1);
+    VMN_TRY(dtext.alloc(text_bytes + 16));
+    for (size_t c = 0; c < 2 * width; ++c)
+        VMN_TRY(export_rows_launch(ctx, grp->P, grp->nbytes, comps[c]->d, n, rec.as<uint8_t>() + L.offset[c], L.B, 1));
+    VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_encode, hexlines_grid(n), dtext.as<uint8_t>(), (const uint8_t*)rec.as<uint8_t>(), (uint32_t)n,
+                         (uint32_t)L.B, d_tmpl, d_mask));
+    return d2h(ctx, out, dtext.p, text_bytes);
+}
+
 extern "C" int vmn_garray_to_be(const vmn_garray* a, uint8_t* be_out) {
     ARG_CHECK(a && (be_out || a->n == 0), "null argument");
     VMN_ENTER(LANE(a->grp->ctx));
@@ -3595,10 +3755,7 @@ static int import_dev(vmn_ctx* ctx, const vmn_modulus& m, size_t nbytes, const u
     if (all_in_range) *all_in_range = 1;
     if (n == 0) return VMN_OK;
     VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
-    VMN_TRY(with_geom(ctx, m, n, [&]<class C, class W>(C, W, const vmn_modulus& mg) {
-        return launch(ctx, "import", k_import_be<C, W::NW>, egrid(mg, n), lds_bytes(mg), d_out, d_rows, nbytes, nbytes, mode, n, mg.d_n,
-                      mg.n0inv, mg.d_rr, ctx->flags);
-    }));
+    VMN_TRY(import_rows_launch(ctx, m, nbytes, d_rows, nbytes, mode, n, d_out));
     if (all_in_range) {
         uint32_t fl = 0;
         VMN_TRY(d2h(ctx, &fl, ctx->flags, sizeof(fl)));
