@@ -189,6 +189,31 @@ int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const char* text, si
                               size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range);
 size_t vmn_garrays_hexlines_size(const vmn_garray* const* comps, size_t width);
 int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t width, char* out);
+/* Ciphertext lists and plaintexts in the reference's `json` interface (ProtocolElGamalInterfaceJSON / ...JSONDecode: the format of
+ * Helios-style ballot boxes), modular groups only, as in the reference: a curve group is VMN_ERR_UNSUPPORTED.  A ciphertext line is
+ * {"alpha":"A","beta":"B"} at width 1 and [{"alpha":"A1","beta":"B1"},...,{"alpha":"Aw","beta":"Bw"}] above (pair i = u_i, v_i), a
+ * plaintext line "M" resp. ["M1",...,"Mw"]; every number is a decimal string as BigInteger.toString(10) writes it, every line
+ * ends with \n, there are no spaces.  csrc/jsonlines_layout.h states the text; the decimal <-> binary conversion of every number
+ * runs on the GPU (csrc/decimal_kernels.h), the import / export kernels of the byte trees on its result.
+ * from_jsonlines has the contract of vmn_garrays_from_hexlines: out receives the 2 * width component arrays u_1..u_width,
+ * v_1..v_width of *n_out elements each; *format_ok = 0, every out[] slot NULL and *first_bad_line = the zero-based index of the
+ * first defective line on a format defect; a line count that differs from a non-zero expected_n is the same with
+ * *first_bad_line = min(lines, expected_n); a text without lines gives 2 * width empty arrays.  Read beyond the written form:
+ * lines ended as readLine ends them, the two keys in either order, spaces and tabs between tokens, leading zeros.
+ * [NOT-IN-REF: a defect is a missing, duplicate, unknown or extra key, an empty number, a sign, a non-digit in a number, a
+ * backslash or a byte >= 0x80, a pair count other than width, [...] at width 1 or a bare map above, anything in front of the
+ * first token or behind the closing bracket, a blank line; the reference rejects the whole file without naming the line.]
+ * Values >= p (however many digits they have) and zero: as vmn_garray_from_bytetree (arrays created, entries replaced,
+ * *all_in_range = 0, may be NULL); subgroup membership is vmn_garray_is_member.
+ * vmn_jsonlines_max_line_bytes: the longest ciphertext line the writer can produce, newline included (0 for a null group, a curve
+ * group, or a width of 0 or above 65536); n times it always suffices as cap.  to_jsonlines takes 2 * width arrays, to_jsonplain
+ * width arrays (decodePlaintexts); both report the bytes written in *written, write no NUL, and return VMN_ERR_ARG, writing
+ * nothing, when cap is too small for this list. */
+size_t vmn_jsonlines_max_line_bytes(const vmn_group* grp, size_t width);
+int vmn_garrays_from_jsonlines(vmn_group* grp, size_t width, const char* text, size_t len, size_t expected_n, vmn_garray** out,
+                               size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range);
+int vmn_garrays_to_jsonlines(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written);
+int vmn_garrays_to_jsonplain(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written);
 size_t vmn_garray_size(const vmn_garray* a);
 /* the group an array belongs to (PGroupElementArray.getPGroup(), PRingElementArray.getPRing()): a binding sizes the host
  * buffers of vmn_*_to_be / _get / _prod ... from it (jni/: every byte[] is checked against the bytes the callee touches) */

@@ -91,17 +91,24 @@ final class GPUArrays {
         final int[] formatOk = new int[1];
         final int[] inRange = new int[1];
         VMNException.check(VMNHip.vmn_garrays_from_hexlinesDirect(group.grp, width, text, len, expectedSize, out, lines, formatOk, bad, inRange));
+        return listOrException(group, out, formatOk[0], bad[0], inRange[0], firstBadLine);
+    }
+
+    /** The policy of both line interfaces on what a reader returned: a format defect, a value out of range or an element
+     *  outside the group is no list. */
+    private static PGroupElementArrayGPU[] listOrException(final GPUGroup group, final long[] out, final int formatOk, final long bad,
+                                                           final int inRange, final long[] firstBadLine) {
         if (firstBadLine != null) {
-            firstBadLine[0] = bad[0];
+            firstBadLine[0] = bad;
         }
-        if (formatOk[0] == 0) {
+        if (formatOk == 0) {
             throw new VMNException(VMNException.ERR_FORMAT);
         }
-        final PGroupElementArrayGPU[] comps = new PGroupElementArrayGPU[2 * width];
+        final PGroupElementArrayGPU[] comps = new PGroupElementArrayGPU[out.length];
         for (int c = 0; c < comps.length; c++) {
             comps[c] = new PGroupElementArrayGPU(group, out[c]);
         }
-        boolean ok = inRange[0] != 0;
+        boolean ok = inRange != 0;
         for (int c = 0; ok && c < comps.length; c++) {
             ok = comps[c].isMember();
         }
@@ -110,6 +117,43 @@ final class GPUArrays {
             throw new VMNException(VMNException.ERR_FORMAT);
         }
         return comps;
+    }
+
+    /** A list in the reference's {@code json} interface (ProtocolElGamalInterfaceJSONDecode: one ciphertext per line,
+     *  {"alpha":"A","beta":"B"} with decimal strings, an array of such pairs at width > 1; modular groups only) as its 2w
+     *  component arrays, parsed and converted from decimal on the GPU.  Arguments and exceptions as readCiphertextsNative. */
+    static PGroupElementArrayGPU[] readCiphertextsJSON(final GPUGroup group, final ByteBuffer text, final long len, final int width,
+                                                       final long expectedSize, final long[] firstBadLine) {
+        final long[] out = new long[2 * width];
+        final long[] lines = new long[1];
+        final long[] bad = new long[1];
+        final int[] formatOk = new int[1];
+        final int[] inRange = new int[1];
+        VMNException.check(VMNHip.vmn_garrays_from_jsonlinesDirect(group.grp, width, text, len, expectedSize, out, lines, formatOk, bad, inRange));
+        return listOrException(group, out, formatOk[0], bad[0], inRange[0], firstBadLine);
+    }
+
+    /** The reverse (writeCiphertexts of the json interface): decimals without leading zeros, no spaces, every line ended by a
+     *  newline, into a fresh direct buffer limited to the bytes written. */
+    static ByteBuffer writeCiphertextsJSON(final GPUGroup group, final PGroupElementArrayGPU[] comps) {
+        return jsonLines(group, comps, comps.length / 2, false);
+    }
+
+    /** decodePlaintexts of the json interface: line i is "M" (width 1) or ["M1",...,"Mw"], the decimal value of plaintext i. */
+    static ByteBuffer decodePlaintextsJSON(final GPUGroup group, final PGroupElementArrayGPU[] plaintexts) {
+        return jsonLines(group, plaintexts, plaintexts.length, true);
+    }
+
+    private static ByteBuffer jsonLines(final GPUGroup group, final PGroupElementArrayGPU[] arrays, final int width, final boolean plain) {
+        final long[] h = handles(arrays);
+        final long lines = arrays.length == 0 ? 0 : VMNHip.vmn_garray_size(h[0]);
+        final long cap = Math.max(1L, lines * VMNHip.vmn_jsonlines_max_line_bytes(group.grp, width));
+        final ByteBuffer buf = ByteBuffer.allocateDirect((int) cap);
+        final long[] written = new long[1];
+        VMNException.check(plain ? VMNHip.vmn_garrays_to_jsonplainDirect(h, width, buf, cap, written)
+                                 : VMNHip.vmn_garrays_to_jsonlinesDirect(h, width, buf, cap, written));
+        buf.limit((int) written[0]);
+        return buf;
     }
 
     /** The reverse (CiphertextWriterLine): lowercase digits, every line ended by a newline, into a fresh direct buffer. */

@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
-"""vmnc_convert.py — the reference's `vmnc -ciphs -ini FMT -outi FMT in out`: a ciphertext list from one interface to another.
+"""vmnc_convert.py — the reference's `vmnc -ciphs -ini FMT -outi FMT in out`: a ciphertext list from one interface to another,
+and `vmnc -plain -outi FMT in out`: the plaintexts the mix-net left behind in the form of an interface.
 
   python tools/vmnc_convert.py -ciphs -ini native -outi raw [-width W] (--bits B | --curve NAME) [--wire java|natural] IN OUT
+  python tools/vmnc_convert.py -plain -outi json [-width W] --bits B [--wire java|natural] IN OUT
 
-FMT: native (one ciphertext per line, the line the hexadecimal byte tree of that ciphertext; the reference's default) or raw
-(one byte tree of the 2 W component arrays; what the mix-net and a proof directory hold).  The group is the RFC 3526 safe-prime
+FMT: native (one ciphertext per line, the line the hexadecimal byte tree of that ciphertext; the reference's default), raw
+(one byte tree of the 2 W component arrays; what the mix-net and a proof directory hold) or json (one ciphertext per line,
+{"alpha":"A","beta":"B"} with decimal strings, an array of W such pairs above width 1; modular groups only, so --curve with
+json is a usage error).  -plain reads the raw array tree of the W plaintext components and writes json ("M" per line, or
+["M1",...,"MW"]) or raw again; it takes no -ini.  The group is the RFC 3526 safe-prime
 group of B bits or the named curve, at the reference's leaf widths (--wire java, the default) or at the bytes of the modulus.
 The list is parsed, range- and membership-checked and written on the GPU (verificatum_vmn_amd.interface).
 
-Exit status: 0 the list was converted; 1 IN is no list of the input interface (a malformed native line is named, counted from
-1, on stderr), no output is written; 2 usage; 3 no GPU (there is no host conversion to fall back to)."""
+Exit status: 0 the list was converted; 1 IN is no list of the input interface (a malformed native or json line is named,
+counted from 1, on stderr), no output is written; 2 usage; 3 no GPU (there is no host conversion to fall back to)."""
 import argparse
 import os
 import sys
@@ -27,9 +32,11 @@ class _Parser(argparse.ArgumentParser):
 
 def main(argv=None):
     ap = _Parser(prog="vmnc_convert.py")
-    ap.add_argument("-ciphs", action="store_true", required=True, help="convert a list of ciphertexts (the one conversion there is)")
-    ap.add_argument("-ini", choices=("native", "raw"), required=True)
-    ap.add_argument("-outi", choices=("native", "raw"), required=True)
+    what = ap.add_mutually_exclusive_group(required=True)
+    what.add_argument("-ciphs", action="store_true", help="convert a list of ciphertexts")
+    what.add_argument("-plain", action="store_true", help="write the raw plaintexts in the form of an interface (json or raw)")
+    ap.add_argument("-ini", choices=("native", "raw", "json"))
+    ap.add_argument("-outi", choices=("native", "raw", "json"), required=True)
     ap.add_argument("-width", type=int, default=1)
     grp_arg = ap.add_mutually_exclusive_group(required=True)
     grp_arg.add_argument("--bits", type=int)
@@ -41,6 +48,14 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.width < 1:
         ap.error("-width must be at least 1")
+    if args.ciphs and args.ini is None:
+        ap.error("-ciphs needs -ini")
+    if args.plain and args.ini is not None:
+        ap.error("-plain reads the raw plaintexts: it takes no -ini")
+    if args.plain and args.outi == "native":
+        ap.error("-plain writes json or raw")
+    if args.curve is not None and "json" in (args.ini, args.outi):
+        ap.error("the json interface covers modular groups only")
     import __graft_entry__ as entry
     vmn = entry.load_package()
     from verificatum_vmn_amd import interface, stdgroups
@@ -64,11 +79,21 @@ def main(argv=None):
             grp = vmn.ECqPGroup(ctx, args.curve, java_widths=args.wire == "java")
         except (KeyError, ValueError, vmn.VmnError) as e:
             ap.error("unknown curve %r (%s)" % (args.curve, e))
+    if args.plain:
+        comps = interface.read_plaintexts(grp, args.input, args.width)
+        if comps is None:
+            sys.stderr.write("%s: not a raw list of plaintexts of width %d over this group\n" % (args.input, args.width))
+            return 1
+        interface.write_plaintexts(args.output, comps, args.outi)
+        return 0
     report = {}
-    ok = interface.convert_ciphertexts(grp, args.input, args.output, args.width, args.ini, args.outi, report=report)
+    ok = interface.convert_list(grp, args.input, args.output, args.width, args.ini, args.outi, report=report)
     if ok:
         return 0
-    if args.ini == "native" and report and not report["format_ok"]:
+    if args.ini == "json" and report and not report["format_ok"]:
+        sys.stderr.write("%s: line %d is not a json ciphertext of width %d ({\"alpha\":\"..\",\"beta\":\"..\"} with decimal strings)\n"
+                         % (args.input, report["first_bad_line"] + 1, args.width))
+    elif args.ini == "native" and report and not report["format_ok"]:
         sys.stderr.write("%s: line %d is not a ciphertext of width %d over this group (%d hex digits of its byte tree)\n"
                          % (args.input, report["first_bad_line"] + 1, args.width, 2 * interface.ciphertext_line_bytes(grp, args.width)))
     else:

@@ -16,6 +16,7 @@
 #include "modp_instances.h"
 #include "ec_instances.h"
 #include "light_kernels.h"
+#include "decimal_kernels.h"
 #include "vmnhip_internal.h"
 #include "sha256.h"
 #include "sha512.h"
@@ -944,6 +945,8 @@ extern "C" void vmn_group_destroy(vmn_group* grp) {
         table_arena_put(grp->ctx, kv.second.d_tab, kv.second.bytes);      // (both streams have drained: nothing reads them any more)
         if (kv.second.ready) (void)hipEventDestroy(kv.second.ready);
     }
+    if (grp->dec.d_pow10) (void)hipFree(grp->dec.d_pow10);
+    if (grp->dec.d_pow2) (void)hipFree(grp->dec.d_pow2);
     if (grp->curve) {
         if (grp->P.d_one) (void)hipFree(grp->P.d_one);
         grp->P = vmn_modulus();
@@ -2096,6 +2099,57 @@ static int hexlines_upload_layout(vmn_ctx* ctx, const hexlines::Layout& L, DevTm
 }
 static unsigned hexlines_grid(size_t nlines) { return (unsigned)((nlines * HEXLINES_LANES + BLOCK - 1) / BLOCK); }
 
+// Where the lines of a text are (both line interfaces): count() uploads the text and counts its lines -- terminators per chunk
+// and their scan --, walk() writes where every line begins and ends.  misc: u64 terminators | u32 first bad line | u32 scan total.
+struct TextLines {
+    DevTmp dtext, counts, first, bsum, misc, starts, ends;
+    const char* family;
+    size_t len = 0, nchunks = 0, nlines = 0;
+    TextLines(vmn_ctx* ctx, const char* fam) : dtext(ctx), counts(ctx), first(ctx), bsum(ctx), misc(ctx), starts(ctx), ends(ctx), family(fam) {}
+    const uint8_t* text() { return dtext.as<uint8_t>(); }
+    uint32_t* first_bad() { return misc.as<uint32_t>() + 2; }
+    int refuse(const char* why) {                              // (named by the interface: __func__ here is this helper's)
+        set_error("reading %s: %s", family, why);
+        return VMN_ERR_ARG;
+    }
+    int count(vmn_ctx* ctx, const uint8_t* utext, size_t text_len) {
+        len = text_len;
+        nchunks = (len + HEXLINES_CHUNK - 1) / HEXLINES_CHUNK;
+        if (nchunks >= ((size_t)1 << 31)) return refuse("text too long");
+        if (!len) return VMN_OK;
+        VMN_TRY(dtext.alloc(len + HEXLINES_PAD));
+        VMN_TRY(h2d(ctx, dtext.p, utext, len));
+        const size_t scan_blocks = (nchunks + (size_t)BLOCK * SCAN_ITEMS - 1) / ((size_t)BLOCK * SCAN_ITEMS);
+        VMN_TRY(counts.alloc(nchunks * sizeof(uint32_t)));
+        VMN_TRY(first.alloc((nchunks + 1) * sizeof(uint32_t)));
+        VMN_TRY(bsum.alloc((scan_blocks + 1) * sizeof(uint32_t)));
+        VMN_TRY(misc.alloc(16));
+        const uint32_t misc_init[4] = {0, 0, 0xffffffffu, 0};
+        VMN_TRY(h2d(ctx, misc.p, misc_init, sizeof(misc_init)));
+        VMN_TRY(launch_light(ctx, family, k_hexlines_count, (unsigned)nchunks, counts.as<uint32_t>(), (unsigned long long*)misc.p, text(), len));
+        VMN_TRY(launch_light(ctx, family, k_u32_blocksum, (unsigned)scan_blocks, bsum.as<uint32_t>(), (const uint32_t*)counts.as<uint32_t>(),
+                             nchunks));
+        hipLaunchKernelGGL(k_u32_scan_top, dim3(1), dim3(64), 0, ctx->stream, bsum.as<uint32_t>(), scan_blocks, misc.as<uint32_t>() + 3);
+        VMN_HIP(hipGetLastError());
+        VMN_TRY(launch_light(ctx, family, k_u32_scan_apply, (unsigned)scan_blocks, first.as<uint32_t>(), (uint32_t*)nullptr,
+                             (const uint32_t*)counts.as<uint32_t>(), (const uint32_t*)bsum.as<uint32_t>(), nchunks));
+        uint32_t got[4];
+        VMN_TRY(d2h(ctx, got, misc.p, sizeof(got)));
+        const uint64_t terms = (uint64_t)got[0] | ((uint64_t)got[1] << 32);
+        const bool open_end = utext[len - 1] != '\n' && utext[len - 1] != '\r';        // text behind the last terminator: one more line
+        if (terms + (open_end ? 1 : 0) >= 0xffffffffull) return refuse("2^32 lines or more");
+        nlines = (size_t)terms + (open_end ? 1 : 0);
+        return VMN_OK;
+    }
+    int walk(vmn_ctx* ctx) {                                   // (nlines != 0)
+        VMN_TRY(starts.alloc(nlines * sizeof(uint64_t)));
+        VMN_TRY(ends.alloc(nlines * sizeof(uint64_t)));
+        return launch_light(ctx, family, k_hexlines_walk, (unsigned)nchunks, (u64*)starts.p, (u64*)ends.p, text(), len,
+                            (const uint32_t*)first.as<uint32_t>(), (uint32_t)nlines);
+    }
+    int read_first_bad(vmn_ctx* ctx, uint32_t* bad) { return d2h(ctx, bad, first_bad(), sizeof(*bad)); }
+};
+
 extern "C" size_t vmn_hexlines_line_bytes(const vmn_group* grp, size_t width) {
     return grp && hexlines_width_ok(grp, width) ? hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, width) : 0;
 }
@@ -2114,35 +2168,9 @@ extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const cha
     const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
 
     // where the lines are: terminators per chunk, their scan, then the starts and ends
-    size_t nlines = 0;
-    DevTmp dtext(ctx), counts(ctx), first(ctx), bsum(ctx), misc(ctx), starts(ctx), ends(ctx);
-    const size_t nchunks = (len + HEXLINES_CHUNK - 1) / HEXLINES_CHUNK;
-    ARG_CHECK(nchunks < ((size_t)1 << 31), "text too long");
-    if (len) {
-        VMN_TRY(dtext.alloc(len + HEXLINES_PAD));
-        VMN_TRY(h2d(ctx, dtext.p, utext, len));
-        const size_t scan_blocks = (nchunks + (size_t)BLOCK * SCAN_ITEMS - 1) / ((size_t)BLOCK * SCAN_ITEMS);
-        VMN_TRY(counts.alloc(nchunks * sizeof(uint32_t)));
-        VMN_TRY(first.alloc((nchunks + 1) * sizeof(uint32_t)));
-        VMN_TRY(bsum.alloc((scan_blocks + 1) * sizeof(uint32_t)));
-        VMN_TRY(misc.alloc(16));                               // u64 terminators | u32 first bad line | u32 scan total
-        const uint32_t misc_init[4] = {0, 0, 0xffffffffu, 0};
-        VMN_TRY(h2d(ctx, misc.p, misc_init, sizeof(misc_init)));
-        VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_count, (unsigned)nchunks, counts.as<uint32_t>(), (unsigned long long*)misc.p,
-                             (const uint8_t*)dtext.as<uint8_t>(), len));
-        VMN_TRY(launch_light(ctx, "hexlines", k_u32_blocksum, (unsigned)scan_blocks, bsum.as<uint32_t>(), (const uint32_t*)counts.as<uint32_t>(),
-                             nchunks));
-        hipLaunchKernelGGL(k_u32_scan_top, dim3(1), dim3(64), 0, ctx->stream, bsum.as<uint32_t>(), scan_blocks, misc.as<uint32_t>() + 3);
-        VMN_HIP(hipGetLastError());
-        VMN_TRY(launch_light(ctx, "hexlines", k_u32_scan_apply, (unsigned)scan_blocks, first.as<uint32_t>(), (uint32_t*)nullptr,
-                             (const uint32_t*)counts.as<uint32_t>(), (const uint32_t*)bsum.as<uint32_t>(), nchunks));
-        uint32_t got[4];
-        VMN_TRY(d2h(ctx, got, misc.p, sizeof(got)));
-        const uint64_t terms = (uint64_t)got[0] | ((uint64_t)got[1] << 32);
-        const bool open_end = utext[len - 1] != '\n' && utext[len - 1] != '\r';        // text behind the last terminator: one more line
-        ARG_CHECK(terms + (open_end ? 1 : 0) < 0xffffffffull, "2^32 lines or more");
-        nlines = (size_t)terms + (open_end ? 1 : 0);
-    }
+    TextLines lines(ctx, "hexlines");
+    VMN_TRY(lines.count(ctx, utext, len));
+    const size_t nlines = lines.nlines;
     if (expected_n != 0 && nlines != expected_n) {
         *first_bad_line = std::min(nlines, expected_n);
         return VMN_OK;
@@ -2153,15 +2181,13 @@ extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const cha
     if (nlines) {
         const uint8_t *d_tmpl = nullptr, *d_mask = nullptr;
         VMN_TRY(hexlines_upload_layout(ctx, L, layout, &d_tmpl, &d_mask));
-        VMN_TRY(starts.alloc(nlines * sizeof(uint64_t)));
-        VMN_TRY(ends.alloc(nlines * sizeof(uint64_t)));
         VMN_TRY(rec.alloc(nlines * L.B + 16));
-        VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_walk, (unsigned)nchunks, (u64*)starts.p, (u64*)ends.p, (const uint8_t*)dtext.as<uint8_t>(),
-                             len, (const uint32_t*)first.as<uint32_t>(), (uint32_t)nlines));
-        VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_decode, hexlines_grid(nlines), rec.as<uint8_t>(), (const uint8_t*)dtext.as<uint8_t>(), len,
-                             (const u64*)starts.p, (const u64*)ends.p, (uint32_t)nlines, (uint32_t)L.B, d_tmpl, d_mask, misc.as<uint32_t>() + 2));
+        VMN_TRY(lines.walk(ctx));
+        VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_decode, hexlines_grid(nlines), rec.as<uint8_t>(), lines.text(), len,
+                             (const u64*)lines.starts.p, (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)L.B, d_tmpl, d_mask,
+                             lines.first_bad()));
         uint32_t bad = 0;
-        VMN_TRY(d2h(ctx, &bad, misc.as<uint32_t>() + 2, sizeof(bad)));
+        VMN_TRY(lines.read_first_bad(ctx, &bad));
         if (bad != 0xffffffffu) {
             *first_bad_line = bad;
             return VMN_OK;
@@ -2228,6 +2254,236 @@ extern "C" int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t wi
     VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_encode, hexlines_grid(n), dtext.as<uint8_t>(), (const uint8_t*)rec.as<uint8_t>(), (uint32_t)n,
                          (uint32_t)L.B, d_tmpl, d_mask));
     return d2h(ctx, out, dtext.p, text_bytes);
+}
+
+// ---- the `json` ciphertext interface: one ciphertext per line, every number a decimal string; modular groups only ----------------
+// (csrc/jsonlines_layout.h for the text of a line, csrc/decimal_kernels.h for the kernels)
+// decimal digits of p: short division by 10^9 until nothing is left, then the digits of the last remainder
+static size_t decimal_digits_of(const Big& p) {
+    Big rest(p);
+    size_t digits = 0;
+    uint32_t last = 0;
+    while (!hostbig::is_zero(rest)) {
+        uint64_t r = 0;
+        for (size_t k = rest.size(); k-- > 0;) {
+            const uint64_t cur = (r << 32) | rest[k];
+            rest[k] = (uint32_t)(cur / DEC_BASE);
+            r = cur % DEC_BASE;
+        }
+        last = (uint32_t)r;
+        digits += DEC_DIGITS;
+    }
+    if (!digits) return 1;
+    digits -= DEC_DIGITS;
+    for (; last; last /= 10) ++digits;
+    return digits;
+}
+// The tables of the two radix conversions, built once per group: 10^(9j) in 32-bit words, 2^(16h) in base 10^9.
+static int decimal_tables(vmn_group* grp, const vmn_group::DecimalTables** out) {
+    std::lock_guard<std::recursive_mutex> tab_guard(grp->tab_mu);
+    vmn_group::DecimalTables& T = grp->dec;
+    *out = &T;
+    if (T.d_pow10) return VMN_OK;
+    const Big& p = grp->P.n_words;
+    const uint32_t nw = (uint32_t)((hostbig::bit_length(p) + 31) / 32);
+    const uint32_t dmax = (uint32_t)decimal_digits_of(p);
+    const uint32_t nc = (dmax + DEC_DIGITS - 1) / DEC_DIGITS;
+    // 10^(9j), j <= nc, on as many words as 10^(9 nc) has: below 2^(30 nc)
+    const size_t cap = ((size_t)30 * nc + 31) / 32 + 1;
+    std::vector<std::vector<uint32_t>> pows(nc + 1, std::vector<uint32_t>(cap, 0));
+    pows[0][0] = 1;
+    for (uint32_t j = 1; j <= nc; ++j) {
+        uint64_t carry = 0;
+        for (size_t i = 0; i < cap; ++i) {
+            const uint64_t t = (uint64_t)pows[j - 1][i] * DEC_BASE + carry;
+            pows[j][i] = (uint32_t)t;
+            carry = t >> 32;
+        }
+    }
+    uint32_t nwa = (uint32_t)cap;
+    while (nwa > 1 && pows[nc][nwa - 1] == 0) --nwa;
+    if (nc > (uint32_t)DEC_MAX_CHUNKS || nwa > (uint32_t)DEC_MAX_WORDS || nw > (uint32_t)DEC_MAX_WORDS) {
+        set_error("the json interface holds moduli of up to 16384 bits");
+        return VMN_ERR_UNSUPPORTED;
+    }
+    std::vector<uint32_t> pow10((size_t)nc * nwa), pow2((size_t)2 * nw * nc);
+    for (uint32_t j = 0; j < nc; ++j) std::copy(pows[j].begin(), pows[j].begin() + nwa, pow10.begin() + (size_t)j * nwa);
+    // 2^(16h), h < 2 nw, in base 10^9: the chunks beyond nc are dropped -- a value below p has no half word that meets them
+    std::vector<uint32_t> cur(nc + 8, 0);
+    cur[0] = 1;
+    for (uint32_t h = 0; h < 2 * nw; ++h) {
+        std::copy(cur.begin(), cur.begin() + nc, pow2.begin() + (size_t)h * nc);
+        uint64_t carry = 0;
+        for (size_t k = 0; k < cur.size(); ++k) {
+            const uint64_t t = ((uint64_t)cur[k] << 16) + carry;
+            cur[k] = (uint32_t)(t % DEC_BASE);
+            carry = t / DEC_BASE;
+        }
+    }
+    uint32_t *d10 = nullptr, *d2 = nullptr;
+    VMN_HIP(hipMalloc(&d10, pow10.size() * sizeof(uint32_t)));
+    hipError_t he = hipMalloc(&d2, pow2.size() * sizeof(uint32_t));
+    if (he == hipSuccess) he = hipMemcpy(d10, pow10.data(), pow10.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d2, pow2.data(), pow2.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        set_error("decimal tables: %s", hipGetErrorString(he));
+        (void)hipFree(d10);
+        if (d2) (void)hipFree(d2);
+        return he == hipErrorOutOfMemory ? VMN_ERR_NOMEM : VMN_ERR_DEVICE;
+    }
+    T.dmax = dmax;
+    T.nc = nc;
+    T.nwa = nwa;
+    T.nw = nw;
+    T.d_pow2 = d2;
+    T.d_pow10 = d10;
+    return VMN_OK;
+}
+static bool jsonlines_width_ok(size_t width) { return width >= 1 && width <= jsonlines::MAX_WIDTH; }
+#define JSON_GROUP_CHECK(grp)                                                                                  \
+    do {                                                                                                       \
+        if ((grp)->curve) {                                                                                    \
+            set_error("%s: the json interface covers modular groups only (as the reference's)", __func__);     \
+            return VMN_ERR_UNSUPPORTED;                                                                        \
+        }                                                                                                      \
+    } while (0)
+
+extern "C" size_t vmn_jsonlines_max_line_bytes(const vmn_group* grp, size_t width) {
+    if (!grp || grp->curve || !jsonlines_width_ok(width)) return 0;
+    const size_t dmax = grp->dec.dmax ? grp->dec.dmax : decimal_digits_of(grp->P.n_words);
+    return jsonlines::max_ciphertext_line(dmax, width);
+}
+extern "C" int vmn_garrays_from_jsonlines(vmn_group* grp, size_t width, const char* text, size_t len, size_t expected_n, vmn_garray** out,
+                                          size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range) {
+    ARG_CHECK(grp && out && n_out && format_ok && first_bad_line && (text || len == 0), "null argument");
+    ARG_CHECK(jsonlines_width_ok(width), "width out of range");
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    for (size_t c = 0; c < 2 * width; ++c) out[c] = nullptr;
+    *n_out = 0;
+    *format_ok = 0;
+    *first_bad_line = 0;
+    if (all_in_range) *all_in_range = 1;
+    JSON_GROUP_CHECK(grp);
+    const vmn_group::DecimalTables* T = nullptr;
+    VMN_TRY(decimal_tables(grp, &T));
+    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
+    const size_t ncomp = 2 * width, nbytes = grp->nbytes;
+
+    TextLines lines(ctx, "jsonlines");
+    VMN_TRY(lines.count(ctx, utext, len));
+    const size_t nlines = lines.nlines;
+    if (expected_n != 0 && nlines != expected_n) {
+        *first_bad_line = std::min(nlines, expected_n);
+        return VMN_OK;
+    }
+
+    // the grammar of every line and the digit spans of its numbers; then decimal -> records of nbytes, component by component
+    DevTmp span_at(ctx), span_len(ctx), rec(ctx);
+    const size_t total = nlines * ncomp;
+    if (nlines) {
+        ARG_CHECK(total / ncomp == nlines && total < ((size_t)1 << 40), "too many numbers");
+        VMN_TRY(span_at.alloc(total * sizeof(uint64_t)));
+        VMN_TRY(span_len.alloc(total * sizeof(uint32_t)));
+        VMN_TRY(lines.walk(ctx));
+        VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_scan, grid_for(nlines), (u64*)span_at.p, span_len.as<uint32_t>(), lines.text(), len,
+                             (const u64*)lines.starts.p, (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)width, lines.first_bad()));
+        uint32_t bad = 0;
+        VMN_TRY(lines.read_first_bad(ctx, &bad));
+        if (bad != 0xffffffffu) {
+            *first_bad_line = bad;
+            return VMN_OK;
+        }
+        VMN_TRY(rec.alloc(total * nbytes + 16));
+        const size_t blocks = (total + DEC_VPB - 1) / DEC_VPB;
+        ARG_CHECK(blocks < ((size_t)1 << 31), "too many numbers");
+        VMN_TRY(launch_light(ctx, "jsonlines", k_dec_to_rows, (unsigned)blocks, rec.as<uint8_t>(), (uint32_t)nbytes, lines.text(),
+                             (const u64*)span_at.p, (const uint32_t*)span_len.as<uint32_t>(), (uint32_t)nlines, (uint32_t)ncomp, T->dmax, T->nwa,
+                             (const uint32_t*)T->d_pow10));
+    }
+
+    std::vector<vmn_garray*> arrays(ncomp, nullptr);
+    auto drop = [&] {
+        for (vmn_garray* a : arrays) vmn_garray_free(a);
+    };
+    int rc = VMN_OK;
+    for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    uint32_t fl = 0;
+    if (rc == VMN_OK && nlines) {
+        rc = dev_zero(ctx, ctx->flags, sizeof(uint32_t));
+        for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) {
+            note_work(ctx, grp->P, (double)nlines);
+            rc = import_rows_launch(ctx, grp->P, nbytes, rec.as<uint8_t>() + c * nlines * nbytes, nbytes, 0, nlines, arrays[c]->d);
+        }
+        if (rc == VMN_OK) rc = read_flag(ctx, &fl);
+    }
+    if (rc != VMN_OK) {
+        drop();
+        return rc;
+    }
+    for (size_t c = 0; c < ncomp; ++c) out[c] = arrays[c];
+    *n_out = nlines;
+    *format_ok = 1;
+    if (all_in_range) *all_in_range = (fl & 1u) ? 0 : 1;
+    return VMN_OK;
+}
+
+// the lines of `ncomp` arrays (2 width of a ciphertext list, width of a list of plaintexts) into a buffer of cap bytes
+static int jsonlines_write(const vmn_garray* const* comps, size_t width, int plain, char* out, size_t cap, size_t* written) {
+    const size_t ncomp = plain ? width : 2 * width;
+    vmn_group* grp = comps[0]->grp;
+    const size_t n = comps[0]->n, nbytes = grp->nbytes;
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    *written = 0;
+    JSON_GROUP_CHECK(grp);
+    if (n == 0) return VMN_OK;
+    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
+    const vmn_group::DecimalTables* T = nullptr;
+    VMN_TRY(decimal_tables(grp, &T));
+    const size_t total = n * ncomp;
+    ARG_CHECK(total / ncomp == n && total < ((size_t)1 << 40), "too many numbers");
+    DevTmp rec(ctx), digits(ctx), counts(ctx), lens(ctx), bsum(ctx), dtext(ctx);
+    VMN_TRY(rec.alloc(total * nbytes + 16));
+    VMN_TRY(digits.alloc(total * T->dmax + 16));
+    VMN_TRY(counts.alloc(total * sizeof(uint32_t)));
+    for (size_t c = 0; c < ncomp; ++c) VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, rec.as<uint8_t>() + c * n * nbytes, nbytes, 0));
+    const size_t blocks = (total + DEC_VPB - 1) / DEC_VPB;
+    ARG_CHECK(blocks < ((size_t)1 << 31), "too many numbers");
+    VMN_TRY(launch_light(ctx, "jsonlines", k_rows_to_dec, (unsigned)blocks, digits.as<uint8_t>(), counts.as<uint32_t>(),
+                         (const uint8_t*)rec.as<uint8_t>(), (uint32_t)nbytes, total, T->dmax, T->nc, T->nw, (const uint32_t*)T->d_pow2));
+    const size_t groups = (n + BLOCK - 1) / BLOCK;
+    VMN_TRY(lens.alloc(n * sizeof(uint32_t)));
+    VMN_TRY(bsum.alloc((groups + 1) * sizeof(uint64_t)));
+    VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_lengths, (unsigned)groups, lens.as<uint32_t>(), (u64*)bsum.p,
+                         (const uint32_t*)counts.as<uint32_t>(), (uint32_t)n, (uint32_t)width, plain));
+    VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_offsets, 1u, (u64*)bsum.p, groups, (u64*)bsum.p + groups));
+    uint64_t text_bytes = 0;
+    VMN_TRY(d2h(ctx, &text_bytes, (const u64*)bsum.p + groups, sizeof(text_bytes)));
+    ARG_CHECK(text_bytes <= cap && out, "the buffer is too small for this list");
+    VMN_TRY(dtext.alloc(text_bytes + 16));
+    VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_emit, (unsigned)((n * JSONLINES_LANES + BLOCK - 1) / BLOCK), dtext.as<uint8_t>(),
+                         (const u64*)bsum.p, (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)digits.as<uint8_t>(),
+                         (const uint32_t*)counts.as<uint32_t>(), (uint32_t)n, (uint32_t)width, T->dmax, plain));
+    VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));
+    *written = (size_t)text_bytes;
+    return VMN_OK;
+}
+static bool jsonlines_comps_ok(const vmn_garray* const* comps, size_t ncomp) {
+    if (!comps || !comps[0]) return false;
+    for (size_t c = 0; c < ncomp; ++c)
+        if (!comps[c] || comps[c]->grp != comps[0]->grp || comps[c]->n != comps[0]->n) return false;
+    return true;
+}
+extern "C" int vmn_garrays_to_jsonlines(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written) {
+    ARG_CHECK(comps && written && jsonlines_width_ok(width), "null argument or width out of range");
+    ARG_CHECK(jsonlines_comps_ok(comps, 2 * width), "2 * width arrays of one group and one size are needed");
+    return jsonlines_write(comps, width, 0, out, cap, written);
+}
+extern "C" int vmn_garrays_to_jsonplain(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written) {
+    ARG_CHECK(comps && written && jsonlines_width_ok(width), "null argument or width out of range");
+    ARG_CHECK(jsonlines_comps_ok(comps, width), "width arrays of one group and one size are needed");
+    return jsonlines_write(comps, width, 1, out, cap, written);
 }
 
 extern "C" int vmn_garray_to_be(const vmn_garray* a, uint8_t* be_out) {

@@ -197,6 +197,17 @@ struct vmn_group {
     // least-recently-used tables are dropped beyond fixed_cache_limit() bytes (64 GB, env VMN_FIXED_CACHE_BYTES) (every proof brings a new base h_0)
     size_t fixed_bytes = 0;
     uint64_t fixed_clock = 0;
+    // The json interface (csrc/decimal_kernels.h), modular groups only: the tables of powers of the two radix conversions, built
+    // on first use (under tab_mu) and kept until the group goes.
+    struct DecimalTables {
+        uint32_t* d_pow10 = nullptr;   // nc rows of nwa words: 10^(9j)
+        uint32_t* d_pow2 = nullptr;    // 2 nw rows of nc chunks (base 10^9): 2^(16h)
+        uint32_t dmax = 0;             // decimal digits of p
+        uint32_t nc = 0;               // ceil(dmax / 9)
+        uint32_t nwa = 0;              // words of 10^(9 nc)
+        uint32_t nw = 0;               // words of p
+    };
+    DecimalTables dec;
 };
 
 struct vmn_garray {

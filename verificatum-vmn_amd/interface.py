@@ -1,4 +1,4 @@
-"""interface.py — the files in front of a session: ciphertext lists in the reference's two interfaces.
+"""interface.py — the files in front of a session: ciphertext lists, plaintexts and the public key in the reference's interfaces.
 
 ``raw``     one byte tree holding the 2w component arrays (``proofdir.read_ciphertexts`` / ``write_ciphertexts``): what
             the mix-net works on and what a proof directory holds.
@@ -6,20 +6,30 @@
             ``CiphertextWriterLine``): one ciphertext per line, the line being the hexadecimal byte tree of that single
             ciphertext.  A ballot box delivers this; the first command of an election is ``vmnc -ciphs -ini native -outi raw``.
 
+``json``    ``ProtocolElGamalInterfaceJSON`` / ``...JSONDecode``, the format of Helios-style ballot boxes, modular groups only:
+            a ciphertext line is ``{"alpha":"A","beta":"B"}`` (an array of such pairs at width > 1), a plaintext line ``"M"``,
+            the public key one map ``{"g":..,"p":..,"q":..,"y":..,"encoding":..}``; every number is a decimal string.
+
 The native text is an array of structures, the arrays are a structure of arrays: the N lines are found, decoded, checked and
 transposed on the GPU (``vmn_garrays_from_hexlines`` / ``vmn_garrays_to_hexlines``, csrc/light_kernels.h), not in a loop over
-the lines.  Both readers apply one policy to what enters here from outside: a format defect, a value out of range or an
-element outside the group is no list (``None``).
+the lines; ``read_ciphertexts`` / ``write_ciphertexts`` / ``convert_ciphertexts`` are the file functions of these two interfaces.
+The json text is converted from and to decimal on the GPU as well (``vmn_garrays_from_jsonlines`` / ``_to_jsonlines`` /
+``_to_jsonplain``, csrc/decimal_kernels.h); ``read_list`` / ``write_list`` / ``convert_list`` take all three interfaces.  All readers
+apply one policy to what enters here from outside: a format defect, a value out of range or an element outside the group is no
+list (``None``).
 """
 from __future__ import annotations
 
 import ctypes as C
+import json
 from typing import List, Optional, Sequence
 
 from . import PGroupElementArray, _check, host_block, lib
 from . import proofdir
 
-FORMATS = ("native", "raw")
+FORMATS = ("native", "raw")                  # what read_ciphertexts / write_ciphertexts / convert_ciphertexts take
+INTERFACES = FORMATS + ("json",)             # what read_list / write_list / convert_list take
+PLAINTEXT_FORMATS = ("json", "raw")
 
 
 def ciphertext_line_bytes(grp, width: int) -> int:
@@ -73,6 +83,57 @@ def format_native(comps: Sequence[PGroupElementArray]) -> bytes:
     return out.raw[:size]
 
 
+def json_max_line_bytes(grp, width: int) -> int:
+    """The longest json ciphertext line over ``grp`` at ``width``, newline included (0 over a curve group)."""
+    return lib().vmn_jsonlines_max_line_bytes(grp._h, C.c_size_t(width))
+
+
+def parse_json(grp, text, width: int, expected_n: int = 0, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+    """``parse_native`` for a json list: the 2w component arrays, or ``None`` under the same policy, with the same ``report``
+    keys.  A curve group raises (the json interface covers modular groups only, as the reference's)."""
+    blk = host_block(text) or host_block(bytes(text))
+    hs = (C.c_void_p * (2 * width))()
+    n, bad = C.c_size_t(0), C.c_size_t(0)
+    fmt, rng = C.c_int(0), C.c_int(1)
+    _check(lib().vmn_garrays_from_jsonlines(grp._h, C.c_size_t(width), blk[0], C.c_size_t(blk[1]), C.c_size_t(expected_n), hs,
+                                            C.byref(n), C.byref(fmt), C.byref(bad), C.byref(rng)))
+    if report is not None:
+        report.update(format_ok=bool(fmt.value), first_bad_line=bad.value, all_in_range=bool(rng.value), lines=n.value)
+    if not fmt.value:
+        return None
+    comps = [PGroupElementArray(grp, C.c_void_p(h)) for h in hs]
+    if not rng.value:
+        _free(comps)
+        return None
+    return _members_or_none(comps)
+
+
+def _json_lines(comps: Sequence[PGroupElementArray], width: int, plain: bool) -> bytes:
+    if not comps:
+        raise ValueError("no arrays")
+    grp, n = comps[0].group, comps[0].size()
+    hs = (C.c_void_p * len(comps))(*[a._h for a in comps])
+    cap = max(1, n * json_max_line_bytes(grp, width))
+    out = C.create_string_buffer(cap)
+    written = C.c_size_t(0)
+    call = lib().vmn_garrays_to_jsonplain if plain else lib().vmn_garrays_to_jsonlines
+    _check(call(hs, C.c_size_t(width), out, C.c_size_t(cap), C.byref(written)))
+    return out.raw[:written.value]
+
+
+def format_json(comps: Sequence[PGroupElementArray]) -> bytes:
+    """The json text of a list given as its 2w component arrays, exactly as the reference writes it."""
+    width = len(comps) // 2
+    if width < 1 or len(comps) != 2 * width:
+        raise ValueError("a ciphertext list has 2 * width component arrays")
+    return _json_lines(comps, width, False)
+
+
+def format_json_plaintexts(comps: Sequence[PGroupElementArray]) -> bytes:
+    """The json text of a list of plaintexts given as its w component arrays: line i is ``"M"`` or ``["M1",...,"Mw"]``."""
+    return _json_lines(comps, len(comps), True)
+
+
 def read_ciphertexts(grp, path: str, width: int, fmt: str = "native", expected_n: int = 0,
                      report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
     """The list file at ``path`` in the interface ``fmt``; ``None`` when it is missing or is no such list."""
@@ -97,6 +158,58 @@ def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray], fmt: str =
         f.write(text)
 
 
+def read_plaintexts(grp, path: str, width: int) -> Optional[List[PGroupElementArray]]:
+    """The w component arrays of a raw list of plaintexts (what the mix-net leaves behind: one array tree at width 1, the node of
+    w array trees above); ``None`` when the file is missing or is no such list -- format, range and membership as for a list
+    of ciphertexts."""
+    buf = proofdir._read_file(path)
+    if buf is None:
+        return None
+    buf = bytes(buf)
+    if width == 1:
+        parts = [buf]
+    else:
+        if len(buf) < 5 or buf[0] != 0 or int.from_bytes(buf[1:5], "big") != width:
+            return None
+        parts, at = [], 5
+        for _ in range(width):                               # every child: a node of n leaves of the group's width
+            if len(buf) < at + 5 or buf[at] != 0:
+                return None
+            size = 5 + int.from_bytes(buf[at + 1:at + 5], "big") * (5 + grp.elem_bytes)
+            parts.append(buf[at:at + size])
+            at += size
+        if at != len(buf):
+            return None
+    comps = []
+    try:
+        for part in parts:
+            comps.append(grp.toElementArrayFromByteTree(part))
+    except (ValueError, RuntimeError):
+        _free(comps)
+        return None
+    if len({a.size() for a in comps}) != 1:
+        _free(comps)
+        return None
+    return _members_or_none(comps)
+
+
+def write_plaintexts(path: str, comps: Sequence[PGroupElementArray], fmt: str = "json") -> None:
+    """decodePlaintexts: the list of plaintexts given as its w component arrays, as ``json`` lines or ``raw`` -- the array tree
+    as it is (ProtocolElGamalInterfaceRaw.java:93-96): one array at width 1, the node of the w arrays above."""
+    if fmt not in PLAINTEXT_FORMATS:
+        raise ValueError("unknown plaintext interface %r (%s)" % (fmt, ", ".join(PLAINTEXT_FORMATS)))
+    if not comps:
+        raise ValueError("no arrays")
+    if fmt == "json":
+        data = format_json_plaintexts(comps)
+    elif len(comps) == 1:
+        data = comps[0].toByteTree()
+    else:
+        data = b"\x00" + len(comps).to_bytes(4, "big") + b"".join(a.toByteTree() for a in comps)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def convert_ciphertexts(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None) -> bool:
     """``vmnc -ciphs -ini in_fmt -outi out_fmt src dst``: False (and no output file) when ``src`` is no list of ``in_fmt``."""
     comps = read_ciphertexts(grp, src, width, in_fmt, report=report)
@@ -107,3 +220,84 @@ def convert_ciphertexts(grp, src: str, dst: str, width: int, in_fmt: str, out_fm
     finally:
         _free(comps)
     return True
+
+
+# ---- all three interfaces ---------------------------------------------------------------------------------------------------------
+# read_ciphertexts / write_ciphertexts / convert_ciphertexts keep the two interfaces they were written for: that any other name,
+# "json" among them, is a ValueError there is their contract (tests/test_gpu_hexlines.py).  These three take every interface of
+# INTERFACES under the same policy -- a format defect, a value out of range or a non-member is no list.
+def read_list(grp, path: str, width: int, fmt: str, expected_n: int = 0, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+    """The list file at ``path`` in the interface ``fmt`` (native, raw, json); ``None`` when it is missing or is no such list."""
+    if fmt not in INTERFACES:
+        raise ValueError("unknown interface %r (%s)" % (fmt, ", ".join(INTERFACES)))
+    if fmt != "json":
+        return read_ciphertexts(grp, path, width, fmt, expected_n, report)
+    buf = proofdir._read_file(path)
+    if buf is None:
+        return None
+    return parse_json(grp, buf, width, expected_n, report)
+
+
+def write_list(path: str, comps: Sequence[PGroupElementArray], fmt: str) -> None:
+    if fmt not in INTERFACES:
+        raise ValueError("unknown interface %r (%s)" % (fmt, ", ".join(INTERFACES)))
+    if fmt != "json":
+        write_ciphertexts(path, comps, fmt)
+        return
+    text = format_json(comps)
+    with open(path, "wb") as f:
+        f.write(text)
+
+
+def convert_list(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None) -> bool:
+    """``vmnc -ciphs -ini in_fmt -outi out_fmt src dst`` over all three interfaces: False (and no output file) when ``src`` is no
+    list of ``in_fmt``."""
+    if out_fmt not in INTERFACES:
+        raise ValueError("unknown interface %r (%s)" % (out_fmt, ", ".join(INTERFACES)))
+    comps = read_list(grp, src, width, in_fmt, report=report)
+    if comps is None:
+        return False
+    try:
+        write_list(dst, comps, out_fmt)
+    finally:
+        _free(comps)
+    return True
+
+
+# ---- the public key of the json interface: four numbers, on the host -------------------------------------------------------------
+def write_public_key_json(path: str, p: int, q: int, g: int, y: int, encoding: Optional[int] = None) -> None:
+    """``{"g":..,"p":..,"q":..,"y":..,"encoding":..}`` with decimal strings (ProtocolElGamalInterfaceJSON.java:110-126).
+    ``encoding``: VCR's ModPGroup encoding scheme; by default 1 for a safe prime (p = 2q + 1), else 2."""
+    if encoding is None:
+        encoding = 1 if p == 2 * q + 1 else 2
+    text = json.dumps({"g": str(g), "p": str(p), "q": str(q), "y": str(y), "encoding": str(encoding)}, separators=(",", ":"))
+    with open(path, "w") as f:
+        f.write(text)
+
+
+def _decimal(value) -> int:
+    if not isinstance(value, str) or not value.isascii() or not value.isdigit():
+        raise ValueError("not an unsigned decimal string: %r" % (value,))
+    return int(value)
+
+
+def read_public_key_json(path: str) -> dict:
+    """``{"p", "q", "g", "y", "encoding"}`` as integers (ProtocolElGamalInterfaceJSON.java:151-206).  The file needs at least p, q,
+    g and y; without "encoding" it is 1 when p = 2q + 1, else 2; y must lie in the group.  ``ValueError`` otherwise."""
+    with open(path) as f:
+        try:
+            obj = json.load(f)
+        except ValueError as e:
+            raise ValueError("no json public key: %s" % e)
+    if not isinstance(obj, dict):
+        raise ValueError("no json public key: not a map")
+    missing = [k for k in ("p", "q", "g", "y") if k not in obj]
+    if missing:
+        raise ValueError("no json public key: %s missing" % ", ".join(missing))
+    p, q, g, y = (_decimal(obj[k]) for k in ("p", "q", "g", "y"))
+    encoding = _decimal(obj["encoding"]) if "encoding" in obj else (1 if p == 2 * q + 1 else 2)
+    if not (p > 2 and q > 1 and (p - 1) % q == 0 and 1 < g < p and pow(g, q, p) == 1):
+        raise ValueError("no json public key: p, q, g are no group")
+    if not (0 < y < p and pow(y, q, p) == 1):
+        raise ValueError("no json public key: y is not in the group")
+    return {"p": p, "q": q, "g": g, "y": y, "encoding": encoding}
