@@ -651,8 +651,11 @@ def test_two_powers_in_one_launch(bits, groups, oracle_for):
 def test_one_exponent_for_the_whole_array_sliding_window(bits, vmn, gpu_ctx, oracle_for, monkeypatch):
     """K1b (csrc/modp_shared_exp.h): X.exp(e) with ONE exponent walks a host-made sliding-window schedule.  Exponents that
     stress the schedule -- a single window, powers of two (trailing zeros only), all ones, alternating runs, the group order
-    minus one, a full-length secret like a decryption share -- in the base and the wide geometries, against GMP and against
-    the fixed-window kernel (VMN_SLIDING_WINDOW=0)."""
+    minus one, a full-length secret like a decryption share -- against GMP and against the fixed-window kernel
+    (VMN_SLIDING_WINDOW=0).  Its sizes (300 and 7 elements) choose the geometry themselves: eight lanes per element (Cfg<80, 8>)
+    at 2048 bits, four (Cfg<112, 4>) at 3072 bits, the single geometry at 4096 bits.  The base and the four-lane geometries of
+    2048 bits and the base one of 3072 bits are forced in tests/test_gpu_power_geometries.py.  (On the device of one
+    workgroup slot below, the schedules of two steps -- 1 << 200, 1 << 33 -- have one step to cut and stay in the plain kernel.)"""
     p, q, g = pyref.modp_group(bits)
     orc = oracle_for(p, q)
     G = vmn.ModPGroup(gpu_ctx, p, q, g)
