@@ -189,6 +189,19 @@ int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const char* text, si
                               size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range);
 size_t vmn_garrays_hexlines_size(const vmn_garray* const* comps, size_t width);
 int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t width, char* out);
+/* The same under a public key of width keywidth (ProtocolElGamal.java:476-481): the plaintext group is G^keywidth, and each half
+ * of a line is [width > 1: node(width; ...)] over [keywidth > 1: node(keywidth; ...)] over element trees, so
+ * B = 5 + 2 ((width > 1 ? 5 : 0) + width ((keywidth > 1 ? 5 : 0) + keywidth E)) [NOT-IN-REF: PPGroupElement.toByteTree is VCR
+ * code; SURVEY.md App. D's rule, applied once more].  The 2 * keywidth * width component arrays come and go in flat order, the
+ * u half first, component c = l * keywidth + j the key j of plaintext component l.  keywidth = 1 is the functions above (which
+ * call these); width = 1 gives the bytes of an unkeyed list of width keywidth.  Defects are reported as above; the bounds on
+ * the widths are the ones above, applied to keywidth * width.  The nesting lives in the line's template and mask alone: the
+ * kernels and the number of launches are those of an unkeyed list of width keywidth * width. */
+size_t vmn_hexlines_line_bytes_keyed(const vmn_group* grp, size_t keywidth, size_t width);
+int vmn_garrays_from_hexlines_keyed(vmn_group* grp, size_t keywidth, size_t width, const char* text, size_t len, size_t expected_n,
+                                    vmn_garray** out, size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range);
+size_t vmn_garrays_hexlines_size_keyed(const vmn_garray* const* comps, size_t keywidth, size_t width);
+int vmn_garrays_to_hexlines_keyed(const vmn_garray* const* comps, size_t keywidth, size_t width, char* out);
 /* Ciphertext lists and plaintexts in the reference's `json` interface (ProtocolElGamalInterfaceJSON / ...JSONDecode: the format of
  * Helios-style ballot boxes), modular groups only, as in the reference: a curve group is VMN_ERR_UNSUPPORTED.  A ciphertext line is
  * {"alpha":"A","beta":"B"} at width 1 and [{"alpha":"A1","beta":"B1"},...,{"alpha":"Aw","beta":"Bw"}] above (pair i = u_i, v_i), a

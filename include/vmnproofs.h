@@ -102,6 +102,19 @@ int vmn_msg_to_bytetree(const vmn_msg* m, uint8_t* out);
  * caller substitutes trivial values as the reference does (PoSBasicTW.java:794-815). */
 int vmn_msg_from_bytetree(vmn_group* grp, const uint8_t* bt, size_t len, const int* layout, const size_t* counts,
                           size_t items, vmn_msg** out, int* format_ok);
+/* Under a public key of width keywidth (ProtocolElGamal.java:476-481) the plaintext group is G^keywidth: F' and B' of a
+ * ciphertext-shaped item are elements of ((G^keywidth)^omega)^2 and k_F, k_B elements of (Z_q^keywidth)^omega, their scalars in
+ * flat order, scalar l * keywidth + j the key j of plaintext component l.  Wire form [NOT-IN-REF: the rule of SURVEY.md App. D
+ * applied once more]: where the forms above have k leaves (k/2 per half), [omega > 1: node(omega; ...)] over
+ * [keywidth > 1: node(keywidth; ...)] over the leaves -- at omega = 1 the bytes of the unkeyed form of width keywidth, at
+ * keywidth = 1 the forms above.  Items of one scalar and array items do not change.  set_keywidth: how vmn_msg_bytetree_size /
+ * vmn_msg_to_bytetree write this message from now on (VMN_ERR_ARG when an item of k > 1 scalars is no multiple of the key
+ * width, 2 * keywidth for elements); the drivers' own messages have key width 1 until it is set.  from_bytetree_keyed reads
+ * the nested form, counts[i] being the scalars in all; the message it returns carries the key width. */
+int vmn_msg_set_keywidth(vmn_msg* m, size_t keywidth);
+size_t vmn_msg_keywidth(const vmn_msg* m);
+int vmn_msg_from_bytetree_keyed(vmn_group* grp, const uint8_t* bt, size_t len, const int* layout, const size_t* counts,
+                                size_t items, size_t keywidth, vmn_msg** out, int* format_ok);
 
 /* ---- one proof over several GPUs (BASELINE.json configs[3], [4]) ---------------------------------------
  * One process per GPU.  Every rank creates the same proof object, sets the same communicator (its own rank), and makes

@@ -94,6 +94,23 @@ final class GPUArrays {
         return listOrException(group, out, formatOk[0], bad[0], inRange[0], firstBadLine);
     }
 
+    /** readCiphertextsNative under a public key of width {@code keyWidth} (ProtocolElGamal.java:476-481): the plaintext group is
+     *  G^keyWidth, every half of a line is nested once more, and the list comes as its 2 * keyWidth * width component arrays in
+     *  flat order, the u half first, component l * keyWidth + j the key j of plaintext component l.  keyWidth 1 is
+     *  readCiphertextsNative. */
+    static PGroupElementArrayGPU[] readCiphertextsNativeKeyed(final GPUGroup group, final ByteBuffer text, final long len,
+                                                              final int keyWidth, final int width, final long expectedSize,
+                                                              final long[] firstBadLine) {
+        final long[] out = new long[2 * keyWidth * width];
+        final long[] lines = new long[1];
+        final long[] bad = new long[1];
+        final int[] formatOk = new int[1];
+        final int[] inRange = new int[1];
+        VMNException.check(VMNHip.vmn_garrays_from_hexlines_keyedDirect(group.grp, keyWidth, width, text, len, expectedSize, out, lines,
+                                                                        formatOk, bad, inRange));
+        return listOrException(group, out, formatOk[0], bad[0], inRange[0], firstBadLine);
+    }
+
     /** The policy of both line interfaces on what a reader returned: a format defect, a value out of range or an element
      *  outside the group is no list. */
     private static PGroupElementArrayGPU[] listOrException(final GPUGroup group, final long[] out, final int formatOk, final long bad,
@@ -163,6 +180,18 @@ final class GPUArrays {
         final long size = VMNHip.vmn_garrays_hexlines_size(h, width);
         final ByteBuffer buf = ByteBuffer.allocateDirect((int) Math.max(1L, size));
         VMNException.check(VMNHip.vmn_garrays_to_hexlinesDirect(h, width, buf));
+        buf.limit((int) size);
+        return buf;
+    }
+
+    /** writeCiphertextsNative for the 2 * keyWidth * width component arrays of a list under a public key of width
+     *  {@code keyWidth}, in the order readCiphertextsNativeKeyed returns them. */
+    static ByteBuffer writeCiphertextsNativeKeyed(final PGroupElementArrayGPU[] comps, final int keyWidth) {
+        final long[] h = handles(comps);
+        final int width = comps.length / (2 * keyWidth);
+        final long size = VMNHip.vmn_garrays_hexlines_size_keyed(h, keyWidth, width);
+        final ByteBuffer buf = ByteBuffer.allocateDirect((int) Math.max(1L, size));
+        VMNException.check(VMNHip.vmn_garrays_to_hexlines_keyedDirect(h, keyWidth, width, buf));
         buf.limit((int) size);
         return buf;
     }

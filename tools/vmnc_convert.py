@@ -2,7 +2,7 @@
 """vmnc_convert.py — the reference's `vmnc -ciphs -ini FMT -outi FMT in out`: a ciphertext list from one interface to another,
 and `vmnc -plain -outi FMT in out`: the plaintexts the mix-net left behind in the form of an interface.
 
-  python tools/vmnc_convert.py -ciphs -ini native -outi raw [-width W] (--bits B | --curve NAME) [--wire java|natural] IN OUT
+  python tools/vmnc_convert.py -ciphs -ini native -outi raw [-width W] [-keywidth K] (--bits B | --curve NAME) [--wire java|natural] IN OUT
   python tools/vmnc_convert.py -plain -outi json [-width W] --bits B [--wire java|natural] IN OUT
 
 FMT: native (one ciphertext per line, the line the hexadecimal byte tree of that ciphertext; the reference's default), raw
@@ -12,6 +12,9 @@ json is a usage error).  -plain reads the raw array tree of the W plaintext comp
 ["M1",...,"MW"]) or raw again; it takes no -ini.  The group is the RFC 3526 safe-prime
 group of B bits or the named curve, at the reference's leaf widths (--wire java, the default) or at the bytes of the modulus.
 The list is parsed, range- and membership-checked and written on the GPU (verificatum_vmn_amd.interface).
+-keywidth K: the list lies under a public key of width K (the protocol info's keywidth): 2 K W component arrays, every half of a
+line or of the raw tree nested once more; native and raw only -- the reference's json classes cannot hold such a list, so
+-keywidth above 1 with json is a usage error.  -plain -outi raw takes it as well.
 
 Exit status: 0 the list was converted; 1 IN is no list of the input interface (a malformed native or json line is named,
 counted from 1, on stderr), no output is written; 2 usage; 3 no GPU (there is no host conversion to fall back to)."""
@@ -38,6 +41,7 @@ def main(argv=None):
     ap.add_argument("-ini", choices=("native", "raw", "json"))
     ap.add_argument("-outi", choices=("native", "raw", "json"), required=True)
     ap.add_argument("-width", type=int, default=1)
+    ap.add_argument("-keywidth", type=int, default=1)
     grp_arg = ap.add_mutually_exclusive_group(required=True)
     grp_arg.add_argument("--bits", type=int)
     grp_arg.add_argument("--curve")
@@ -48,6 +52,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.width < 1:
         ap.error("-width must be at least 1")
+    if args.keywidth < 1:
+        ap.error("-keywidth must be at least 1")
+    if args.keywidth > 1 and "json" in (args.ini, args.outi):
+        ap.error("the json interface cannot hold a list under a key of width above 1")
     if args.ciphs and args.ini is None:
         ap.error("-ciphs needs -ini")
     if args.plain and args.ini is not None:
@@ -80,14 +88,14 @@ def main(argv=None):
         except (KeyError, ValueError, vmn.VmnError) as e:
             ap.error("unknown curve %r (%s)" % (args.curve, e))
     if args.plain:
-        comps = interface.read_plaintexts(grp, args.input, args.width)
+        comps = interface.read_plaintexts(grp, args.input, args.width, args.keywidth)
         if comps is None:
             sys.stderr.write("%s: not a raw list of plaintexts of width %d over this group\n" % (args.input, args.width))
             return 1
-        interface.write_plaintexts(args.output, comps, args.outi)
+        interface.write_plaintexts(args.output, comps, args.outi, args.keywidth)
         return 0
     report = {}
-    ok = interface.convert_list(grp, args.input, args.output, args.width, args.ini, args.outi, report=report)
+    ok = interface.convert_list(grp, args.input, args.output, args.width, args.ini, args.outi, report=report, keywidth=args.keywidth)
     if ok:
         return 0
     if args.ini == "json" and report and not report["format_ok"]:
@@ -95,7 +103,7 @@ def main(argv=None):
                          % (args.input, report["first_bad_line"] + 1, args.width))
     elif args.ini == "native" and report and not report["format_ok"]:
         sys.stderr.write("%s: line %d is not a ciphertext of width %d over this group (%d hex digits of its byte tree)\n"
-                         % (args.input, report["first_bad_line"] + 1, args.width, 2 * interface.ciphertext_line_bytes(grp, args.width)))
+                         % (args.input, report["first_bad_line"] + 1, args.width, 2 * interface.ciphertext_line_bytes(grp, args.width, args.keywidth)))
     else:
         sys.stderr.write("%s: not a list of ciphertexts of width %d over this group in the %s interface "
                          "(format, a value out of range, or an element outside the group)\n" % (args.input, args.width, args.ini))

@@ -12,13 +12,15 @@ MixNetElGamalVerifyFiatShamir.java:382-388).
     python tools/vmnv_vectors.py <nizkp dir> -session [-mix | -shuffle | -decrypt] [-auxsid SID] [-width W] [-nopos | -noposc | -noccpos]
                                  [-nodec] [-t par,der,bas,PoS] [--arrays]        the WHOLE directory, as `vmnv` verifies it
     python tools/vmnv_vectors.py --demo <new dir> -session [-mix | -shuffle | -decrypt] [--parties 3] [--threshold 2] [--active 2]
-                                 [--width 1] [--precomputed N_0] [--curve NAME]
+                                 [--width 1] [--keywidth 1] [--precomputed N_0] [--curve NAME]
 
 -session is MixNetElGamalVerifyFiatShamirSession.verify (:1318-1670) through proofdir.verify_session; the options have the meaning of
 MixNetElGamalVerifyFiatShamirTool.java:562-640, 1015-1044 (expected auxsid "default", expected width 0 = the width of params.json,
 unless given; without -mix / -shuffle / -decrypt the type is taken from the proof).  It prints the TEST VECTOR blocks in the order
 of the session, the per-party ones between the reference's BEGIN PARTY / END PARTY banners, one line per party and the result;
-exit status 0: accepted, 1: rejected, 2: the directory is not a session that can be verified (SessionFormatError).
+exit status 0: accepted, 1: rejected, 2: the directory is not a session that can be verified (SessionFormatError).  The width
+of the public key (the protocol info's keywidth) is params.json's "keywidth", 1 when it has none; --demo --keywidth K writes a
+session under a key of width K, whose lists have 2 K W component arrays.
 
 The directory layout is the reference's (verificatum-vmn_amd/proofdir.py); what `vmnv` reads from the protocol-info XML is
 in <dir>/params.json.  THE diff that would pin parity: on a machine with a JDK + VCR, run `vmnv -t der.rho,PoS ...` on a proof
@@ -132,21 +134,25 @@ def block(name, value, printed_as=None):
 def demo_session(args, vmn, ctx, proofdir, randomsource, stdgroups):
     """A synthetic list of -n ciphertexts of width --width, mixed / shuffled / decrypted by --parties parties (threshold
     --threshold, --active of them shuffling) through proofdir.write_session."""
-    k, thr, width = args.parties, args.threshold, args.width
+    k, thr, width, kw = args.parties, args.threshold, args.width, args.keywidth
     params = demo_params(args, stdgroups)
     grp = group_of(vmn, ctx, params)
     q, g = grp.q, grp.g
     rnd = randomsource.InsecureShaRandomSource(b"vmnv-demo-session", q)
-    coeffs = rnd.ring_array(thr)
-    shares = [None] + [sum(c * pow(l, d, q) for d, c in enumerate(coeffs)) % q for l in range(1, k + 1)]
-    poly = [grp.k_exp(g, c) for c in coeffs]
-    T = [grp.ringArray(rnd.ring_array(args.n)) for _ in range(width)]
-    M = [grp.exp(g, grp.ringArray(rnd.ring_array(args.n))) for _ in range(width)]
-    W = [grp.exp(g, t) for t in T] + [m.mul(grp.exp(poly[0], t)) for m, t in zip(M, T)]
+    coeffs = [rnd.ring_array(thr) for _ in range(kw)]                       # one polynomial per row of the key
+    share = lambda j, l: sum(c * pow(l, d, q) for d, c in enumerate(coeffs[j])) % q
+    rows = lambda f: f(0) if kw == 1 else tuple(f(j) for j in range(kw))    # an element of G^kw / Z_q^kw: its rows, the row itself at 1
+    shares = [None] + [rows(lambda j: share(j, l)) for l in range(1, k + 1)]
+    poly = [rows(lambda j: grp.k_exp(g, coeffs[j][d])) for d in range(thr)]
+    y = [grp.k_exp(g, coeffs[j][0]) for j in range(kw)]
+    T = [grp.ringArray(rnd.ring_array(args.n)) for _ in range(kw * width)]
+    M = [grp.exp(g, grp.ringArray(rnd.ring_array(args.n))) for _ in range(kw * width)]
+    W = [grp.exp(g, t) for t in T] + [m.mul(grp.exp(y[c % kw], t)) for c, (m, t) in enumerate(zip(M, T))]
     typ = proofdir.SHUFFLE_TYPE if args.shuffle else proofdir.DECRYPT_TYPE if args.decrypt else proofdir.MIX_TYPE
     proofdir.write_session(args.nizkp, grp, params, typ, W, poly[0], randomsource.SecureRandomSource(q), k, thr,
-                           active=args.active or thr, n0=args.precomputed, poly=poly, shares=shares)
-    print(f"wrote {args.nizkp}: a {typ} session, {args.n} ciphertexts of width {width}, {k} parties, threshold {thr}", file=sys.stderr)
+                           active=args.active or thr, n0=args.precomputed, poly=poly, shares=shares, keywidth=kw)
+    print(f"wrote {args.nizkp}: a {typ} session, {args.n} ciphertexts of width {width}, key width {kw}, {k} parties, threshold {thr}",
+          file=sys.stderr)
 
 
 def session_main(args, vmn, ctx, proofdir):
@@ -217,6 +223,7 @@ def main():
                     help="verify the threshold decryption of a list instead of a shuffle; with --demo: write one")
     ap.add_argument("--list", default=None, help="-decrypt: the decrypted list (default: Ciphertexts.bt of the directory)")
     ap.add_argument("--width", type=int, default=1, help="--demo -decrypt: width of the ciphertexts")
+    ap.add_argument("--keywidth", type=int, default=1, help="--demo -session: width of the public key (written to params.json)")
     ap.add_argument("--parties", type=int, default=3, help="--demo -decrypt: number of parties k")
     ap.add_argument("--threshold", type=int, default=2, help="--demo -decrypt: parties needed to decrypt")
     ap.add_argument("-session", "--session", dest="session", action="store_true",

@@ -2082,8 +2082,10 @@ extern "C" int vmn_rarray_from_bytetree(vmn_group* grp, const uint8_t* bt, size_
 }
 // ---- the `native` ciphertext interface: one ciphertext per line, the line the hex digits of its byte tree -------------------
 // (csrc/hexlines_layout.h for the bytes of a line, csrc/light_kernels.h for the kernels)
-static bool hexlines_width_ok(const vmn_group* grp, size_t width) {
-    return width >= 1 && width <= 65536 && hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, width) < ((size_t)1 << 30);
+// (under a key of width keywidth the bounds are the unkeyed ones on the keywidth * width components of a half)
+static bool hexlines_width_ok(const vmn_group* grp, size_t keywidth, size_t width) {
+    return keywidth >= 1 && keywidth <= 65536 && width >= 1 && width <= 65536 && keywidth * width <= 65536 &&
+           hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, keywidth, width) < ((size_t)1 << 30);
 }
 // template and mask of a line on the device: the mask behind the template, each padded to a multiple of eight bytes
 static int hexlines_upload_layout(vmn_ctx* ctx, const hexlines::Layout& L, DevTmp& dev, const uint8_t** d_tmpl, const uint8_t** d_mask) {
@@ -2150,13 +2152,15 @@ struct TextLines {
     int read_first_bad(vmn_ctx* ctx, uint32_t* bad) { return d2h(ctx, bad, first_bad(), sizeof(*bad)); }
 };
 
-extern "C" size_t vmn_hexlines_line_bytes(const vmn_group* grp, size_t width) {
-    return grp && hexlines_width_ok(grp, width) ? hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, width) : 0;
+extern "C" size_t vmn_hexlines_line_bytes_keyed(const vmn_group* grp, size_t keywidth, size_t width) {
+    return grp && hexlines_width_ok(grp, keywidth, width) ? hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, keywidth, width) : 0;
 }
-extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const char* text, size_t len, size_t expected_n, vmn_garray** out,
-                                         size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range) {
+extern "C" size_t vmn_hexlines_line_bytes(const vmn_group* grp, size_t width) { return vmn_hexlines_line_bytes_keyed(grp, 1, width); }
+extern "C" int vmn_garrays_from_hexlines_keyed(vmn_group* grp, size_t keywidth, size_t omega, const char* text, size_t len, size_t expected_n,
+                                               vmn_garray** out, size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range) {
     ARG_CHECK(grp && out && n_out && format_ok && first_bad_line && (text || len == 0), "null argument");
-    ARG_CHECK(hexlines_width_ok(grp, width), "width out of range");
+    ARG_CHECK(hexlines_width_ok(grp, keywidth, omega), "width out of range");
+    const size_t width = keywidth * omega;                     // components of a half: the nesting is in the layout alone
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
     for (size_t c = 0; c < 2 * width; ++c) out[c] = nullptr;
@@ -2164,7 +2168,7 @@ extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const cha
     *format_ok = 0;
     *first_bad_line = 0;
     if (all_in_range) *all_in_range = 1;
-    const hexlines::Layout L = hexlines::make_layout(grp->curve != nullptr, grp->nbytes, width);
+    const hexlines::Layout L = hexlines::make_layout(grp->curve != nullptr, grp->nbytes, keywidth, omega);
     const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
 
     // where the lines are: terminators per chunk, their scan, then the starts and ends
@@ -2220,21 +2224,27 @@ extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const cha
     if (all_in_range) *all_in_range = (fl & 1u) ? 0 : 1;
     return VMN_OK;
 }
+extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const char* text, size_t len, size_t expected_n, vmn_garray** out,
+                                         size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range) {
+    return vmn_garrays_from_hexlines_keyed(grp, 1, width, text, len, expected_n, out, n_out, format_ok, first_bad_line, all_in_range);
+}
 
-// the arrays of a ciphertext list: 2 * width of them, of one group and one size
-static bool hexlines_comps_ok(const vmn_garray* const* comps, size_t width) {
-    if (!comps || !comps[0] || !hexlines_width_ok(comps[0]->grp, width)) return false;
-    for (size_t c = 0; c < 2 * width; ++c)
+// the arrays of a ciphertext list: 2 * keywidth * width of them, of one group and one size
+static bool hexlines_comps_ok(const vmn_garray* const* comps, size_t keywidth, size_t width) {
+    if (!comps || !comps[0] || !hexlines_width_ok(comps[0]->grp, keywidth, width)) return false;
+    for (size_t c = 0; c < 2 * keywidth * width; ++c)
         if (!comps[c] || comps[c]->grp != comps[0]->grp || comps[c]->n != comps[0]->n) return false;
     return true;
 }
-extern "C" size_t vmn_garrays_hexlines_size(const vmn_garray* const* comps, size_t width) {
-    if (!hexlines_comps_ok(comps, width)) return 0;
-    return comps[0]->n * (2 * vmn_hexlines_line_bytes(comps[0]->grp, width) + 1);
+extern "C" size_t vmn_garrays_hexlines_size_keyed(const vmn_garray* const* comps, size_t keywidth, size_t width) {
+    if (!hexlines_comps_ok(comps, keywidth, width)) return 0;
+    return comps[0]->n * (2 * vmn_hexlines_line_bytes_keyed(comps[0]->grp, keywidth, width) + 1);
 }
-extern "C" int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t width, char* out) {
-    ARG_CHECK(comps && width >= 1 && comps[0], "null argument");
-    ARG_CHECK(hexlines_comps_ok(comps, width), "2 * width arrays of one group and one size are needed");
+extern "C" size_t vmn_garrays_hexlines_size(const vmn_garray* const* comps, size_t width) { return vmn_garrays_hexlines_size_keyed(comps, 1, width); }
+extern "C" int vmn_garrays_to_hexlines_keyed(const vmn_garray* const* comps, size_t keywidth, size_t omega, char* out) {
+    ARG_CHECK(comps && keywidth >= 1 && omega >= 1 && comps[0], "null argument");
+    ARG_CHECK(hexlines_comps_ok(comps, keywidth, omega), "2 * keywidth * width arrays of one group and one size are needed");
+    const size_t width = keywidth * omega;
     vmn_group* grp = comps[0]->grp;
     const size_t n = comps[0]->n;
     ARG_CHECK(out || n == 0, "null argument");
@@ -2242,7 +2252,7 @@ extern "C" int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t wi
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
     if (n == 0) return VMN_OK;
-    const hexlines::Layout L = hexlines::make_layout(grp->curve != nullptr, grp->nbytes, width);
+    const hexlines::Layout L = hexlines::make_layout(grp->curve != nullptr, grp->nbytes, keywidth, omega);
     DevTmp rec(ctx), layout(ctx), dtext(ctx);
     const uint8_t *d_tmpl = nullptr, *d_mask = nullptr;
     VMN_TRY(hexlines_upload_layout(ctx, L, layout, &d_tmpl, &d_mask));
@@ -2254,6 +2264,10 @@ extern "C" int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t wi
     VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_encode, hexlines_grid(n), dtext.as<uint8_t>(), (const uint8_t*)rec.as<uint8_t>(), (uint32_t)n,
                          (uint32_t)L.B, d_tmpl, d_mask));
     return d2h(ctx, out, dtext.p, text_bytes);
+}
+extern "C" int vmn_garrays_to_hexlines(const vmn_garray* const* comps, size_t width, char* out) {
+    ARG_CHECK(comps && width >= 1 && comps[0], "null argument");
+    return vmn_garrays_to_hexlines_keyed(comps, 1, width, out);
 }
 
 // ---- the `json` ciphertext interface: one ciphertext per line, every number a decimal string; modular groups only ----------------

@@ -355,6 +355,7 @@ struct vmn_msg {
     };
     std::vector<Item> items;
     bool ec = false;                   // group elements are curve points: an element is node(leaf(x), leaf(y)) on the wire
+    size_t kw = 1;                     // key width: k > 1 scalars of an item are elements of ((.)^kw)^omega (vmn_msg_set_keywidth)
     uint64_t serial = next_serial();   // distinguishes a message from an earlier one that lived at the same address
     static uint64_t next_serial() {
         static std::atomic<uint64_t> counter{1};
@@ -2679,13 +2680,21 @@ static void put_header(uint8_t*& o, uint8_t tag, size_t n) {
     *o++ = (uint8_t)(n >> 8);
     *o++ = (uint8_t)n;
 }
-static size_t scalar_item_size(const vmn_msg::Item& it, bool ec) {
+// W scalars as an element of ((.)^kw)^omega, W = kw * omega: [omega > 1: node(omega; ...)] over [kw > 1: node(kw; ...)] over leaves
+static size_t nested_size(size_t W, size_t kw, size_t leaf) {
+    const size_t omega = W / kw;
+    return (omega != 1 ? 5 : 0) + omega * ((kw > 1 ? 5 : 0) + kw * leaf);
+}
+static bool keywidth_fits(const vmn_msg::Item& it, size_t kw) {
+    if (it.kind != VMN_ITEM_ELEMENTS && it.kind != VMN_ITEM_RING) return true;
+    return it.count <= 1 || it.count % ((it.kind == VMN_ITEM_ELEMENTS ? 2 : 1) * kw) == 0;
+}
+static size_t scalar_item_size(const vmn_msg::Item& it, bool ec, size_t kw) {
     // one element: a leaf, or -- a curve point -- node(leaf(x), leaf(y))
     const size_t leaf = (ec && it.kind == VMN_ITEM_ELEMENTS) ? 15 + it.width : 5 + it.width;
     if (it.count == 1) return leaf;
-    if (it.kind == VMN_ITEM_RING) return 5 + it.count * leaf;
-    if (it.count == 2) return 5 + 2 * leaf;
-    return 5 + 2 * (5 + (it.count / 2) * leaf);
+    if (it.kind == VMN_ITEM_RING) return nested_size(it.count, kw, leaf);
+    return 5 + 2 * nested_size(it.count / 2, kw, leaf);
 }
 size_t vmn_msg_bytetree_size(const vmn_msg* m) {
     if (!m) return 0;
@@ -2693,7 +2702,7 @@ size_t vmn_msg_bytetree_size(const vmn_msg* m) {
     for (auto& it : m->items) {
         if (it.kind == VMN_ITEM_GARRAY) total += vmn_garray_bytetree_size(it.ga);
         else if (it.kind == VMN_ITEM_RARRAY) total += vmn_rarray_bytetree_size(it.ra);
-        else total += scalar_item_size(it, m->ec);
+        else total += scalar_item_size(it, m->ec, m->kw);
     }
     return total;
 }
@@ -2728,21 +2737,33 @@ int vmn_msg_to_bytetree(const vmn_msg* m, uint8_t* out) {
             memcpy(o, src, it.width);
             o += it.width;
         };
+        auto nested = [&](size_t base, size_t W) {                  // scalars base .. base + W - 1, an element of ((.)^kw)^omega
+            const size_t omega = W / m->kw;
+            if (omega != 1) put_header(o, 0, omega);
+            for (size_t l = 0; l < omega; ++l) {
+                if (m->kw > 1) put_header(o, 0, m->kw);
+                for (size_t j = 0; j < m->kw; ++j) leaf(base + l * m->kw + j);
+            }
+        };
         if (it.count == 1) {
             leaf(0);
-        } else if (it.kind == VMN_ITEM_RING || it.count == 2) {
-            put_header(o, 0, it.count);
-            for (size_t k = 0; k < it.count; ++k) leaf(k);
+        } else if (it.kind == VMN_ITEM_RING) {
+            nested(0, it.count);
         } else {
             put_header(o, 0, 2);
-            for (size_t half = 0; half < 2; ++half) {
-                put_header(o, 0, it.count / 2);
-                for (size_t k = 0; k < it.count / 2; ++k) leaf(half * (it.count / 2) + k);
-            }
+            for (size_t half = 0; half < 2; ++half) nested(half * (it.count / 2), it.count / 2);
         }
     }
     return VMN_OK;
 }
+int vmn_msg_set_keywidth(vmn_msg* m, size_t keywidth) {
+    if (!m || keywidth < 1) return fail(VMN_ERR_ARG, "vmn_msg_set_keywidth: null argument or key width 0");
+    for (auto& it : m->items)
+        if (!keywidth_fits(it, keywidth)) return fail(VMN_ERR_ARG, "vmn_msg_set_keywidth: an item of %zu scalars does not fit key width %zu", it.count, keywidth);
+    m->kw = keywidth;
+    return VMN_OK;
+}
+size_t vmn_msg_keywidth(const vmn_msg* m) { return m ? m->kw : 0; }
 
 namespace {
 struct Reader {
@@ -2770,9 +2791,10 @@ struct Reader {
 };
 }  // namespace
 
-int vmn_msg_from_bytetree(vmn_group* grp, const uint8_t* bt, size_t len, const int* layout, const size_t* counts, size_t items,
-                          vmn_msg** out, int* format_ok) {
-    if (!grp || !bt || !layout || !counts || !out || !format_ok) return fail(VMN_ERR_ARG, "vmn_msg_from_bytetree: null argument");
+int vmn_msg_from_bytetree_keyed(vmn_group* grp, const uint8_t* bt, size_t len, const int* layout, const size_t* counts, size_t items,
+                                size_t keywidth, vmn_msg** out, int* format_ok) {
+    if (!grp || !bt || !layout || !counts || !out || !format_ok || keywidth < 1)
+        return fail(VMN_ERR_ARG, "vmn_msg_from_bytetree: null argument or key width 0");
     *format_ok = 0;
     *out = nullptr;
     const size_t eb = vmn_group_elem_bytes(grp), xb = vmn_group_exp_bytes(grp);
@@ -2781,6 +2803,7 @@ int vmn_msg_from_bytetree(vmn_group* grp, const uint8_t* bt, size_t len, const i
     if (!rd.header(0, &n) || n != items) return VMN_OK;
     const bool ec = vmn_group_kind(grp) == 1;
     std::unique_ptr<vmn_msg> m(new vmn_msg(ec));
+    m->kw = keywidth;
     for (size_t i = 0; i < items; ++i) {
         if (layout[i] == VMN_ITEM_GARRAY || layout[i] == VMN_ITEM_RARRAY) {
             const size_t width = layout[i] == VMN_ITEM_GARRAY ? eb : xb;
@@ -2811,17 +2834,23 @@ int vmn_msg_from_bytetree(vmn_group* grp, const uint8_t* bt, size_t len, const i
         it.width = layout[i] == VMN_ITEM_ELEMENTS ? eb : xb;
         bool good = true;
         const bool point = ec && it.kind == VMN_ITEM_ELEMENTS;
+        if (!keywidth_fits(it, keywidth)) return fail(VMN_ERR_ARG, "vmn_msg_from_bytetree: item %zu does not fit key width %zu", i, keywidth);
+        auto nested = [&](size_t W) {                              // an element of ((.)^keywidth)^omega, W = keywidth * omega
+            const size_t omega = W / keywidth;
+            bool fine = omega == 1 || (rd.header(0, &n) && n == omega);
+            for (size_t l = 0; fine && l < omega; ++l) {
+                fine = keywidth == 1 || (rd.header(0, &n) && n == keywidth);
+                for (size_t j = 0; fine && j < keywidth; ++j) fine = rd.element(it.width, point, it.bytes);
+            }
+            return fine;
+        };
         if (it.count == 1) {
             good = rd.element(it.width, point, it.bytes);
-        } else if (it.kind == VMN_ITEM_RING || it.count == 2) {
-            good = rd.header(0, &n) && n == it.count;
-            for (size_t k = 0; good && k < it.count; ++k) good = rd.element(it.width, point, it.bytes);
+        } else if (it.kind == VMN_ITEM_RING) {
+            good = nested(it.count);
         } else {
             good = rd.header(0, &n) && n == 2;
-            for (size_t half = 0; good && half < 2; ++half) {
-                good = rd.header(0, &n) && n == it.count / 2;
-                for (size_t k = 0; good && k < it.count / 2; ++k) good = rd.element(it.width, point, it.bytes);
-            }
+            for (size_t half = 0; good && half < 2; ++half) good = nested(it.count / 2);
         }
         if (!good) return VMN_OK;
         if (it.kind == VMN_ITEM_RING) {                // pRing.toElement rejects a value >= q (PoSBasicTW.java:985-989)
@@ -2836,6 +2865,10 @@ int vmn_msg_from_bytetree(vmn_group* grp, const uint8_t* bt, size_t len, const i
     *format_ok = 1;
     *out = m.release();
     return VMN_OK;
+}
+int vmn_msg_from_bytetree(vmn_group* grp, const uint8_t* bt, size_t len, const int* layout, const size_t* counts, size_t items,
+                          vmn_msg** out, int* format_ok) {
+    return vmn_msg_from_bytetree_keyed(grp, bt, len, layout, counts, items, 1, out, format_ok);
 }
 
 // ---- shuffler lines --------------------------------------------------------------------------------------------

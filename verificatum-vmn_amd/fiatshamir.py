@@ -95,26 +95,40 @@ def array_tree_size(n: int, elem_bytes: int, cw: Optional[int] = None) -> int:
     return 5 + n * (5 + elem_bytes if cw is None else 15 + 2 * cw)
 
 
-def product_element_tree(group, els: Sequence) -> bytes:
+def nested_tree(trees: Sequence[bytes], keywidth: int = 1) -> bytes:
+    """The tree of an element (an array, a ring element) of (X^kappa)^omega given as the trees of its kappa * omega factors in
+    flat order, factor l * kappa + j the key j of plaintext component l: [omega > 1: node(omega; ...)] over [kappa > 1:
+    node(kappa; ...)] over the factors' own trees (a product is the node of its factors' trees; the plaintext
+    group under a key of width kappa is G^kappa, MixNetElGamalVerifyFiatShamir.java:316-317).  kappa = 1: node(omega trees), the
+    tree itself at omega = 1; omega = 1: node(kappa trees), the bytes of the unkeyed form of width kappa."""
+    if keywidth < 1 or len(trees) % keywidth:
+        raise ValueError("%d factors are no multiple of the key width %d" % (len(trees), keywidth))
+    omega = len(trees) // keywidth
+    inner = [b"".join(trees[l * keywidth:(l + 1) * keywidth]) for l in range(omega)]
+    if keywidth > 1:
+        inner = [_hdr(0, keywidth) + t for t in inner]
+    return inner[0] if omega == 1 else _hdr(0, omega) + b"".join(inner)
+
+
+def product_element_tree(group, els: Sequence, keywidth: int = 1) -> bytes:
     """``element_tree`` for any kind of group: the same shapes (one element alone: its own tree; node(a, b) at width 1;
     node(node(w trees), node(w trees)) otherwise) over the trees of the single elements, which are leaves for a modular group
     and point nodes for a curve (``group.coord_bytes``: the coordinate width, None / absent for a modular group).  Over a
-    modular group the bytes are those of ``element_tree``."""
+    modular group the bytes are those of ``element_tree``.  ``keywidth`` = kappa > 1: each half is ``nested_tree`` of its
+    kappa * omega element trees."""
     cw = getattr(group, "coord_bytes", None)
     enc = [group_element_tree(group.enc_el(e), cw) for e in els]
     if len(enc) == 1:
         return enc[0]
-    if len(enc) == 2:
-        return _hdr(0, 2) + enc[0] + enc[1]
     half = len(enc) // 2
-    return _hdr(0, 2) + _hdr(0, half) + b"".join(enc[:half]) + _hdr(0, half) + b"".join(enc[half:])
+    return _hdr(0, 2) + nested_tree(enc[:half], keywidth) + nested_tree(enc[half:], keywidth)
 
 
-def wide_element_tree(group, els: Sequence) -> bytes:
-    """An element of G^omega given as its omega components: node(omega element trees), the element's own tree at omega = 1."""
+def wide_element_tree(group, els: Sequence, keywidth: int = 1) -> bytes:
+    """An element of G^omega given as its omega components: node(omega element trees), the element's own tree at omega = 1;
+    with ``keywidth`` = kappa an element of (G^kappa)^omega given as its kappa * omega components (``nested_tree``)."""
     cw = getattr(group, "coord_bytes", None)
-    enc = [group_element_tree(group.enc_el(e), cw) for e in els]
-    return enc[0] if len(enc) == 1 else _hdr(0, len(enc)) + b"".join(enc)
+    return nested_tree([group_element_tree(group.enc_el(e), cw) for e in els], keywidth)
 
 
 class InstanceHasher(threading.Thread):

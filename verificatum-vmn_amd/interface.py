@@ -17,6 +17,11 @@ The json text is converted from and to decimal on the GPU as well (``vmn_garrays
 ``_to_jsonplain``, csrc/decimal_kernels.h); ``read_list`` / ``write_list`` / ``convert_list`` take all three interfaces.  All readers
 apply one policy to what enters here from outside: a format defect, a value out of range or an element outside the group is no
 list (``None``).
+
+Under a public key of width kappa (``keywidth``, 1 by default) a ciphertext of ``width`` omega has 2 kappa omega components and
+every half of a list or of a line one more node level (``proofdir``'s head, ``vmn_garrays_from_hexlines_keyed``); ``native`` and
+``raw`` take it, ``json`` does not: the reference's JSON classes cast the components to elements of a modular group, so they
+cannot hold such a list, and ``keywidth`` > 1 with ``json`` is a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -32,9 +37,14 @@ INTERFACES = FORMATS + ("json",)             # what read_list / write_list / con
 PLAINTEXT_FORMATS = ("json", "raw")
 
 
-def ciphertext_line_bytes(grp, width: int) -> int:
+def ciphertext_line_bytes(grp, width: int, keywidth: int = 1) -> int:
     """B: the bytes of one ciphertext of ``width`` over ``grp`` as a byte tree; a native line has 2B hex digits."""
-    return lib().vmn_hexlines_line_bytes(grp._h, C.c_size_t(width))
+    return lib().vmn_hexlines_line_bytes_keyed(grp._h, C.c_size_t(keywidth), C.c_size_t(width))
+
+
+def _no_keyed_json(fmt: str, keywidth: int) -> None:
+    if fmt == "json" and keywidth != 1:
+        raise ValueError("the json interface cannot hold a list under a key of width %d" % keywidth)
 
 
 def _free(comps) -> None:
@@ -49,17 +59,19 @@ def _members_or_none(comps):
     return comps
 
 
-def parse_native(grp, text, width: int, expected_n: int = 0, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+def parse_native(grp, text, width: int, expected_n: int = 0, report: Optional[dict] = None,
+                 keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
     """The 2w component arrays ``u_1..u_w, v_1..v_w`` of a native list held in memory (``bytes``, or a host buffer object as
     ``host_block`` takes them); ``None`` when a line is malformed, a value is out of range or an element is no member of the
     group -- the raw reader's policy.  ``report`` (a dict) receives ``format_ok``, ``first_bad_line`` (zero-based; only
-    meaningful when ``format_ok`` is false), ``all_in_range`` and ``lines``."""
+    meaningful when ``format_ok`` is false), ``all_in_range`` and ``lines``.  Under a key of width ``keywidth`` = kappa the
+    2 kappa w arrays in flat order, component l kappa + j the key j of plaintext component l."""
     blk = host_block(text) or host_block(bytes(text))
-    hs = (C.c_void_p * (2 * width))()
+    hs = (C.c_void_p * (2 * keywidth * width))()
     n, bad = C.c_size_t(0), C.c_size_t(0)
     fmt, rng = C.c_int(0), C.c_int(1)
-    _check(lib().vmn_garrays_from_hexlines(grp._h, C.c_size_t(width), blk[0], C.c_size_t(blk[1]), C.c_size_t(expected_n), hs,
-                                           C.byref(n), C.byref(fmt), C.byref(bad), C.byref(rng)))
+    _check(lib().vmn_garrays_from_hexlines_keyed(grp._h, C.c_size_t(keywidth), C.c_size_t(width), blk[0], C.c_size_t(blk[1]),
+                                                 C.c_size_t(expected_n), hs, C.byref(n), C.byref(fmt), C.byref(bad), C.byref(rng)))
     if report is not None:
         report.update(format_ok=bool(fmt.value), first_bad_line=bad.value, all_in_range=bool(rng.value), lines=n.value)
     if not fmt.value:
@@ -71,15 +83,16 @@ def parse_native(grp, text, width: int, expected_n: int = 0, report: Optional[di
     return _members_or_none(comps)
 
 
-def format_native(comps: Sequence[PGroupElementArray]) -> bytes:
-    """The native text of a list given as its 2w component arrays: lowercase digits, every line ended by a newline."""
-    width = len(comps) // 2
-    if width < 1 or len(comps) != 2 * width:
-        raise ValueError("a ciphertext list has 2 * width component arrays")
+def format_native(comps: Sequence[PGroupElementArray], keywidth: int = 1) -> bytes:
+    """The native text of a list given as its 2w component arrays (2 kappa w under a key of width ``keywidth``): lowercase
+    digits, every line ended by a newline."""
+    width = len(comps) // (2 * keywidth) if keywidth >= 1 else 0
+    if width < 1 or len(comps) != 2 * keywidth * width:
+        raise ValueError("a ciphertext list has 2 * keywidth * width component arrays")
     hs = (C.c_void_p * len(comps))(*[a._h for a in comps])
-    size = lib().vmn_garrays_hexlines_size(hs, C.c_size_t(width))
+    size = lib().vmn_garrays_hexlines_size_keyed(hs, C.c_size_t(keywidth), C.c_size_t(width))
     out = C.create_string_buffer(max(1, size))
-    _check(lib().vmn_garrays_to_hexlines(hs, C.c_size_t(width), out))
+    _check(lib().vmn_garrays_to_hexlines_keyed(hs, C.c_size_t(keywidth), C.c_size_t(width), out))
     return out.raw[:size]
 
 
@@ -135,51 +148,49 @@ def format_json_plaintexts(comps: Sequence[PGroupElementArray]) -> bytes:
 
 
 def read_ciphertexts(grp, path: str, width: int, fmt: str = "native", expected_n: int = 0,
-                     report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+                     report: Optional[dict] = None, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
     """The list file at ``path`` in the interface ``fmt``; ``None`` when it is missing or is no such list."""
     if fmt not in FORMATS:
         raise ValueError("unknown interface %r (native, raw)" % (fmt,))
     if fmt == "raw":
-        return _members_or_none(proofdir.read_ciphertexts(grp, path, width, expected_n))
+        return _members_or_none(proofdir.read_ciphertexts(grp, path, width, expected_n, keywidth))
     buf = proofdir._read_file(path)
     if buf is None:
         return None
-    return parse_native(grp, buf, width, expected_n, report)
+    return parse_native(grp, buf, width, expected_n, report, keywidth)
 
 
-def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray], fmt: str = "native") -> None:
+def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray], fmt: str = "native", keywidth: int = 1) -> None:
     if fmt not in FORMATS:
         raise ValueError("unknown interface %r (native, raw)" % (fmt,))
     if fmt == "raw":
-        proofdir.write_ciphertexts(path, comps)
+        proofdir.write_ciphertexts(path, comps, keywidth)
         return
-    text = format_native(comps)
+    text = format_native(comps, keywidth)
     with open(path, "wb") as f:
         f.write(text)
 
 
-def read_plaintexts(grp, path: str, width: int) -> Optional[List[PGroupElementArray]]:
+def read_plaintexts(grp, path: str, width: int, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
     """The w component arrays of a raw list of plaintexts (what the mix-net leaves behind: one array tree at width 1, the node of
-    w array trees above); ``None`` when the file is missing or is no such list -- format, range and membership as for a list
-    of ciphertexts."""
+    w array trees above; under a key of width kappa the kappa w arrays of ``proofdir``'s nested form); ``None`` when the file is
+    missing or is no such list -- format, range and membership as for a list of ciphertexts."""
     buf = proofdir._read_file(path)
     if buf is None:
         return None
     buf = bytes(buf)
-    if width == 1:
+    if width == 1 and keywidth == 1:
         parts = [buf]
     else:
-        if len(buf) < 5 or buf[0] != 0 or int.from_bytes(buf[1:5], "big") != width:
-            return None
-        parts, at = [], 5
-        for _ in range(width):                               # every child: a node of n leaves of the group's width
-            if len(buf) < at + 5 or buf[at] != 0:
+        def array(b, at):                                    # every array: a node of n leaves of the group's width
+            if len(b) < at + 5 or b[at] != 0:
                 return None
-            size = 5 + int.from_bytes(buf[at + 1:at + 5], "big") * (5 + grp.elem_bytes)
-            parts.append(buf[at:at + size])
-            at += size
-        if at != len(buf):
+            size = 5 + int.from_bytes(b[at + 1:at + 5], "big") * (5 + grp.elem_bytes)
+            return b[at:at + size], at + size
+        got = proofdir._nested_reader(buf, 0, width, keywidth, array)
+        if got is None or got[1] != len(buf):
             return None
+        parts = got[0]
     comps = []
     try:
         for part in parts:
@@ -193,30 +204,31 @@ def read_plaintexts(grp, path: str, width: int) -> Optional[List[PGroupElementAr
     return _members_or_none(comps)
 
 
-def write_plaintexts(path: str, comps: Sequence[PGroupElementArray], fmt: str = "json") -> None:
+def write_plaintexts(path: str, comps: Sequence[PGroupElementArray], fmt: str = "json", keywidth: int = 1) -> None:
     """decodePlaintexts: the list of plaintexts given as its w component arrays, as ``json`` lines or ``raw`` -- the array tree
-    as it is (ProtocolElGamalInterfaceRaw.java:93-96): one array at width 1, the node of the w arrays above."""
+    as it is (ProtocolElGamalInterfaceRaw.java:93-96): one array at width 1, the node of the w arrays above, nested once more
+    under a key of width ``keywidth`` (``raw`` only)."""
     if fmt not in PLAINTEXT_FORMATS:
         raise ValueError("unknown plaintext interface %r (%s)" % (fmt, ", ".join(PLAINTEXT_FORMATS)))
+    _no_keyed_json(fmt, keywidth)
     if not comps:
         raise ValueError("no arrays")
     if fmt == "json":
         data = format_json_plaintexts(comps)
-    elif len(comps) == 1:
-        data = comps[0].toByteTree()
     else:
-        data = b"\x00" + len(comps).to_bytes(4, "big") + b"".join(a.toByteTree() for a in comps)
+        data = proofdir._wide_array_tree(comps, keywidth)
     with open(path, "wb") as f:
         f.write(data)
 
 
-def convert_ciphertexts(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None) -> bool:
+def convert_ciphertexts(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None,
+                        keywidth: int = 1) -> bool:
     """``vmnc -ciphs -ini in_fmt -outi out_fmt src dst``: False (and no output file) when ``src`` is no list of ``in_fmt``."""
-    comps = read_ciphertexts(grp, src, width, in_fmt, report=report)
+    comps = read_ciphertexts(grp, src, width, in_fmt, report=report, keywidth=keywidth)
     if comps is None:
         return False
     try:
-        write_ciphertexts(dst, comps, out_fmt)
+        write_ciphertexts(dst, comps, out_fmt, keywidth)
     finally:
         _free(comps)
     return True
@@ -226,39 +238,44 @@ def convert_ciphertexts(grp, src: str, dst: str, width: int, in_fmt: str, out_fm
 # read_ciphertexts / write_ciphertexts / convert_ciphertexts keep the two interfaces they were written for: that any other name,
 # "json" among them, is a ValueError there is their contract (tests/test_gpu_hexlines.py).  These three take every interface of
 # INTERFACES under the same policy -- a format defect, a value out of range or a non-member is no list.
-def read_list(grp, path: str, width: int, fmt: str, expected_n: int = 0, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+def read_list(grp, path: str, width: int, fmt: str, expected_n: int = 0, report: Optional[dict] = None,
+              keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
     """The list file at ``path`` in the interface ``fmt`` (native, raw, json); ``None`` when it is missing or is no such list."""
     if fmt not in INTERFACES:
         raise ValueError("unknown interface %r (%s)" % (fmt, ", ".join(INTERFACES)))
+    _no_keyed_json(fmt, keywidth)
     if fmt != "json":
-        return read_ciphertexts(grp, path, width, fmt, expected_n, report)
+        return read_ciphertexts(grp, path, width, fmt, expected_n, report, keywidth)
     buf = proofdir._read_file(path)
     if buf is None:
         return None
     return parse_json(grp, buf, width, expected_n, report)
 
 
-def write_list(path: str, comps: Sequence[PGroupElementArray], fmt: str) -> None:
+def write_list(path: str, comps: Sequence[PGroupElementArray], fmt: str, keywidth: int = 1) -> None:
     if fmt not in INTERFACES:
         raise ValueError("unknown interface %r (%s)" % (fmt, ", ".join(INTERFACES)))
+    _no_keyed_json(fmt, keywidth)
     if fmt != "json":
-        write_ciphertexts(path, comps, fmt)
+        write_ciphertexts(path, comps, fmt, keywidth)
         return
     text = format_json(comps)
     with open(path, "wb") as f:
         f.write(text)
 
 
-def convert_list(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None) -> bool:
+def convert_list(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None,
+                 keywidth: int = 1) -> bool:
     """``vmnc -ciphs -ini in_fmt -outi out_fmt src dst`` over all three interfaces: False (and no output file) when ``src`` is no
     list of ``in_fmt``."""
     if out_fmt not in INTERFACES:
         raise ValueError("unknown interface %r (%s)" % (out_fmt, ", ".join(INTERFACES)))
-    comps = read_list(grp, src, width, in_fmt, report=report)
+    _no_keyed_json(out_fmt, keywidth)
+    comps = read_list(grp, src, width, in_fmt, report=report, keywidth=keywidth)
     if comps is None:
         return False
     try:
-        write_list(dst, comps, out_fmt)
+        write_list(dst, comps, out_fmt, keywidth)
     finally:
         _free(comps)
     return True

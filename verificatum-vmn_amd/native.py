@@ -79,7 +79,7 @@ def plib() -> C.CDLL:
             raise VmnError(-2, f"{LIB_PATH} is missing: run __graft_entry__.build()")
         _plib = C.CDLL(LIB_PATH)
         for name in ("vmn_msg_items", "vmn_msg_bytetree_size", "vmn_pos_width", "vmn_ccpos_width", "vmn_decproof_width",
-                     "vmn_decproof_keywidth"):
+                     "vmn_decproof_keywidth", "vmn_msg_keywidth"):
             getattr(_plib, name).restype = C.c_size_t
         for name in ("vmn_msg_item_garray", "vmn_msg_item_rarray", "vmn_pos_permutation_commitment"):
             getattr(_plib, name).restype = C.c_void_p
@@ -178,6 +178,16 @@ class Message:
             return [self.group.dec_el(r) for r in rows]
         return [int.from_bytes(r, "big") for r in rows]
 
+    def setKeyWidth(self, keywidth: int) -> "Message":
+        """``vmn_msg_set_keywidth``: from now on the items of k > 1 scalars (F', B', k_F, k_B) are written as elements of the
+        product over G^kappa resp. Z_q^kappa -- one more node level per plaintext component; 1 is the form every message has
+        when it is made."""
+        _check(plib().vmn_msg_set_keywidth(self._h, C.c_size_t(keywidth)))
+        return self
+
+    def keyWidth(self) -> int:
+        return plib().vmn_msg_keywidth(self._h)
+
     def toByteTree(self) -> bytes:
         size = plib().vmn_msg_bytetree_size(self._h)
         out = C.create_string_buffer(size)
@@ -198,8 +208,9 @@ class Message:
         return size
 
     @staticmethod
-    def fromByteTree(group, bt: bytes, layout: Sequence[int], counts: Sequence[int]) -> Optional["Message"]:
-        """None when the bytes are not a message of that layout (the caller substitutes trivial values)."""
+    def fromByteTree(group, bt: bytes, layout: Sequence[int], counts: Sequence[int], keywidth: int = 1) -> Optional["Message"]:
+        """None when the bytes are not a message of that layout (the caller substitutes trivial values).  ``keywidth`` > 1:
+        the nested form of ``setKeyWidth`` (``vmn_msg_from_bytetree_keyed``)."""
         h, ok = C.c_void_p(), C.c_int(0)
         lay = (C.c_int * len(layout))(*layout)
         cnt = (C.c_size_t * len(counts))(*counts)
@@ -208,8 +219,12 @@ class Message:
             ptr, length = blk[0], bt[1]
         else:
             ptr, length = bytes(bt), len(bt)
-        _check(plib().vmn_msg_from_bytetree(group._h, ptr, C.c_size_t(length), lay, cnt, C.c_size_t(len(layout)),
-                                            C.byref(h), C.byref(ok)))
+        if keywidth == 1:
+            _check(plib().vmn_msg_from_bytetree(group._h, ptr, C.c_size_t(length), lay, cnt, C.c_size_t(len(layout)),
+                                                C.byref(h), C.byref(ok)))
+        else:
+            _check(plib().vmn_msg_from_bytetree_keyed(group._h, ptr, C.c_size_t(length), lay, cnt, C.c_size_t(len(layout)),
+                                                      C.c_size_t(keywidth), C.byref(h), C.byref(ok)))
         return Message(group, h) if ok.value else None
 
     @staticmethod
@@ -435,13 +450,14 @@ class PoSBasicTW(_NativeProof):
         """``getD()`` (:958): B_{N-1} / h_0^(prod e_i), after verify."""
         return self._get("D")
 
-    def readCommitment(self, bt, n: int, width: int):
+    def readCommitment(self, bt, n: int, width: int, keywidth: int = 1):
         """``setCommitment(ByteTreeReader)`` (:780-823): parse the published byte tree (framing, range and subgroup
-        membership of every element, on the GPU); malformed input gives None -- the caller substitutes trivial values."""
-        return Message.fromByteTree(self.G, bt, self._com_kinds, [n, 1, n, 1, 1, 2 * width])
+        membership of every element, on the GPU); malformed input gives None -- the caller substitutes trivial values.
+        ``width``: the components of a half in all (kappa * omega under a key of width ``keywidth`` = kappa)."""
+        return Message.fromByteTree(self.G, bt, self._com_kinds, [n, 1, n, 1, 1, 2 * width], keywidth)
 
-    def readReply(self, bt, n: int, width: int):
-        return Message.fromByteTree(self.G, bt, self._rep_kinds, [1, n, 1, 1, n, width])
+    def readReply(self, bt, n: int, width: int, keywidth: int = 1):
+        return Message.fromByteTree(self.G, bt, self._rep_kinds, [1, n, 1, 1, n, width], keywidth)
 
 
 class PoSCBasicTW(_NativeProof):

@@ -23,6 +23,17 @@ Above the single links: ``verify_session`` is the standalone verifier itself (Mi
 What the reference takes from its protocol-info XML (session id, bit lengths, the descriptions of group / PRG / hash
 that go into the global prefix, :158-189) is kept here in ``params.json`` next to the files; the XML itself and the
 bulletin board are out of scope.
+
+Under a public key of width kappa (``keywidth``; ProtocolElGamal.java:476-481, 738-744) the plaintext group is G^kappa
+(MixNetElGamalVerifyFiatShamir.java:316-317) and a ciphertext of width omega has 2 kappa omega components, component
+c = l kappa + j the key j of plaintext component l.  [NOT-IN-REF: VCR's PPGroup classes write the trees; here the rule of SURVEY.md
+App. D -- a product element, array or ring element is the node of its factors' trees -- applied once more] every half of a list,
+of a ciphertext-shaped element and every element of (Z_q^kappa)^omega is [omega > 1: node(omega; ...)] over [kappa > 1:
+node(kappa; ...)] over the components' own trees (``fiatshamir.nested_tree``).  kappa = 1 leaves every byte as it was;
+omega = 1 gives the bytes of an unkeyed list of width kappa.  The generators and der.rho do not depend on kappa (:556-576,
+:158-189), and g in the seeds of the shuffles is the generator of the atomic group (:659, :769, :1483).  Everywhere below
+``keywidth`` defaults to 1, ``width`` (where it is a parameter) is omega, and a wide key ``pkey`` has 2 kappa omega rows: g
+repeated, then y_0 .. y_(kappa-1) repeated omega times.
 """
 from __future__ import annotations
 
@@ -97,40 +108,48 @@ def derive_generators(grp, params: dict, rho: bytes, n: int) -> PGroupElementArr
 
 
 # ---- arrays as files ------------------------------------------------------------------------------------------------------
-def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray]) -> None:
+def _nested_pieces(arrays: Sequence[PGroupElementArray], keywidth: int):
+    """fs.nested_tree over the arrays' own trees, piece by piece (a list file is written without joining its arrays)."""
+    if keywidth < 1 or len(arrays) % keywidth:
+        raise ValueError("%d component arrays are no multiple of the key width %d" % (len(arrays), keywidth))
+    omega = len(arrays) // keywidth
+    if omega > 1:
+        yield fs._hdr(0, omega)
+    for l in range(omega):
+        if keywidth > 1:
+            yield fs._hdr(0, keywidth)
+        for a in arrays[l * keywidth:(l + 1) * keywidth]:
+            yield a.toByteTree()
+
+
+def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray], keywidth: int = 1) -> None:
     """A PPGroupElementArray of width w as 2w component arrays: node(u-part, v-part), a part being the array's own tree
-    at width 1 and node(w array trees) otherwise."""
+    at width 1 and node(w array trees) otherwise; under a key of width kappa 2 kappa w arrays, a part
+    nested once more (the head of this file)."""
     half = len(comps) // 2
     with open(path, "wb") as f:
         f.write(fs._hdr(0, 2))
         for part in (comps[:half], comps[half:]):
-            if half > 1:
-                f.write(fs._hdr(0, half))
-            for a in part:
-                f.write(a.toByteTree())
+            for piece in _nested_pieces(part, keywidth):
+                f.write(piece)
 
 
-def _ciphertexts_tree(comps: Sequence[PGroupElementArray]) -> bytes:
+def _ciphertexts_tree(comps: Sequence[PGroupElementArray], keywidth: int = 1) -> bytes:
     """The bytes write_ciphertexts puts into a list file."""
     half = len(comps) // 2
-    out = [fs._hdr(0, 2)]
-    for part in (comps[:half], comps[half:]):
-        if half > 1:
-            out.append(fs._hdr(0, half))
-        out += [a.toByteTree() for a in part]
-    return b"".join(out)
+    return fs._hdr(0, 2) + b"".join(piece for part in (comps[:half], comps[half:]) for piece in _nested_pieces(part, keywidth))
 
 
-def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0) -> Optional[List[PGroupElementArray]]:
-    """The 2w component arrays of a ciphertext list file, parsed (range + membership) on the GPU; None when the file is not
-    such a list (the verifier then fails the party, :1446-1460)."""
+def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
+    """The 2w component arrays (2 kappa w under a key of width kappa) of a ciphertext list file, parsed (range + membership) on
+    the GPU; None when the file is not such a list (the verifier then fails the party, :1446-1460)."""
     buf = _read_file(path)
     if buf is None:
         return None
-    return parse_ciphertexts(grp, buf, width, expected_n)
+    return parse_ciphertexts(grp, buf, width, expected_n, keywidth)
 
 
-def parse_ciphertexts(grp, buf: bytes, width: int, expected_n: int = 0) -> Optional[List[PGroupElementArray]]:
+def parse_ciphertexts(grp, buf: bytes, width: int, expected_n: int = 0, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
     """read_ciphertexts for a list file whose bytes the caller already holds."""
     pos = 0
 
@@ -150,12 +169,15 @@ def parse_ciphertexts(grp, buf: bytes, width: int, expected_n: int = 0) -> Optio
             if width > 1:
                 header(0, width)
             for _ in range(width):
-                n = int.from_bytes(buf[pos + 1:pos + 5], "big")
-                if len(buf) < pos + 5 or buf[pos] != 0 or (expected_n and n != expected_n):
-                    raise ValueError("array node")
-                size = grp.array_tree_size(n)
-                comps.append(grp.toElementArrayFromByteTree(buf[pos:pos + size], n))
-                pos += size
+                if keywidth > 1:
+                    header(0, keywidth)
+                for _ in range(keywidth):
+                    n = int.from_bytes(buf[pos + 1:pos + 5], "big")
+                    if len(buf) < pos + 5 or buf[pos] != 0 or (expected_n and n != expected_n):
+                        raise ValueError("array node")
+                    size = grp.array_tree_size(n)
+                    comps.append(grp.toElementArrayFromByteTree(buf[pos:pos + size], n))
+                    pos += size
         if pos != len(buf) or len({c.size() for c in comps}) != 1:
             raise ValueError("trailing bytes")
         return comps
@@ -186,9 +208,14 @@ def _arr(a) -> str:
     return "(" + ", ".join(_hex(x) for x in a.toInts()) + ")"
 
 
+def _hexk(x, keywidth: int = 1) -> str:
+    """_hex for an element of G^kappa resp. Z_q^kappa given as its kappa rows: "(row_0, .., row_(kappa-1))", the row itself at kappa = 1."""
+    return _hex(x) if keywidth == 1 else "(" + ", ".join(_hex(e) for e in x) + ")"
+
+
 # ---- prover: PoSTW.prove with nizkp != null ----------------------------------------------------------------------------
 def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], rand,
-                  H: Optional[PGroupElementArray] = None, out_file: Optional[str] = None) -> List[PGroupElementArray]:
+                  H: Optional[PGroupElementArray] = None, out_file: Optional[str] = None, keywidth: int = 1) -> List[PGroupElementArray]:
     """Party l shuffles the list in l_file(nizkp, l - 1) (given as W) and proves it: re-encryption + permutation
     (ShufflerElGamalSession.java:400-409, 273-278), then PoSTW.prove (:95-165).  Returns w'; writes L_l and the three
     proof files.  `rand`: the prover's random source (native.RandomSource semantics).  `out_file`: where L_l goes instead of
@@ -209,7 +236,7 @@ def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequ
     prover = native.PoSBasicTW(grp, NV, NE, NR, rand=rand)
     prover.precompute(g, H, pi)
     WP = native.reencrypt_native(grp, pkey, W, S, pi)
-    write_ciphertexts(out_file, WP)
+    write_ciphertexts(out_file, WP, keywidth)
     prover.setInstance(pkey, W, WP, S)
     u_bt = prover.u.toByteTree()
     with open(pc_file(nizkp, l), "wb") as f:                                     # "PermutationCommitment" :107-112
@@ -218,20 +245,20 @@ def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequ
     d.update(fs._hdr(0, 6) + grp.element_tree(g))
     d.update(H.toByteTree())
     d.update(u_bt)
-    d.update(fs.product_element_tree(grp, pkey))
+    d.update(fs.product_element_tree(grp, pkey, keywidth))
     for path in (l_file(nizkp, l - 1), out_file):
         with open(path, "rb") as f:
             d.update(f.read())
     seed = chal.finish(d, 8 * hashlib.new(hn).digest_size)
     prover.setBatchVectorSeed(seed)
     com = prover.commit()
-    com_bt = com.native.toByteTree()
+    com_bt = _keyed(com.native, keywidth).toByteTree()
     with open(posc_file(nizkp, l), "wb") as f:                                   # "Commitment" :131-139
         f.write(com_bt)
     v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")     # :141-149
     rep = prover.reply(v)
     with open(posr_file(nizkp, l), "wb") as f:                                   # "Reply" :151-159
-        f.write(rep.native.toByteTree())
+        f.write(_keyed(rep.native, keywidth).toByteTree())
     com = rep = None
     prover.free()
     for a in S:
@@ -241,34 +268,40 @@ def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequ
     return WP
 
 
-def write_inputs(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray]) -> None:
-    """params.json, FullPublicKey.bt and the input list L_0."""
+def _keyed(msg, keywidth: int):
+    """The proof message `msg` (native.Message), written under the key width from now on."""
+    return msg if keywidth == 1 else msg.setKeyWidth(keywidth)
+
+
+def write_inputs(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], keywidth: int = 1) -> None:
+    """params.json, FullPublicKey.bt and the input list L_0.  `pkey`: the rows of the key as the file holds it -- for a session
+    the basic key (g, .., g, y_0, .., y_(kappa-1)), an element of getCiphPGroup(plainPGroup, 1)."""
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
     with open(_p(nizkp, PARAMS), "w") as f:
         json.dump(params, f, indent=1)
     with open(pk_file(nizkp), "wb") as f:
-        f.write(fs.product_element_tree(grp, pkey))
-    write_ciphertexts(l_file(nizkp, 0), W)
+        f.write(fs.product_element_tree(grp, pkey, keywidth))
+    write_ciphertexts(l_file(nizkp, 0), W, keywidth)
 
 
 # ---- verifier: MixNetElGamalVerifyFiatShamirSession.verifyPoS -----------------------------------------------------------
 def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vectors: Optional[Dict[str, str]] = None,
-                   with_arrays: bool = False) -> bool:
+                   with_arrays: bool = False, keywidth: int = 1) -> bool:
     """verifyPoS(l, g, generators, input = L_(l-1), output = L_l) (:843-937).  `vectors` (a dict) receives the test vectors
     the reference prints under `vmnv -t` at the places it prints them; `with_arrays` adds the N-sized ones (PoS.B, PoS.Bp,
     PoS.k_B, PoS.k_E, bas.h).  A file that cannot be parsed makes the verdict False (the reference substitutes trivial values
     and the equations then fail)."""
     tv = vectors if vectors is not None else {}
-    width = len(pkey) // 2
+    width = len(pkey) // 2 // keywidth
     hn = _hashname(params)
     rho = global_prefix(params)
     tv["der.rho"] = rho.hex()                                                  # :188
     chal = fs.Challenger(rho, hn)
-    W = read_ciphertexts(grp, l_file(nizkp, l - 1), width)
+    W = read_ciphertexts(grp, l_file(nizkp, l - 1), width, 0, keywidth)
     if W is None:
         return False
     n = W[0].size()
-    WP = read_ciphertexts(grp, l_file(nizkp, l), width, n)
+    WP = read_ciphertexts(grp, l_file(nizkp, l), width, n, keywidth)
     if WP is None:
         return False
     H = derive_generators(grp, params, rho, n)                                 # :557-566
@@ -284,12 +317,12 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
         d.update(fs._hdr(0, 6) + grp.element_tree(grp.g))
         d.update(H.toByteTree())
         d.update(u_bt)
-        d.update(fs.product_element_tree(grp, pkey))
+        d.update(fs.product_element_tree(grp, pkey, keywidth))
         for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
             with open(path, "rb") as f:
                 d.update(f.read())
         return chal.finish(d, 8 * hashlib.new(hn).digest_size)
-    verdict = pos_core(nizkp, l, grp, params, pkey, W, WP, H, U, seed, tv, with_arrays)
+    verdict = pos_core(nizkp, l, grp, params, pkey, W, WP, H, U, seed, tv, with_arrays, keywidth)
     for a in W + WP + [H, U]:
         a.free()
     return verdict
@@ -309,7 +342,8 @@ def parse_commitment(grp, u_bt: Optional[bytes], n: int) -> Optional[PGroupEleme
         return None
 
 
-def pos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W, WP, H, U, seed, tv: dict, with_arrays: bool = False) -> bool:
+def pos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W, WP, H, U, seed, tv: dict, with_arrays: bool = False,
+             keywidth: int = 1) -> bool:
     """verifyPoS on loaded inputs: the lists W and WP, the generators H and the permutation commitment U as device arrays,
     `seed()` -> the seed of the batching vector (the one value that depends on the lists' and the generators' BYTES).  Reads
     the party's commitment and reply files; frees nothing it was given."""
@@ -319,12 +353,12 @@ def pos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W, WP, H, U,
     g = grp.g
     V = native.PoSBasicTW(grp, NV, NE, NR)
     try:
-        return _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays)
+        return _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays, keywidth)
     finally:
         V.free()
 
 
-def _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays) -> bool:
+def _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays, keywidth=1) -> bool:
     V.precompute(g, H)                                                         # :857
     V.setInstance(pkey, W, WP)
     V.setPermutationCommitment(U)
@@ -335,7 +369,7 @@ def _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, 
     tv["PoS.A"] = _hex(V.getA())                                               # :888-889
     tv["PoS.F"] = "(" + ", ".join(_hex(x) for x in V.getF()) + ")"
     com_bt = _read_file(posc_file(nizkp, l))                                   # :892-895
-    com = V.readCommitment(com_bt, n, width) if com_bt is not None else None
+    com = V.readCommitment(com_bt, n, width, keywidth) if com_bt is not None else None
     if com is None:
         return False
     V.setCommitment(com)
@@ -347,7 +381,7 @@ def _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, 
     tv["PoS.v"] = format(vch, "x")                                             # :915
     V.setChallenge(vch)
     rep_bt = _read_file(posr_file(nizkp, l))                                   # :921-925
-    rep = V.readReply(rep_bt, n, width) if rep_bt is not None else None
+    rep = V.readReply(rep_bt, n, width, keywidth) if rep_bt is not None else None
     if rep is None:
         return False
     verdict = V.verify(rep)
@@ -423,9 +457,11 @@ def _seed_and_challenge(chal, hn, head: bytes, parts, commit_fn, NV):
     return seed, com_bt, v
 
 
-def write_precomputation(nizkp: str, l: int, grp, params: dict, n_max: int, rand, H: Optional[PGroupElementArray] = None):
+def write_precomputation(nizkp: str, l: int, grp, params: dict, n_max: int, rand, H: Optional[PGroupElementArray] = None,
+                         keywidth: int = 1):
     """`vmn -precomp` of party l for N_0 = n_max ciphertexts: the permutation commitment u and its proof of a shuffle of
-    commitments.  Returns the prover's secrets for the online phase: (pi, R, U, H)."""
+    commitments.  Returns the prover's secrets for the online phase: (pi, R, U, H).  Nothing here depends on `keywidth`: the
+    commitment and its proof live in the atomic group (:652-703); the parameter is what write_session hands every writer."""
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
     NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
     hn = _hashname(params)
@@ -462,7 +498,7 @@ def write_precomputation(nizkp: str, l: int, grp, params: dict, n_max: int, rand
 
 
 def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], rand,
-                            pi, R, U, H, out_file: Optional[str] = None) -> List[PGroupElementArray]:
+                            pi, R, U, H, out_file: Optional[str] = None, keywidth: int = 1) -> List[PGroupElementArray]:
     """The online phase for the N <= N_0 ciphertexts that arrived (W = the list in l_file(nizkp, l - 1)): shrink
     (PermutationCommitment.java:390-471, keep list to its file), re-encrypt and permute (ShufflerElGamalSession.java:789-792),
     CCPoSW.prove (:75-158).  Returns w'.  `out_file`: where L_l goes instead of l_file(nizkp, l)."""
@@ -478,7 +514,7 @@ def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequenc
     U_s, R_s, H_s = U.extract(keep), R.copyOfRange(0, n), H.copyOfRange(0, n)
     S = [native.random_ring_array_native(grp, rand, n, NR) for _ in range(width)]
     WP = native.reencrypt_native(grp, pkey, W, S, pi_s)
-    write_ciphertexts(out_file, WP)
+    write_ciphertexts(out_file, WP, keywidth)
     P = native.CCPoSBasicW(grp, NV, NE, NR, rand=rand)
     P.setInstance(g, H_s, U_s, pkey, W, WP, R_s, pi_s, S)
     box = {}
@@ -486,16 +522,16 @@ def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequenc
     def commit(seed):
         P.setBatchVectorSeed(seed)
         box["com"] = P.commit()
-        bt = box["com"].native.toByteTree()
+        bt = _keyed(box["com"].native, keywidth).toByteTree()
         with open(ccposc_file(nizkp, l), "wb") as f:
             f.write(bt)
         return bt
     _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 6) + grp.element_tree(g),
-                                  [H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey), l_file(nizkp, l - 1), out_file],
+                                  [H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey, keywidth), l_file(nizkp, l - 1), out_file],
                                   commit, NV)
     rep = P.reply(v)
     with open(ccposr_file(nizkp, l), "wb") as f:
-        f.write(rep.native.toByteTree())
+        f.write(_keyed(rep.native, keywidth).toByteTree())
     box.clear()
     rep = None
     P.free()
@@ -505,13 +541,13 @@ def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequenc
 
 
 def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, n_max: int,
-                               vectors: Optional[Dict[str, str]] = None) -> bool:
+                               vectors: Optional[Dict[str, str]] = None, keywidth: int = 1) -> bool:
     """The standalone verifier's path for a precomputed shuffle of party l (MixNetElGamalVerifyFiatShamirSession.java
     :1395-1500): readPermutationCommitment(N_0), verifyPoSC, read the output, shrinkPermComm through the keep list, verifyCCPoS.
     `vectors` receives der.rho, PoSC.s, PoSC.v, CCPoS.s, CCPoS.v (the names the reference registers, Tool.java:155-175) and the
     verifiers' intermediates (PoSC.A/C/D, CCPoS.A, CCPoS.B: not printed by the reference; for diffing two builds of this code)."""
     tv = vectors if vectors is not None else {}
-    width = len(pkey) // 2
+    width = len(pkey) // 2 // keywidth
     hn = _hashname(params)
     rho = global_prefix(params)
     tv["der.rho"] = rho.hex()
@@ -527,11 +563,11 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
                      lambda: chal.challenge(fs._hdr(0, 3) + grp.element_tree(g) + H.toByteTree() + u_bt, bits), tv):
         return False           # (the reference then takes the generators for u and goes on; a harness stops with the verdict)
     # ---- the lists, the keep list, verifyCCPoS :757-830
-    W = read_ciphertexts(grp, l_file(nizkp, l - 1), width)
+    W = read_ciphertexts(grp, l_file(nizkp, l - 1), width, 0, keywidth)
     if W is None:
         return False
     n = W[0].size()
-    WP = read_ciphertexts(grp, l_file(nizkp, l), width, n)
+    WP = read_ciphertexts(grp, l_file(nizkp, l), width, n, keywidth)
     if WP is None:
         return False
     keep = read_keep_list(nizkp, l, n_max, n)
@@ -544,12 +580,12 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
         d.update(fs._hdr(0, 6) + grp.element_tree(g))
         d.update(H_s.toByteTree())
         d.update(U_s.toByteTree())
-        d.update(fs.product_element_tree(grp, pkey))
+        d.update(fs.product_element_tree(grp, pkey, keywidth))
         for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
             with open(path, "rb") as f:
                 d.update(f.read())
         return chal.finish(d, bits)
-    verdict = ccpos_core(nizkp, l, grp, params, pkey, H_s, U_s, W, WP, seed2, tv)
+    verdict = ccpos_core(nizkp, l, grp, params, pkey, H_s, U_s, W, WP, seed2, tv, keywidth)
     for a in W + WP + [H, U, U_s, H_s]:
         a.free()
     return verdict
@@ -595,19 +631,19 @@ def _posc_core(V, nizkp, l, grp, chal, NV, H, U, n_max, seed, tv) -> bool:
     return bool(ok_posc)
 
 
-def ccpos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, H_s, U_s, W, WP, seed, tv: dict) -> bool:
+def ccpos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, H_s, U_s, W, WP, seed, tv: dict, keywidth: int = 1) -> bool:
     """verifyCCPoS (:757-830) on loaded inputs: the shrunk generators and permutation commitment and the two lists as device
     arrays, `seed()` -> the seed of the batching vector.  Frees nothing it was given."""
     NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
     chal = fs.Challenger(global_prefix(params), _hashname(params))
     C = native.CCPoSBasicW(grp, NV, NE, NR)
     try:
-        return _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv)
+        return _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv, keywidth)
     finally:
         C.free()
 
 
-def _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv) -> bool:
+def _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv, keywidth=1) -> bool:
     n, width = W[0].size(), len(pkey) // 2
     C.setInstance(grp.g, H_s, U_s, pkey, W, WP)
     seed2 = seed()
@@ -617,7 +653,7 @@ def _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv) -> 
     A, B = C.getAB()
     tv["CCPoS.A"], tv["CCPoS.B"] = _hex(A), "(" + ", ".join(_hex(x) for x in B) + ")"
     com_bt = _read_file(ccposc_file(nizkp, l))
-    com = native.Message.fromByteTree(grp, com_bt, native.CCPoSBasicW._com_kinds, [1, 2 * width]) if com_bt is not None else None
+    com = native.Message.fromByteTree(grp, com_bt, native.CCPoSBasicW._com_kinds, [1, 2 * width], keywidth) if com_bt is not None else None
     if com is None:
         return False
     C.setCommitment(com)
@@ -625,7 +661,7 @@ def _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv) -> 
     tv["CCPoS.v"] = format(v2, "x")
     C.setChallenge(v2)
     rep_bt = _read_file(ccposr_file(nizkp, l))
-    rep = native.Message.fromByteTree(grp, rep_bt, native.CCPoSBasicW._rep_kinds, [1, width, n]) if rep_bt is not None else None
+    rep = native.Message.fromByteTree(grp, rep_bt, native.CCPoSBasicW._rep_kinds, [1, width, n], keywidth) if rep_bt is not None else None
     if rep is None:
         return False
     return bool(C.verify(rep))
@@ -644,6 +680,10 @@ def _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv) -> 
 # is node(omega array trees), the array's own tree at omega = 1 -- a part of a ciphertext list file; an element of G^omega (B')
 # is node(omega element trees), the element's own tree at omega = 1.  An element's tree is a leaf over a modular group and
 # node(leaf(x), leaf(y)) over a curve (infinity: both leaves 0xff), as in the arrays and messages the library writes.
+# Under a key of width kappa (v.plainPGroup = G^kappa) the factors, the plaintexts and B' are nested once more (the head of this
+# file); y' is node(kappa element trees), the reply node(kappa leaves) (Z_q^kappa), the polynomial in the exponent -- threshold
+# coefficients in G^kappa, :239-265 -- node(kappa array trees), array j holding row j of every coefficient; a key, a share and a
+# coefficient are then kappa-tuples, row 0 first.
 # =============================================================================================================================
 def poly_file(nizkp):
     return _p(nizkp, "proofs", "PolynomialInExponent.bt")
@@ -674,45 +714,92 @@ def _prg_seed_bits(params: dict) -> int:
     return 8 * hashlib.new({"SHA-256": "sha256", "SHA-384": "sha384", "SHA-512": "sha512"}[params.get("prg", "SHA-256")]).digest_size
 
 
-def _wide_array_tree(comps: Sequence[PGroupElementArray]) -> bytes:
-    """toByteTree() of an array of G^omega given as its omega component arrays."""
-    body = b"".join(a.toByteTree() for a in comps)
-    return body if len(comps) == 1 else fs._hdr(0, len(comps)) + body
+def _wide_array_tree(comps: Sequence[PGroupElementArray], keywidth: int = 1) -> bytes:
+    """toByteTree() of an array of G^omega given as its omega component arrays, of (G^kappa)^omega given as its kappa omega."""
+    return fs.nested_tree([a.toByteTree() for a in comps], keywidth)
 
 
-def _read_wide_array(grp, path: str, width: int, n: int) -> Optional[List[PGroupElementArray]]:
-    """The omega component arrays (n elements each) of such a file; None when the file is missing or is no such array."""
+def _nested_reader(buf: bytes, pos: int, width: int, keywidth: int, item):
+    """The kappa * omega values of fs.nested_tree at buf[pos:], each read by item(buf, pos) -> (value, next pos) | None;
+    (values, next pos), or None when a node is not the one the widths ask for."""
+    def node(count):
+        nonlocal pos
+        if buf[pos:pos + 5] != fs._hdr(0, count):
+            return False
+        pos += 5
+        return True
+    if width > 1 and not node(width):
+        return None
+    values = []
+    for _ in range(width):
+        if keywidth > 1 and not node(keywidth):
+            return None
+        for _ in range(keywidth):
+            got = item(buf, pos)
+            if got is None:
+                return None
+            values.append(got[0])
+            pos = got[1]
+    return values, pos
+
+
+def _read_wide_array(grp, path: str, width: int, n: int, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
+    """The omega component arrays (kappa omega under a key of width kappa; n elements each) of such a file; None when the file
+    is missing or is no such array."""
+    comps = []
     try:
         with open(path, "rb") as f:
             buf = f.read()
-        pos = 0
-        if width > 1:
-            if buf[:5] != fs._hdr(0, width):
-                return None
-            pos = 5
         size = grp.array_tree_size(n)
-        comps = []
-        for _ in range(width):
-            comps.append(grp.toElementArrayFromByteTree(buf[pos:pos + size], n))
-            pos += size
-        if pos != len(buf) or not all(c.isMember() for c in comps):
+
+        def array(b, at):
+            comps.append(grp.toElementArrayFromByteTree(b[at:at + size], n))
+            return comps[-1], at + size
+        got = _nested_reader(buf, 0, width, keywidth, array)
+        if got is None or got[1] != len(buf) or not all(c.isMember() for c in comps):
             return None
         return comps
     except (OSError, ValueError, native.VmnError):
         return None
 
 
-def _wide_element_tree(grp, els) -> bytes:
-    return fs.wide_element_tree(grp, els)
+def _wide_element_tree(grp, els, keywidth: int = 1) -> bytes:
+    return fs.wide_element_tree(grp, els, keywidth)
 
 
-def _commitment_tree(grp, yp, Bp) -> bytes:
-    return fs._hdr(0, 2) + grp.element_tree(yp) + _wide_element_tree(grp, Bp)
+def _rows(x, keywidth: int):
+    """An element of G^kappa / Z_q^kappa as the tuple of its rows (kappa = 1: the element itself is the one row)."""
+    return (x,) if keywidth == 1 else tuple(x)
 
 
-def _read_commitment(grp, path: str, width: int):
-    """(y', (B'_0 .. B'_(omega-1))) of a commitment file as group elements; None when the framing is wrong (over a curve also:
-    a leaf that is not of the coordinate width, a point that is not on the curve)."""
+def _commitment_tree(grp, yp, Bp, keywidth: int = 1) -> bytes:
+    return fs._hdr(0, 2) + fs.nested_tree([grp.element_tree(e) for e in _rows(yp, keywidth)], keywidth) + _wide_element_tree(grp, Bp, keywidth)
+
+
+def _reply_tree(grp, kx, keywidth: int = 1) -> bytes:
+    """k_x of Z_q^kappa: node(kappa leaves), the leaf itself at kappa = 1."""
+    return fs.nested_tree([fs.leaf(int(v).to_bytes(grp.exp_bytes, "big")) for v in _rows(kx, keywidth)], keywidth)
+
+
+def _read_reply(grp, buf: bytes, keywidth: int = 1):
+    """The reply of a DecrFactReply file's bytes (an integer, a kappa-tuple under a key of width kappa); None when the bytes are
+    no such tree.  A row >= q is handed on: it costs the party its verdict, not the file its format (:606-613)."""
+    xb = grp.exp_bytes
+
+    def leaf(b, at):
+        if b[at:at + 5] != fs._hdr(1, xb) or len(b) < at + 5 + xb:
+            return None
+        return int.from_bytes(b[at + 5:at + 5 + xb], "big"), at + 5 + xb
+    got = _nested_reader(buf, 0, 1, keywidth, leaf)
+    if got is None or got[1] != len(buf):
+        return None
+    return got[0][0] if keywidth == 1 else tuple(got[0])
+
+
+def _read_commitment(grp, path: str, width: int, keywidth: int = 1):
+    """(y', (B'_0 .. B'_(omega-1))) of a commitment file as group elements (y' a kappa-tuple and B' kappa omega elements under a
+    key of width kappa); None when the framing is wrong (over a curve also: a leaf that is not of the coordinate width, a point
+    that is not on the curve)."""
     try:
         with open(path, "rb") as f:
             buf = f.read()
@@ -720,20 +807,13 @@ def _read_commitment(grp, path: str, width: int):
         return None
     if buf[:5] != fs._hdr(0, 2):
         return None
-    pos, els = 5, []
-    for i in range(1 + width):
-        if i == 1 and width > 1:
-            if buf[pos:pos + 5] != fs._hdr(0, width):
-                return None
-            pos += 5
-        got = grp.element_from_tree(buf, pos)
-        if got is None:
-            return None
-        els.append(got[0])
-        pos = got[1]
-    if pos != len(buf):
+    yp = _nested_reader(buf, 5, 1, keywidth, grp.element_from_tree)
+    if yp is None:
         return None
-    return els[0], tuple(els[1:])
+    Bp = _nested_reader(buf, yp[1], width, keywidth, grp.element_from_tree)
+    if Bp is None or Bp[1] != len(buf):
+        return None
+    return (yp[0][0] if keywidth == 1 else tuple(yp[0])), tuple(Bp[0])
 
 
 def eval_polynomial_in_exponent(grp, coeffs: Sequence, l: int):
@@ -745,11 +825,52 @@ def eval_polynomial_in_exponent(grp, coeffs: Sequence, l: int):
     return acc
 
 
-def _decryption_seed(chal, grp, params, list_bytes: bytes, poly_bt: bytes, factor_trees: Sequence[bytes]) -> bytes:
-    """challenge(node(node(g, ciphertexts), node(polynomial, node(factors of parties 1..k))), 8 * minNoSeedBytes)  :434-461"""
+def eval_keys(grp, coeffs: Sequence, l: int, keywidth: int = 1):
+    """eval_polynomial_in_exponent row by row for coefficients in G^kappa (kappa-tuples): the kappa-tuple y_l."""
+    if keywidth == 1:
+        return eval_polynomial_in_exponent(grp, coeffs, l)
+    return tuple(eval_polynomial_in_exponent(grp, [c[j] for c in coeffs], l) for j in range(keywidth))
+
+
+def _polynomial_tree(grp, poly: Sequence, keywidth: int = 1) -> bytes:
+    """PolynomialInExponent.bt: the array tree of the coefficients; in G^kappa node(kappa array trees), array j = row j."""
+    arrays = [grp.toElementArray([_rows(c, keywidth)[j] for c in poly]) for j in range(keywidth)]
+    bt = fs.nested_tree([a.toByteTree() for a in arrays], keywidth)
+    for a in arrays:
+        a.free()
+    return bt
+
+
+def parse_polynomial(grp, buf: Optional[bytes], threshold: int, keywidth: int = 1):
+    """The `threshold` coefficients of a PolynomialInExponent.bt file's bytes (kappa-tuples under a key of width kappa); None
+    when the bytes are no such tree or a coefficient is outside the group."""
+    arrays = []
+    try:
+        if buf is None:
+            return None
+        size = grp.array_tree_size(threshold)
+
+        def array(b, at):
+            arrays.append(grp.toElementArrayFromByteTree(b[at:at + size], threshold))
+            return arrays[-1], at + size
+        got = _nested_reader(buf, 0, 1, keywidth, array)
+        if got is None or got[1] != len(buf) or not all(a.isMember() for a in arrays):
+            return None
+        rows = [a.toInts() for a in arrays]
+        return rows[0] if keywidth == 1 else [tuple(r[d] for r in rows) for d in range(threshold)]
+    except (ValueError, native.VmnError):
+        return None
+    finally:
+        for a in arrays:
+            a.free()
+
+
+def _decryption_seed(chal, grp, params, list_bytes: bytes, poly_bt: bytes, factor_trees: Sequence[bytes], keywidth: int = 1) -> bytes:
+    """challenge(node(node(g, ciphertexts), node(polynomial, node(factors of parties 1..k))), 8 * minNoSeedBytes)  :434-461;
+    g is plainPGroup.getg() = (g, .., g) (:1587)."""
     bits = _prg_seed_bits(params)
     d = chal.start(bits)
-    d.update(fs._hdr(0, 2) + fs._hdr(0, 2) + grp.element_tree(grp.g))
+    d.update(fs._hdr(0, 2) + fs._hdr(0, 2) + fs.nested_tree([grp.element_tree(grp.g)] * keywidth, keywidth))
     d.update(list_bytes)
     d.update(fs._hdr(0, 2) + poly_bt + fs._hdr(0, len(factor_trees)))
     for t in factor_trees:
@@ -759,39 +880,42 @@ def _decryption_seed(chal, grp, params, list_bytes: bytes, poly_bt: bytes, facto
 
 def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], poly: Sequence[int],
                      shares: Sequence[Optional[int]], rand, k: int, threshold: int,
-                     tamper=None) -> List[PGroupElementArray]:
+                     tamper=None, keywidth: int = 1, tamper_reply=None) -> List[PGroupElementArray]:
     """All k parties of DistrElGamalSession.decrypt (:344-545) on the list W (2 omega component arrays, the list the last mix
     server wrote): `poly` = the coefficients g^(a_d) of the polynomial in the exponent (threshold of them), `shares` = the
     secret shares x_l (k + 1 entries, entry 0 unused), `rand` = the parties' random source.  Writes the six kinds of files and
     returns the plaintexts (omega arrays).  The polynomial in the exponent is written as the array tree of its coefficients:
     PGroup.toByteTree(PGroupElement[]) is VCR code, not part of the reference tree.  `tamper(l, factors)` (tests): replaces the
-    factors party l publishes."""
+    factors party l publishes; `tamper_reply(l, k_x)` (tests): the reply it publishes.  Under a key of width `keywidth` = kappa
+    W has 2 kappa omega arrays and a coefficient of `poly` and a share are kappa-tuples."""
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
     NV, NE = int(params["vbitlenro"]), int(params["ebitlenro"])
-    width = len(W) // 2
+    width = len(W) // 2                                                            # components in all: kappa * omega
     hn = _hashname(params)
     chal = fs.Challenger(global_prefix(params), hn)
     U, V = list(W[:width]), list(W[width:])
-    y = pkey[-1]
-    ys = [None] + [eval_polynomial_in_exponent(grp, poly, l) for l in range(1, k + 1)]
-    poly_bt = grp.toElementArray(list(poly)).toByteTree()
+    y = pkey[-1] if keywidth == 1 else tuple(pkey[width:width + keywidth])
+    keyed = {} if keywidth == 1 else {"keywidth": keywidth}
+    ys = [None] + [eval_keys(grp, poly, l, keywidth) for l in range(1, k + 1)]
+    poly_bt = _polynomial_tree(grp, poly, keywidth)
     with open(poly_file(nizkp), "wb") as f:
         f.write(poly_bt)
     F: List[Optional[List[PGroupElementArray]]] = [None]
     for l in range(1, k + 1):                                                      # :384-399
-        fl = native.decryptionFactors(U, shares[l], grp.q, k)
+        fl = native.decryptionFactors(U, shares[l] if keywidth == 1 else list(shares[l]), grp.q, k)
         if tamper is not None:
             fl = tamper(l, fl)
         F.append(fl)
         with open(df_file(nizkp, l), "wb") as f:
-            f.write(_wide_array_tree(fl))
+            f.write(_wide_array_tree(fl, keywidth))
     correct = [True] * (k + 1)
     comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)         # :406-410
-    seed = _decryption_seed(chal, grp, params, _ciphertexts_tree(W), poly_bt, [_wide_array_tree(fl) for fl in F[1:]])
+    seed = _decryption_seed(chal, grp, params, _ciphertexts_tree(W, keywidth), poly_bt, [_wide_array_tree(fl, keywidth) for fl in F[1:]],
+                            keywidth)
     sessions = []
     for l in range(1, k + 1):
         s = native.DistrElGamalSessionBasic(grp, l, k, threshold, NE, rand=rand)
-        s.setInstance(U, ys, F)
+        s.setInstance(U, ys, F, **keyed)
         s.setBatchVectorSeed(seed)
         s.batchInput()
         sessions.append(s)
@@ -800,14 +924,16 @@ def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[
         yp, Bp = sessions[l - 1].commit(shares[l])
         commitments.append((yp, Bp))
         with open(dfc_file(nizkp, l), "wb") as f:
-            f.write(_commitment_tree(grp, yp, Bp))
-    com_bt = fs._hdr(0, k) + b"".join(_commitment_tree(grp, *c) for c in commitments[1:])
+            f.write(_commitment_tree(grp, yp, Bp, keywidth))
+    com_bt = fs._hdr(0, k) + b"".join(_commitment_tree(grp, *c, keywidth) for c in commitments[1:])
     v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")      # :474-480
     ver = sessions[0]
     for l in range(1, k + 1):                                                      # :483
         kx = sessions[l - 1].reply(v)
+        if tamper_reply is not None:
+            kx = tamper_reply(l, kx)
         with open(dfr_file(nizkp, l), "wb") as f:
-            f.write(fs.leaf(kx.to_bytes(grp.exp_bytes, "big")))
+            f.write(_reply_tree(grp, kx, keywidth))
         if l != 1:
             ver.setCommitment(l, *commitments[l])
             ver.setReply(l, kx)
@@ -822,7 +948,7 @@ def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[
         comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)
     plain = native.plaintexts(V, comb)                                             # :536-538
     with open(plaintexts_file(nizkp), "wb") as f:
-        f.write(_wide_array_tree(plain))
+        f.write(_wide_array_tree(plain, keywidth))
     with open(cr_file(nizkp), "wb") as f:                                          # :542
         f.write(_booleans_tree(correct))
     for s in sessions:
@@ -832,7 +958,8 @@ def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[
     return plain
 
 
-def verify_decryption(nizkp: str, grp, params: dict, pkey: Sequence, list_file: str, vectors: Optional[Dict[str, str]] = None) -> bool:
+def verify_decryption(nizkp: str, grp, params: dict, pkey: Sequence, list_file: str, vectors: Optional[Dict[str, str]] = None,
+                      keywidth: int = 1) -> bool:
     """The verifier's decryption branch (MixNetElGamalVerifyFiatShamirSession.java:1545-1667) for the list in `list_file`:
     read the correct indices (at least `threshold` of them, :1163-1174) and every party's factors, combine the indicated ones,
     derive the seed and the challenge, check the COMBINED proof, and match Plaintexts.bt with second components x combined
@@ -843,16 +970,16 @@ def verify_decryption(nizkp: str, grp, params: dict, pkey: Sequence, list_file: 
     list_bytes = _read_file(list_file)
     if list_bytes is None or not os.path.exists(poly_file(nizkp)) or not os.path.exists(cr_file(nizkp)):
         return False
-    W = parse_ciphertexts(grp, list_bytes, len(pkey) // 2)
+    W = parse_ciphertexts(grp, list_bytes, len(pkey) // 2 // keywidth, 0, keywidth)
     if W is None:
         return False
-    ok, _ = dec_core(nizkp, grp, params, pkey, W, list_bytes, tv)
+    ok, _ = dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, keywidth)
     for a in W:
         a.free()
     return ok
 
 
-def dec_core(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], list_bytes, tv: dict):
+def dec_core(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], list_bytes, tv: dict, keywidth: int = 1):
     """The decryption branch on a loaded list: its 2 omega component arrays W and the bytes of its tree (what the seed is
     hashed over).  Returns (verdict, the correct indices read from CorrectIndices.bt or None); frees nothing it was given."""
     NV, NE = int(params["vbitlenro"]), int(params["ebitlenro"])
@@ -868,24 +995,22 @@ def dec_core(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupEl
         return False, None
     if correct is None or sum(1 for l in range(1, k + 1) if correct[l]) < threshold:
         return False, correct
-    return _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct), correct
+    return _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct, keywidth), correct
 
 
-def _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct) -> bool:
-    n = W[0].size()
-    try:
-        P = grp.toElementArrayFromByteTree(poly_bt, threshold)
-        if not P.isMember():
-            return False
-        poly = P.toInts()
-    except (ValueError, native.VmnError):
+def _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct, keywidth=1) -> bool:
+    n = W[0].size()                                                                # (width: components in all, kappa * omega)
+    omega = width // keywidth
+    keyed = {} if keywidth == 1 else {"keywidth": keywidth}
+    poly = parse_polynomial(grp, poly_bt, threshold, keywidth)
+    if poly is None:
         return False
-    ys = [None] + [eval_polynomial_in_exponent(grp, poly, l) for l in range(1, k + 1)]
+    ys = [None] + [eval_keys(grp, poly, l, keywidth) for l in range(1, k + 1)]
     for l in range(1, k + 1):
-        tv["Dec.y_%d" % l] = _hex(ys[l])
+        tv["Dec.y_%d" % l] = _hexk(ys[l], keywidth)
     F: List[Optional[List[PGroupElementArray]]] = [None]
     for l in range(1, k + 1):                                                      # getDecryptionFactors :1098-1114
-        fl = _read_wide_array(grp, df_file(nizkp, l), width, n)
+        fl = _read_wide_array(grp, df_file(nizkp, l), omega, n, keywidth)
         if fl is None:
             return False
         F.append(fl)
@@ -894,44 +1019,41 @@ def _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold,
         comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)     # :1569-1574
     except native.VmnError:
         return False
-    seed = _decryption_seed(chal, grp, params, list_bytes, poly_bt, [_wide_array_tree(fl) for fl in F[1:]])
+    seed = _decryption_seed(chal, grp, params, list_bytes, poly_bt, [_wide_array_tree(fl, keywidth) for fl in F[1:]], keywidth)
     tv["Dec.s"] = seed.hex()                                                       # :1609
     basic = native.DistrElGamalSessionBasic(grp, 1, k, threshold, NE)
-    basic.setInstance(U, ys, F)
+    basic.setInstance(U, ys, F, **keyed)
     basic.setBatchVectorSeed(seed)
     basic.batchInput()
     trees = []
     for l in range(1, k + 1):                                                      # readCommitments :1182-1190
-        c = _read_commitment(grp, dfc_file(nizkp, l), width)
+        c = _read_commitment(grp, dfc_file(nizkp, l), omega, keywidth)
         if c is None:
             return False
         try:
             basic.setCommitment(l, *c)
         except native.VmnError:
             return False
-        trees.append(_commitment_tree(grp, *c))
+        trees.append(_commitment_tree(grp, *c, keywidth))
     v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + fs._hdr(0, k) + b"".join(trees), NV), "big")
     tv["Dec.v"] = str(v)                                                           # :1634
     for l in range(1, k + 1):                                                      # readReplies :1198-1206
-        try:
-            with open(dfr_file(nizkp, l), "rb") as f:
-                buf = f.read()
-        except OSError:
+        buf = _read_file(dfr_file(nizkp, l))
+        kx = _read_reply(grp, buf, keywidth) if buf is not None else None
+        if kx is None:
             return False
-        if len(buf) != 5 + grp.exp_bytes or buf[:5] != fs._hdr(1, grp.exp_bytes):
-            return False
-        basic.setReply(l, int.from_bytes(buf[5:], "big"))
+        basic.setReply(l, kx)
     try:
-        basic.combine(correct, pkey[-1], comb)                                     # :1640-1644
+        basic.combine(correct, pkey[-1] if keywidth == 1 else tuple(pkey[width:width + keywidth]), comb)       # :1640-1644
         basic.batchCombined()
         verdict = basic.verifyCombined(v)
     except native.VmnError:
         return False
     computed = native.plaintexts(V, comb)                                          # :1652-1663
-    plain = _read_wide_array(grp, plaintexts_file(nizkp), width, n)
+    plain = _read_wide_array(grp, plaintexts_file(nizkp), omega, n, keywidth)
     ok = bool(verdict) and plain is not None and all(a.equals(b) for a, b in zip(plain, computed))
     basic.free()
-    for a in comb + computed + (plain or []) + [c for fl in F[1:] for c in fl] + [P]:
+    for a in comb + computed + (plain or []) + [c for fl in F[1:] for c in fl]:
         a.free()
     return ok
 
@@ -1148,7 +1270,8 @@ class SessionVerdict:
 @dataclasses.dataclass
 class SessionEngines:
     """The proof engines run_session drives.  Every one takes the session context `ctx` (nizkp, grp, params with the proof's
-    auxsid, pkey = the widened key) first; device arrays are opaque to the control flow.
+    auxsid, pkey = the widened key, keywidth = kappa) first; device arrays are opaque to the control flow.  With kappa > 1 g',
+    y and a coefficient are kappa-tuples and a list has 2 kappa width arrays.
         read_pkey(ctx, path) -> [g', y] | None                 read_poly(ctx, path, threshold) -> coefficients | None
         read_list(ctx, path, data, width, n) -> list | None     (n = 0: any size)      list_size(ctx, list) -> N
         derive_generators(ctx, rho, n) -> (H, bytes of H's tree)                        copy_range(ctx, array, n) -> array
@@ -1178,30 +1301,22 @@ class SessionEngines:
 
 # ---- the engines on the GPU ---------------------------------------------------------------------------------------------------
 def _gpu_read_pkey(ctx, path):
+    """An element of getCiphPGroup(plainPGroup, 1): node(g', y), each half node(kappa element trees) when kappa > 1."""
     buf = _read_file(path)
     if buf is None or buf[:5] != fs._hdr(0, 2):
         return None
     pos, els = 5, []
     for _ in range(2):
-        got = ctx.grp.element_from_tree(buf, pos)
+        got = _nested_reader(buf, pos, 1, ctx.keywidth, ctx.grp.element_from_tree)
         if got is None:
             return None
-        els.append(got[0])
+        els.append(got[0][0] if ctx.keywidth == 1 else tuple(got[0]))
         pos = got[1]
     return els if pos == len(buf) else None
 
 
 def _gpu_read_poly(ctx, path, threshold):
-    buf = _read_file(path)
-    try:
-        if buf is None:
-            return None
-        P = ctx.grp.toElementArrayFromByteTree(buf, threshold)
-        coeffs = P.toInts() if P.isMember() else None
-        P.free()
-        return coeffs
-    except (ValueError, native.VmnError):
-        return None
+    return parse_polynomial(ctx.grp, _read_file(path), threshold, ctx.keywidth)
 
 
 def _gpu_derive_generators(ctx, rho, n):
@@ -1231,16 +1346,16 @@ def _gpu_free(ctx, arrays):
 
 GPU_ENGINES = SessionEngines(
     read_pkey=_gpu_read_pkey, read_poly=_gpu_read_poly,
-    read_list=lambda ctx, path, data, width, n: parse_ciphertexts(ctx.grp, data, width, n),
+    read_list=lambda ctx, path, data, width, n: parse_ciphertexts(ctx.grp, data, width, n, ctx.keywidth),
     list_size=lambda ctx, comps: comps[0].size(),
     derive_generators=_gpu_derive_generators,
     copy_range=lambda ctx, a, n: a.copyOfRange(0, n),
     read_commitment=lambda ctx, data, n: parse_commitment(ctx.grp, data, n),
     shrink=_gpu_shrink,
     verify_posc=lambda ctx, l, H, U, n_max, seed, tv: posc_core(ctx.nizkp, l, ctx.grp, ctx.params, H, U, n_max, seed, tv),
-    verify_ccpos=lambda ctx, l, H_s, U_s, W, WP, seed, tv: ccpos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, H_s, U_s, W, WP, seed, tv),
-    verify_pos=lambda ctx, l, H, U, W, WP, seed, tv, with_arrays: pos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, W, WP, H, U, seed, tv, with_arrays),
-    verify_dec=lambda ctx, W, data, tv: dec_core(ctx.nizkp, ctx.grp, ctx.params, ctx.pkey, W, data, tv),
+    verify_ccpos=lambda ctx, l, H_s, U_s, W, WP, seed, tv: ccpos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, H_s, U_s, W, WP, seed, tv, ctx.keywidth),
+    verify_pos=lambda ctx, l, H, U, W, WP, seed, tv, with_arrays: pos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, W, WP, H, U, seed, tv, with_arrays, ctx.keywidth),
+    verify_dec=lambda ctx, W, data, tv: dec_core(ctx.nizkp, ctx.grp, ctx.params, ctx.pkey, W, data, tv, ctx.keywidth),
     hash_seed=_gpu_hash_seed,
     show=lambda ctx, a: "(" + ", ".join(_arr(c) for c in a) + ")" if isinstance(a, list) else _arr(a),
     free=_gpu_free)
@@ -1343,11 +1458,16 @@ _FROM_FILE, _FROM_GENERATORS = object(), object()
 
 
 def run_session(nizkp: str, grp, params: dict, expected: SessionParams, eng: SessionEngines,
-                vectors: Optional[dict] = None, with_arrays: bool = False, stats: Optional[dict] = None) -> SessionVerdict:
+                vectors: Optional[dict] = None, with_arrays: bool = False, stats: Optional[dict] = None,
+                keywidth: Optional[int] = None) -> SessionVerdict:
     """The control flow of MixNetElGamalVerifyFiatShamirSession.verify (:1318-1670) over the engines `eng`: session files, keys,
     generators once, the chain of parties with its replacement rules, the decryption of the list the chain ends in.  See
-    verify_session.  `stats` (a dict) receives which seeds were hashed ahead, used and discarded."""
+    verify_session.  `stats` (a dict) receives which seeds were hashed ahead, used and discarded.  `keywidth`: the width of the
+    public key; None takes params["keywidth"], 1 when params has none."""
     tv = vectors if vectors is not None else {}
+    kw = int(params.get("keywidth", 1)) if keywidth is None else int(keywidth)
+    if kw < 1:
+        raise SessionFormatError("Key width is not positive!")
     k, threshold = int(params["k"]), int(params["threshold"])
     tv["par.k"], tv["par.lambda"] = str(k), str(threshold)                         # :1322-1331
     tv["par.n_e"], tv["par.n_r"], tv["par.n_v"] = str(int(params["ebitlenro"])), str(int(params["rbitlen"])), str(int(params["vbitlenro"]))
@@ -1356,27 +1476,27 @@ def run_session(nizkp: str, grp, params: dict, expected: SessionParams, eng: Ses
     sp = determine_session_params(nizkp, params, expected, tv)                     # :1338
     params = dict(params, auxsid=sp.auxsid)
     width = sp.width
-    ctx = SimpleNamespace(nizkp=nizkp, grp=grp, params=params, pkey=None)
+    ctx = SimpleNamespace(nizkp=nizkp, grp=grp, params=params, pkey=None, keywidth=kw)
     # ---- readFullPKey :194-234
     if not os.path.exists(pk_file(nizkp)):
         raise SessionFormatError("Joint public key file %s can not be found!" % pk_file(nizkp))
     pk = eng.read_pkey(ctx, pk_file(nizkp))
     if pk is None:
         raise SessionFormatError("Could not read full El Gamal public key from file! (%s)" % pk_file(nizkp))
-    tv["bas.pk"] = "(" + _hex(pk[0]) + ", " + _hex(pk[1]) + ")"
-    if pk[0] != grp.g:
+    tv["bas.pk"] = "(" + _hexk(pk[0], kw) + ", " + _hexk(pk[1], kw) + ")"
+    if pk[0] != (grp.g if kw == 1 else (grp.g,) * kw):                             # plainPGroup.getg() :229
         raise SessionFormatError("Basic public key is not the standard generator!")
     if width > 0:
-        ctx.pkey = [pk[0]] * width + [pk[1]] * width                               # ProtocolElGamal.getWidePublicKey
+        ctx.pkey = list(_rows(pk[0], kw)) * width + list(_rows(pk[1], kw)) * width     # ProtocolElGamal.getWidePublicKey
     # ---- readMixServerPKeys :239-287
     if sp.dec:
         poly = eng.read_poly(ctx, poly_file(nizkp), threshold)
         if poly is None:
             raise SessionFormatError("Unable to read polynomial in exponent from file! (%s)" % poly_file(nizkp))
-        ys = [None] + [eval_polynomial_in_exponent(grp, poly, l) for l in range(1, k + 1)]
+        ys = [None] + [eval_keys(grp, poly, l, kw) for l in range(1, k + 1)]
         if pk[1] != poly[0]:
             raise SessionFormatError("Mismatching public keys!")
-        tv["bas.y_l"] = "(" + ",".join(_hex(ys[l]) for l in range(1, threshold + 1)) + ")"
+        tv["bas.y_l"] = "(" + ",".join(_hexk(ys[l], kw) for l in range(1, threshold + 1)) + ")"
     # ---- the global prefix :158-189, :1351
     tv["par.sid"] = params["sid"]
     rho = global_prefix(params)
@@ -1419,7 +1539,7 @@ def run_session(nizkp: str, grp, params: dict, expected: SessionParams, eng: Ses
         env = os.environ.get("VMN_SESSION_HASH_AHEAD", "1")
         ahead = _SeedsAhead(env != "0", stats)
         g_tree = grp.element_tree(grp.g)
-        pk_tree = fs.product_element_tree(grp, ctx.pkey) if ctx.pkey else None
+        pk_tree = fs.product_element_tree(grp, ctx.pkey, kw) if ctx.pkey else None
         posc_active = lambda l: os.path.exists(pc_file(nizkp, l))                  # :958-962
         ccpos_active = lambda l: os.path.exists(ccposc_file(nizkp, l)) or os.path.exists(posc_file(nizkp, l))      # :972-976
         is_active = lambda l: (sp.posc and precomp and not sp.ccpos and posc_active(l)) or ccpos_active(l)
@@ -1528,7 +1648,7 @@ def run_session(nizkp: str, grp, params: dict, expected: SessionParams, eng: Ses
 
 
 def verify_session(nizkp: str, grp, params: dict, expected: SessionParams = SessionParams(), vectors: Optional[dict] = None,
-                   with_arrays: bool = False) -> SessionVerdict:
+                   with_arrays: bool = False, keywidth: Optional[int] = None) -> SessionVerdict:
     """What `vmnv` does with a proof directory (MixNetElGamalVerifyFiatShamirSession.verify :1318-1670), on the GPU:
     the session files (version, type, auxsid, width, proofs/activethreshold, proofs/maxciph), the keys (FullPublicKey.bt =
     (g, y) at width 1, widened here; with a decryption the polynomial in the exponent, whose element 0 is y), the generators
@@ -1549,14 +1669,19 @@ def verify_session(nizkp: str, grp, params: dict, expected: SessionParams = Sess
     `vectors` receives, in the reference's names: par.k, par.lambda (the threshold), par.lambda.active (the active threshold,
     which the reference prints under par.lambda a second time, :498), par.n_e, par.n_r, par.n_v, par.s_PRG, par.s_Gq, par.s_H,
     par.version, par.omega, par.N_0, par.sid, bas.pk, bas.y_l, der.rho, Dec.*; with `with_arrays` bas.h and bas.L_0; and
-    vectors["party"][l] = the PoS.* / PoSC.* / CCPoS.* vectors of party l (with `with_arrays` also u and bas.L_l)."""
-    return run_session(nizkp, grp, params, expected, GPU_ENGINES, vectors, with_arrays)
+    vectors["party"][l] = the PoS.* / PoSC.* / CCPoS.* vectors of party l (with `with_arrays` also u and bas.L_l).
+
+    Under a public key of width kappa (`keywidth`, by default params["keywidth"], 1 when absent) FullPublicKey.bt is an element
+    of getCiphPGroup(G^kappa, 1) whose first half must be (g, .., g) (:205-231), the coefficients of the polynomial lie in
+    G^kappa, the lists have 2 kappa width arrays, and bas.pk, bas.y_l, Dec.y_l show an element of G^kappa as the tuple of its
+    rows; the files are nested as the head of this module says."""
+    return run_session(nizkp, grp, params, expected, GPU_ENGINES, vectors, with_arrays, keywidth=keywidth)
 
 
 # ---- the writer: all k parties of a session -----------------------------------------------------------------------------------------
 def write_session(nizkp: str, grp, params: dict, session_type: str, W: Sequence, y, rand, k: int, threshold: int,
                   active: Optional[int] = None, n0: int = 0, failing=(), poly: Optional[Sequence] = None,
-                  shares: Optional[Sequence] = None, writers=None):
+                  shares: Optional[Sequence] = None, writers=None, keywidth: int = 1):
     """Every party of a session of `session_type` (mixing / shuffling / decryption) on the list W (2 * width component arrays)
     under the key (g, y), y = poly[0]: write_inputs, then for the active parties l = 1 .. `active` (default: threshold)
     write_shuffle, or with n0 > 0 write_precomputation for N_0 = n0 and write_committed_shuffle, then write_decryption with `poly`
@@ -1575,7 +1700,12 @@ def write_session(nizkp: str, grp, params: dict, session_type: str, W: Sequence,
 
     `failing`: parties that publish an invalid proof -- the party's honest commitment with the reply of a second, unrelated run
     on the same input.  The honest parties then go on as ShufflerElGamalSession.java:317-329: the party's output is replaced by
-    its input (also in the file they keep for the verifier) and the next party shuffles that."""
+    its input (also in the file they keep for the verifier) and the next party shuffles that.
+
+    `keywidth` = kappa > 1: W has 2 kappa width arrays, `y`, every coefficient of `poly` (a polynomial over Z_q^kappa in the
+    exponent, y = poly[0]) and every share are kappa-tuples; FullPublicKey.bt is (g, .., g, y_0, .., y_(kappa-1)), the width file
+    holds omega, params.json gains "keywidth" and every writer is handed keywidth=kappa.  With kappa = 1 nothing is handed on and
+    params.json has no such entry: the directory is byte for byte the one written without the parameter."""
     wr = writers if writers is not None else SimpleNamespace(
         write_inputs=write_inputs, write_shuffle=write_shuffle, write_precomputation=write_precomputation,
         write_committed_shuffle=write_committed_shuffle, write_decryption=write_decryption)
@@ -1584,12 +1714,18 @@ def write_session(nizkp: str, grp, params: dict, session_type: str, W: Sequence,
     active = threshold if active is None else active
     if not threshold <= active <= k:
         raise ValueError("threshold <= active <= k")
-    width = len(W) // 2
+    if keywidth < 1 or len(W) % (2 * keywidth):
+        raise ValueError("a list under a key of width kappa has 2 * kappa * width component arrays")
+    width = len(W) // 2 // keywidth
     params = dict(params, k=k, threshold=threshold, width=width, N_0=n0)
+    keyed = {}
+    if keywidth > 1:
+        params["keywidth"] = keywidth
+        keyed["keywidth"] = keywidth
     g = grp.g
-    wide = [g] * width + [y] * width
+    wide = [g] * (keywidth * width) + list(_rows(y, keywidth)) * width
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
-    wr.write_inputs(nizkp, grp, params, [g, y], W)
+    wr.write_inputs(nizkp, grp, params, [g] * keywidth + list(_rows(y, keywidth)), W, **keyed)
     write_string(version_file(nizkp), params["version"])
     write_string(auxsid_file(nizkp), params["auxsid"])
     write_int(width_file(nizkp), width)
@@ -1600,13 +1736,13 @@ def write_session(nizkp: str, grp, params: dict, session_type: str, W: Sequence,
             write_int(mc_file(nizkp), n0)
         pre, H = {}, None
         for l in range(1, active + 1) if n0 else ():
-            pre[l] = wr.write_precomputation(nizkp, l, grp, params, n0, rand, H)
+            pre[l] = wr.write_precomputation(nizkp, l, grp, params, n0, rand, H, **keyed)
             H = pre[l][3]
 
         def play(where, l, inp, out_file, secrets):
             if n0:
-                return wr.write_committed_shuffle(where, l, grp, params, wide, inp, rand, *secrets, out_file=out_file)
-            return wr.write_shuffle(where, l, grp, params, wide, inp, rand, out_file=out_file)
+                return wr.write_committed_shuffle(where, l, grp, params, wide, inp, rand, *secrets, out_file=out_file, **keyed)
+            return wr.write_shuffle(where, l, grp, params, wide, inp, rand, out_file=out_file, **keyed)
         for l in range(1, active + 1):
             out_file = ls_file(nizkp) if n0 and l == active else l_file(nizkp, l)
             out = play(nizkp, l, last, out_file, pre.get(l))
@@ -1614,7 +1750,7 @@ def write_session(nizkp: str, grp, params: dict, session_type: str, W: Sequence,
                 with tempfile.TemporaryDirectory(dir=nizkp) as other:
                     os.makedirs(_p(other, "proofs"))
                     shutil.copyfile(l_file(nizkp, l - 1), l_file(other, l - 1))
-                    secrets = wr.write_precomputation(other, l, grp, params, n0, rand, H) if n0 else None
+                    secrets = wr.write_precomputation(other, l, grp, params, n0, rand, H, **keyed) if n0 else None
                     play(other, l, last, l_file(other, l), secrets)
                     reply = ccposr_file if n0 else posr_file
                     shutil.copyfile(reply(other, l), reply(nizkp, l))
@@ -1631,5 +1767,5 @@ def write_session(nizkp: str, grp, params: dict, session_type: str, W: Sequence,
             os.replace(ls_file(nizkp), l_file(nizkp, active))
         else:
             write_string(type_file(nizkp), DECRYPT_TYPE)
-        plain = wr.write_decryption(nizkp, grp, params, wide, last, poly, shares, rand, k, threshold)
+        plain = wr.write_decryption(nizkp, grp, params, wide, last, poly, shares, rand, k, threshold, **keyed)
     return params, plain
