@@ -110,6 +110,76 @@ def nested_tree(trees: Sequence[bytes], keywidth: int = 1) -> bytes:
     return inner[0] if omega == 1 else _hdr(0, omega) + b"".join(inner)
 
 
+class NoSuchTree(Exception):
+    """The bytes under a ``Cursor`` are not the tree its caller asks for: a wrong tag, a wrong count, a short buffer, bytes
+    behind the end.  Private to the readers: each catches it at its entry point and answers None."""
+
+
+class Cursor:
+    """A position in the bytes of a byte tree, moved by the one who knows which tree to expect: THE reader of the proof
+    directory's framing (``_hdr``, ``leaf`` and ``nested_tree`` write it).  Every operation raises ``NoSuchTree`` -- never
+    IndexError -- where the bytes are not what it was asked for."""
+
+    def __init__(self, buf: bytes, pos: int = 0):
+        self.buf, self.pos = buf, pos
+
+    def _header(self, tag: int, move: bool = True) -> int:
+        head = bytes(self.buf[self.pos:self.pos + 5])
+        if len(head) != 5 or head[0] != tag:
+            raise NoSuchTree()
+        if move:
+            self.pos += 5
+        return int.from_bytes(head[1:], "big")
+
+    def node(self, count: Optional[int] = None) -> int:
+        """Step into a node (of ``count`` children, when given); its child count."""
+        if count is not None and self._header(0, False) != count:
+            raise NoSuchTree()
+        return self._header(0)
+
+    def children(self) -> int:
+        """The child count of the node here, without stepping into it (an array tree says its own size)."""
+        return self._header(0, False)
+
+    def leaf(self, length: int) -> bytes:
+        """The data of a leaf of ``length`` bytes."""
+        if self._header(1, False) != length or len(self.buf) < self.pos + 5 + length:
+            raise NoSuchTree()
+        self.pos += 5
+        return self.take(length)
+
+    def take(self, size: int) -> bytes:
+        """The next ``size`` bytes, a subtree whose size the caller knows, for the caller's own reader."""
+        if size < 0 or len(self.buf) < self.pos + size:
+            raise NoSuchTree()
+        self.pos += size
+        return self.buf[self.pos - size:self.pos]
+
+    def item(self, read):
+        """The value of ``read(buf, pos) -> (value, next position) | None`` (``group.element_from_tree``) here."""
+        got = read(self.buf, self.pos)
+        if got is None:
+            raise NoSuchTree()
+        self.pos = got[1]
+        return got[0]
+
+    def nested(self, width: int, keywidth: int, item) -> list:
+        """The kappa * omega values of ``nested_tree``, each read by ``item(cursor)``, in flat order."""
+        if width > 1:
+            self.node(width)
+        values = []
+        for _ in range(width):
+            if keywidth > 1:
+                self.node(keywidth)
+            values += [item(self) for _ in range(keywidth)]
+        return values
+
+    def end(self) -> None:
+        """The tree fills its buffer."""
+        if self.pos != len(self.buf):
+            raise NoSuchTree()
+
+
 def product_element_tree(group, els: Sequence, keywidth: int = 1) -> bytes:
     """``element_tree`` for any kind of group: the same shapes (one element alone: its own tree; node(a, b) at width 1;
     node(node(w trees), node(w trees)) otherwise) over the trees of the single elements, which are leaves for a modular group

@@ -178,30 +178,7 @@ def read_plaintexts(grp, path: str, width: int, keywidth: int = 1) -> Optional[L
     buf = proofdir._read_file(path)
     if buf is None:
         return None
-    buf = bytes(buf)
-    if width == 1 and keywidth == 1:
-        parts = [buf]
-    else:
-        def array(b, at):                                    # every array: a node of n leaves of the group's width
-            if len(b) < at + 5 or b[at] != 0:
-                return None
-            size = 5 + int.from_bytes(b[at + 1:at + 5], "big") * (5 + grp.elem_bytes)
-            return b[at:at + size], at + size
-        got = proofdir._nested_reader(buf, 0, width, keywidth, array)
-        if got is None or got[1] != len(buf):
-            return None
-        parts = got[0]
-    comps = []
-    try:
-        for part in parts:
-            comps.append(grp.toElementArrayFromByteTree(part))
-    except (ValueError, RuntimeError):
-        _free(comps)
-        return None
-    if len({a.size() for a in comps}) != 1:
-        _free(comps)
-        return None
-    return _members_or_none(comps)
+    return _members_or_none(proofdir.read_array_nests(grp, bytes(buf), 1, width, keywidth))
 
 
 def write_plaintexts(path: str, comps: Sequence[PGroupElementArray], fmt: str = "json", keywidth: int = 1) -> None:

@@ -93,18 +93,73 @@ def global_prefix(params: dict) -> bytes:
     return hashlib.new(_hashname(params), fs._hdr(0, len(parts)) + b"".join(parts)).digest()
 
 
+_HASHES = {"SHA-256": "sha256", "SHA-384": "sha384", "SHA-512": "sha512"}
+
+
 def _hashname(params: dict) -> str:
-    return {"SHA-256": "sha256", "SHA-384": "sha384", "SHA-512": "sha512"}[params.get("rohash_name", "SHA-256")]
+    return _HASHES[params.get("rohash_name", "SHA-256")]
+
+
+@dataclasses.dataclass(frozen=True)
+class _Derived:
+    """What the writers and verifiers below take from params.json: the bit lengths n_v, n_e, n_r, the random oracle's hash and
+    its digest length in bits (the length of a shuffle's seed), rho with its challenger, and 8 * prg.minNoSeedBytes() -- the
+    digest length of the PRG's hash function (PRGHeuristic), the length of the decryption's seed."""
+    NV: int
+    NE: int
+    NR: int
+    hashname: str
+    bits: int
+    rho: bytes
+    chal: fs.Challenger
+    prg: str
+
+    @classmethod
+    def of(cls, params: dict, rho: Optional[bytes] = None) -> "_Derived":
+        hn = _hashname(params)
+        rho = global_prefix(params) if rho is None else rho
+        return cls(int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"]), hn, 8 * hashlib.new(hn).digest_size,
+                   rho, fs.Challenger(rho, hn), params.get("prg", "SHA-256"))
+
+    @property
+    def prg_bits(self) -> int:
+        return 8 * hashlib.new(_HASHES[self.prg]).digest_size
+
+    def seed(self, parts, bits: Optional[int] = None) -> bytes:
+        """RO(rho || node(parts...)) of `bits` bits (default: a shuffle's): `parts` are the node's header with its first child,
+        then the other children, hashed in order -- byte strings, or paths of files whose bytes are streamed in."""
+        bits = self.bits if bits is None else bits
+        d = self.chal.start(bits)
+        for part in parts:
+            if isinstance(part, str):
+                with open(part, "rb") as f:
+                    d.update(f.read())
+            else:
+                d.update(part)
+        return self.chal.finish(d, bits)
+
+    def challenge(self, seed: bytes, com_bt: bytes) -> int:
+        """v = RO(rho || node(leaf(seed), commitment)) of n_v bits as a positive integer (PoSTW.java:141-149)."""
+        return int.from_bytes(self.chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, self.NV), "big")
+
+
+def posc_seed_parts(g_tree: bytes, H_bt, u_bt) -> list:
+    """node(g, h, u): the seed of a proof of a shuffle of commitments (PoSCTW.java:73-134; verifyPoSC :652-703)."""
+    return [fs._hdr(0, 3) + g_tree, H_bt, u_bt]
+
+
+def shuffle_seed_parts(g_tree: bytes, H_bt, u_bt, pk_tree: bytes, L, LP) -> list:
+    """node(g, h, u, pk, L, L'): the seed of a proof of a shuffle, plain (PoSTW.java:114-129; verifyPoS :869-879) or
+    commitment-consistent (CCPoSW.java:75-158).  A list may be given as the path of its file: the file IS its tree."""
+    return [fs._hdr(0, 6) + g_tree, H_bt, u_bt, pk_tree, L, LP]
 
 
 def derive_generators(grp, params: dict, rho: bytes, n: int) -> PGroupElementArray:
     """``IndependentGeneratorsRO("generators", H, rho, n_r).generate(pGroup, n)`` (distr/IndependentGeneratorsRO.java:110-130;
     called at MixNetElGamalVerifyFiatShamirSession.java:557-566): seed = RO(rho || leaf("generators")), then
     pGroup.randomElementArray(n, PRG(seed), n_r) on the GPU (vmn_garray_from_prg)."""
-    hn = _hashname(params)
-    seed_bits = 8 * hashlib.new(hn).digest_size
-    seed = fs.Challenger(rho, hn).challenge(fs.leaf(b"generators"), seed_bits)
-    return grp.elementArrayFromPRG(seed, n, int(params["rbitlen"]))
+    D = _Derived.of(params, rho)
+    return grp.elementArrayFromPRG(D.seed([fs.leaf(b"generators")]), n, D.NR)
 
 
 # ---- arrays as files ------------------------------------------------------------------------------------------------------
@@ -122,27 +177,60 @@ def _nested_pieces(arrays: Sequence[PGroupElementArray], keywidth: int):
             yield a.toByteTree()
 
 
+def _list_pieces(comps: Sequence[PGroupElementArray], keywidth: int):
+    """The bytes of a list file, piece by piece: node(u-part, v-part), each part nested."""
+    half = len(comps) // 2
+    yield fs._hdr(0, 2)
+    for part in (comps[:half], comps[half:]):
+        yield from _nested_pieces(part, keywidth)
+
+
 def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray], keywidth: int = 1) -> None:
     """A PPGroupElementArray of width w as 2w component arrays: node(u-part, v-part), a part being the array's own tree
     at width 1 and node(w array trees) otherwise; under a key of width kappa 2 kappa w arrays, a part
     nested once more (the head of this file)."""
-    half = len(comps) // 2
     with open(path, "wb") as f:
-        f.write(fs._hdr(0, 2))
-        for part in (comps[:half], comps[half:]):
-            for piece in _nested_pieces(part, keywidth):
-                f.write(piece)
+        for piece in _list_pieces(comps, keywidth):
+            f.write(piece)
 
 
 def _ciphertexts_tree(comps: Sequence[PGroupElementArray], keywidth: int = 1) -> bytes:
     """The bytes write_ciphertexts puts into a list file."""
-    half = len(comps) // 2
-    return fs._hdr(0, 2) + b"".join(piece for part in (comps[:half], comps[half:]) for piece in _nested_pieces(part, keywidth))
+    return b"".join(_list_pieces(comps, keywidth))
+
+
+def read_array_nests(grp, buf: bytes, nests: int, width: int, keywidth: int = 1, expected_n: int = 0):
+    """THE reader of the arrays a file holds: `nests` nests (fs.nested_tree) of kappa * omega array trees each, under node(nests)
+    where there is more than one, filling the whole of buf.  Every array has n elements: `expected_n`, or when that is 0 the
+    count in the first array's own header; its bytes are cut out by grp.array_tree_size(n) and imported (range-checked) on the
+    GPU.  No membership check: that is the caller's choice.  None when buf is no such tree or an import fails; the arrays
+    imported until then are freed."""
+    cur, comps, n = fs.Cursor(buf), [], expected_n or None
+
+    def array(c):
+        nonlocal n
+        n = c.children() if n is None else n
+        if c.children() != n:
+            raise fs.NoSuchTree()
+        comps.append(grp.toElementArrayFromByteTree(c.take(grp.array_tree_size(n)), n))
+        return comps[-1]
+    try:
+        if nests > 1:
+            cur.node(nests)
+        for _ in range(nests):
+            cur.nested(width, keywidth, array)
+        cur.end()
+        return comps
+    except (fs.NoSuchTree, ValueError, native.VmnError):
+        for a in comps:
+            a.free()
+        return None
 
 
 def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
-    """The 2w component arrays (2 kappa w under a key of width kappa) of a ciphertext list file, parsed (range + membership) on
-    the GPU; None when the file is not such a list (the verifier then fails the party, :1446-1460)."""
+    """The 2w component arrays (2 kappa w under a key of width kappa) of a ciphertext list file, parsed (framing + range) on the
+    GPU; None when the file is not such a list (the verifier then fails the party, :1446-1460).  Membership in the group is not
+    checked here; interface.read_ciphertexts adds that check (_members_or_none)."""
     buf = _read_file(path)
     if buf is None:
         return None
@@ -151,38 +239,7 @@ def read_ciphertexts(grp, path: str, width: int, expected_n: int = 0, keywidth: 
 
 def parse_ciphertexts(grp, buf: bytes, width: int, expected_n: int = 0, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
     """read_ciphertexts for a list file whose bytes the caller already holds."""
-    pos = 0
-
-    def header(tag, count=None):
-        nonlocal pos
-        if len(buf) < pos + 5 or buf[pos] != tag:
-            raise ValueError("byte tree framing")
-        c = int.from_bytes(buf[pos + 1:pos + 5], "big")
-        if count is not None and c != count:
-            raise ValueError("byte tree child count")
-        pos += 5
-        return c
-    try:
-        header(0, 2)
-        comps = []
-        for _ in range(2):
-            if width > 1:
-                header(0, width)
-            for _ in range(width):
-                if keywidth > 1:
-                    header(0, keywidth)
-                for _ in range(keywidth):
-                    n = int.from_bytes(buf[pos + 1:pos + 5], "big")
-                    if len(buf) < pos + 5 or buf[pos] != 0 or (expected_n and n != expected_n):
-                        raise ValueError("array node")
-                    size = grp.array_tree_size(n)
-                    comps.append(grp.toElementArrayFromByteTree(buf[pos:pos + size], n))
-                    pos += size
-        if pos != len(buf) or len({c.size() for c in comps}) != 1:
-            raise ValueError("trailing bytes")
-        return comps
-    except (ValueError, native.VmnError):
-        return None
+    return read_array_nests(grp, buf, 2, width, keywidth, expected_n)
 
 
 def _read_file(path: str) -> Optional[bytes]:
@@ -192,6 +249,13 @@ def _read_file(path: str) -> Optional[bytes]:
             return f.read()
     except OSError:
         return None
+
+
+def _write(path: str, data: bytes) -> bytes:
+    """A file of the directory, written; hands the bytes back."""
+    with open(path, "wb") as f:
+        f.write(data)
+    return data
 
 
 def _hex(x) -> str:
@@ -204,13 +268,18 @@ def _hex(x) -> str:
     return format(int(x), "x")
 
 
+def _hexes(xs) -> str:
+    """A tuple of elements as text: "(_hex(x_0), _hex(x_1), ..)"."""
+    return "(" + ", ".join(_hex(x) for x in xs) + ")"
+
+
 def _arr(a) -> str:
-    return "(" + ", ".join(_hex(x) for x in a.toInts()) + ")"
+    return _hexes(a.toInts())
 
 
 def _hexk(x, keywidth: int = 1) -> str:
     """_hex for an element of G^kappa resp. Z_q^kappa given as its kappa rows: "(row_0, .., row_(kappa-1))", the row itself at kappa = 1."""
-    return _hex(x) if keywidth == 1 else "(" + ", ".join(_hex(e) for e in x) + ")"
+    return _hex(x) if keywidth == 1 else _hexes(x)
 
 
 # ---- prover: PoSTW.prove with nizkp != null ----------------------------------------------------------------------------
@@ -222,44 +291,32 @@ def write_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W: Sequ
     l_file(nizkp, l) (a session's last list, write_session)."""
     out_file = out_file or l_file(nizkp, l)
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
+    D = _Derived.of(params)
     n, width = W[0].size(), len(W) // 2
-    hn = _hashname(params)
-    rho = global_prefix(params)
-    chal = fs.Challenger(rho, hn)
     own_h = H is None
     if own_h:
-        H = derive_generators(grp, params, rho, n)
+        H = derive_generators(grp, params, D.rho, n)
     g = grp.g
     pi = rand.permutation(n)
-    S = [native.random_ring_array_native(grp, rand, n, NR) for _ in range(width)]
-    prover = native.PoSBasicTW(grp, NV, NE, NR, rand=rand)
+    S = [native.random_ring_array_native(grp, rand, n, D.NR) for _ in range(width)]
+    prover = native.PoSBasicTW(grp, D.NV, D.NE, D.NR, rand=rand)
     prover.precompute(g, H, pi)
     WP = native.reencrypt_native(grp, pkey, W, S, pi)
-    write_ciphertexts(out_file, WP, keywidth)
+    write_ciphertexts(out_file, WP, keywidth)                                    # (before the seed, which is hashed over the file)
     prover.setInstance(pkey, W, WP, S)
-    u_bt = prover.u.toByteTree()
-    with open(pc_file(nizkp, l), "wb") as f:                                     # "PermutationCommitment" :107-112
-        f.write(u_bt)
-    d = chal.start(8 * hashlib.new(hn).digest_size)                            # the seed of the batching vector :114-129
-    d.update(fs._hdr(0, 6) + grp.element_tree(g))
-    d.update(H.toByteTree())
-    d.update(u_bt)
-    d.update(fs.product_element_tree(grp, pkey, keywidth))
-    for path in (l_file(nizkp, l - 1), out_file):
-        with open(path, "rb") as f:
-            d.update(f.read())
-    seed = chal.finish(d, 8 * hashlib.new(hn).digest_size)
-    prover.setBatchVectorSeed(seed)
-    com = prover.commit()
-    com_bt = _keyed(com.native, keywidth).toByteTree()
-    with open(posc_file(nizkp, l), "wb") as f:                                   # "Commitment" :131-139
-        f.write(com_bt)
-    v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")     # :141-149
-    rep = prover.reply(v)
-    with open(posr_file(nizkp, l), "wb") as f:                                   # "Reply" :151-159
-        f.write(_keyed(rep.native, keywidth).toByteTree())
-    com = rep = None
+    u_bt = _write(pc_file(nizkp, l), prover.u.toByteTree())                      # "PermutationCommitment" :107-112
+    box = {}
+
+    def commit(seed):                                                            # the seed of the batching vector :114-129
+        prover.setBatchVectorSeed(seed)
+        box["com"] = prover.commit()
+        return _write(posc_file(nizkp, l), _keyed(box["com"].native, keywidth).toByteTree())      # "Commitment" :131-139
+    parts = shuffle_seed_parts(grp.element_tree(g), H.toByteTree(), u_bt, fs.product_element_tree(grp, pkey, keywidth),
+                               l_file(nizkp, l - 1), out_file)
+    rep = prover.reply(_seed_and_challenge(D, parts, commit))                    # :141-149
+    _write(posr_file(nizkp, l), _keyed(rep.native, keywidth).toByteTree())       # "Reply" :151-159
+    box.clear()
+    rep = None
     prover.free()
     for a in S:
         a.free()
@@ -279,8 +336,7 @@ def write_inputs(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGro
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
     with open(_p(nizkp, PARAMS), "w") as f:
         json.dump(params, f, indent=1)
-    with open(pk_file(nizkp), "wb") as f:
-        f.write(fs.product_element_tree(grp, pkey, keywidth))
+    _write(pk_file(nizkp), fs.product_element_tree(grp, pkey, keywidth))
     write_ciphertexts(l_file(nizkp, 0), W, keywidth)
 
 
@@ -293,10 +349,8 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     and the equations then fail)."""
     tv = vectors if vectors is not None else {}
     width = len(pkey) // 2 // keywidth
-    hn = _hashname(params)
-    rho = global_prefix(params)
-    tv["der.rho"] = rho.hex()                                                  # :188
-    chal = fs.Challenger(rho, hn)
+    D = _Derived.of(params)
+    tv["der.rho"] = D.rho.hex()                                                # :188
     W = read_ciphertexts(grp, l_file(nizkp, l - 1), width, 0, keywidth)
     if W is None:
         return False
@@ -304,24 +358,15 @@ def verify_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequence, vector
     WP = read_ciphertexts(grp, l_file(nizkp, l), width, n, keywidth)
     if WP is None:
         return False
-    H = derive_generators(grp, params, rho, n)                                 # :557-566
+    H = derive_generators(grp, params, D.rho, n)                               # :557-566
     if with_arrays:
         tv["bas.h"] = _arr(H)
     u_bt = _read_file(pc_file(nizkp, l))                                       # :861-866
     U = parse_commitment(grp, u_bt, n)
     if U is None:
         return False
-
-    def seed():                                                                # :869-879
-        d = chal.start(8 * hashlib.new(hn).digest_size)
-        d.update(fs._hdr(0, 6) + grp.element_tree(grp.g))
-        d.update(H.toByteTree())
-        d.update(u_bt)
-        d.update(fs.product_element_tree(grp, pkey, keywidth))
-        for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
-            with open(path, "rb") as f:
-                d.update(f.read())
-        return chal.finish(d, 8 * hashlib.new(hn).digest_size)
+    seed = lambda: D.seed(shuffle_seed_parts(grp.element_tree(grp.g), H.toByteTree(), u_bt,                  # :869-879
+                                             fs.product_element_tree(grp, pkey, keywidth), l_file(nizkp, l - 1), l_file(nizkp, l)))
     verdict = pos_core(nizkp, l, grp, params, pkey, W, WP, H, U, seed, tv, with_arrays, keywidth)
     for a in W + WP + [H, U]:
         a.free()
@@ -347,51 +392,44 @@ def pos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, W, WP, H, U,
     """verifyPoS on loaded inputs: the lists W and WP, the generators H and the permutation commitment U as device arrays,
     `seed()` -> the seed of the batching vector (the one value that depends on the lists' and the generators' BYTES).  Reads
     the party's commitment and reply files; frees nothing it was given."""
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
+    D = _Derived.of(params)
     n, width = W[0].size(), len(pkey) // 2
-    chal = fs.Challenger(global_prefix(params), _hashname(params))
-    g = grp.g
-    V = native.PoSBasicTW(grp, NV, NE, NR)
+    V = native.PoSBasicTW(grp, D.NV, D.NE, D.NR)
     try:
-        return _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays, keywidth)
+        V.precompute(grp.g, H)                                                     # :857
+        V.setInstance(pkey, W, WP)
+        V.setPermutationCommitment(U)
+        seed = seed()
+        tv["PoS.s"] = seed.hex()                                                   # :881
+        V.setBatchVectorSeed(seed)                                                 # :883
+        V.computeAF()                                                              # :886
+        tv["PoS.A"], tv["PoS.F"] = _hex(V.getA()), _hexes(V.getF())                # :888-889
+        com_bt = _read_file(posc_file(nizkp, l))                                   # :892-895
+        com = V.readCommitment(com_bt, n, width, keywidth) if com_bt is not None else None
+        if com is None:
+            return False
+        V.setCommitment(com)
+        if with_arrays:                                                            # :897-902
+            tv["PoS.B"], tv["PoS.Bp"] = _arr(com.item(0)), _arr(com.item(2))
+        tv["PoS.Ap"], tv["PoS.Cp"], tv["PoS.Dp"] = (_hex(com.item(k)[0]) for k in (1, 3, 4))
+        tv["PoS.Fp"] = _hexes(com.item(5))
+        vch = D.challenge(seed, com_bt)                                            # :905-913
+        tv["PoS.v"] = format(vch, "x")                                             # :915
+        V.setChallenge(vch)
+        rep_bt = _read_file(posr_file(nizkp, l))                                   # :921-925
+        rep = V.readReply(rep_bt, n, width, keywidth) if rep_bt is not None else None
+        if rep is None:
+            return False
+        verdict = V.verify(rep)
+        tv["PoS.C"], tv["PoS.D"] = _hex(V.getC()), _hex(V.getD())                  # :927-928
+        tv["PoS.k_A"], tv["PoS.k_C"], tv["PoS.k_D"] = (_hex(rep.item(k)[0]) for k in (0, 2, 3))      # :930-934
+        tv["PoS.k_F"] = _hexes(rep.item(5))
+        if with_arrays:
+            tv["PoS.k_B"], tv["PoS.k_E"] = _arr(rep.item(1)), _arr(rep.item(4))
+        tv["verdicts(A,B,C,D,F)"] = str(V.verdicts)
+        return bool(verdict)
     finally:
         V.free()
-
-
-def _pos_core(V, nizkp, l, grp, pkey, n, width, chal, NV, g, W, WP, H, U, seed, tv, with_arrays, keywidth=1) -> bool:
-    V.precompute(g, H)                                                         # :857
-    V.setInstance(pkey, W, WP)
-    V.setPermutationCommitment(U)
-    seed = seed()
-    tv["PoS.s"] = seed.hex()                                                   # :881
-    V.setBatchVectorSeed(seed)                                                 # :883
-    V.computeAF()                                                              # :886
-    tv["PoS.A"] = _hex(V.getA())                                               # :888-889
-    tv["PoS.F"] = "(" + ", ".join(_hex(x) for x in V.getF()) + ")"
-    com_bt = _read_file(posc_file(nizkp, l))                                   # :892-895
-    com = V.readCommitment(com_bt, n, width, keywidth) if com_bt is not None else None
-    if com is None:
-        return False
-    V.setCommitment(com)
-    if with_arrays:                                                            # :897-902
-        tv["PoS.B"], tv["PoS.Bp"] = _arr(com.item(0)), _arr(com.item(2))
-    tv["PoS.Ap"], tv["PoS.Cp"], tv["PoS.Dp"] = (_hex(com.item(k)[0]) for k in (1, 3, 4))
-    tv["PoS.Fp"] = "(" + ", ".join(_hex(x) for x in com.item(5)) + ")"
-    vch = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")      # :905-913
-    tv["PoS.v"] = format(vch, "x")                                             # :915
-    V.setChallenge(vch)
-    rep_bt = _read_file(posr_file(nizkp, l))                                   # :921-925
-    rep = V.readReply(rep_bt, n, width, keywidth) if rep_bt is not None else None
-    if rep is None:
-        return False
-    verdict = V.verify(rep)
-    tv["PoS.C"], tv["PoS.D"] = _hex(V.getC()), _hex(V.getD())                  # :927-928
-    tv["PoS.k_A"], tv["PoS.k_C"], tv["PoS.k_D"] = (_hex(rep.item(k)[0]) for k in (0, 2, 3))      # :930-934
-    tv["PoS.k_F"] = "(" + ", ".join(_hex(x) for x in rep.item(5)) + ")"
-    if with_arrays:
-        tv["PoS.k_B"], tv["PoS.k_E"] = _arr(rep.item(1)), _arr(rep.item(4))
-    tv["verdicts(A,B,C,D,F)"] = str(V.verdicts)
-    return bool(verdict)
 
 
 # =============================================================================================================================
@@ -431,30 +469,28 @@ def _booleans_tree(flags) -> bytes:
     return fs.leaf(bytes(1 if f else 0 for f in flags))
 
 
-def _read_booleans(path: str, n: int):
-    with open(path, "rb") as f:
-        buf = f.read()
-    if len(buf) != 5 + n or buf[0] != 1 or int.from_bytes(buf[1:5], "big") != n or any(b > 1 for b in buf[5:]):
+def _parse_booleans(buf: Optional[bytes], n: int):
+    """The n flags of a boolean array's bytes; None when there are none or they are no such leaf."""
+    try:
+        if buf is None:
+            return None
+        cur = fs.Cursor(buf)
+        data = cur.leaf(n)
+        cur.end()
+        return None if any(b > 1 for b in data) else [b == 1 for b in data]
+    except fs.NoSuchTree:
         return None
-    return [b == 1 for b in buf[5:]]
 
 
-def _seed_and_challenge(chal, hn, head: bytes, parts, commit_fn, NV):
-    """The two random-oracle calls around a commitment: seed = RO(rho || node(parts...)); v = RO(rho || node(leaf(seed),
-    commitment)) as a positive integer.  `parts`: byte strings / file paths hashed in order after `head`."""
-    bits = 8 * hashlib.new(hn).digest_size
-    d = chal.start(bits)
-    d.update(head)
-    for part in parts:
-        if isinstance(part, str):
-            with open(part, "rb") as f:
-                d.update(f.read())
-        else:
-            d.update(part)
-    seed = chal.finish(d, bits)
-    com_bt = commit_fn(seed)
-    v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")
-    return seed, com_bt, v
+def _read_booleans(path: str, n: int):
+    return _parse_booleans(_read_file(path), n)
+
+
+def _seed_and_challenge(D: _Derived, parts, commit_fn) -> int:
+    """A prover's two random-oracle calls around its commitment: seed = D.seed(parts), commit_fn(seed) -> the bytes of the
+    commitment it publishes, v = D.challenge(seed, those bytes)."""
+    seed = D.seed(parts)
+    return D.challenge(seed, commit_fn(seed))
 
 
 def write_precomputation(nizkp: str, l: int, grp, params: dict, n_max: int, rand, H: Optional[PGroupElementArray] = None,
@@ -463,34 +499,24 @@ def write_precomputation(nizkp: str, l: int, grp, params: dict, n_max: int, rand
     commitments.  Returns the prover's secrets for the online phase: (pi, R, U, H).  Nothing here depends on `keywidth`: the
     commitment and its proof live in the atomic group (:652-703); the parameter is what write_session hands every writer."""
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
-    hn = _hashname(params)
-    rho = global_prefix(params)
-    chal = fs.Challenger(rho, hn)
+    D = _Derived.of(params)
     if H is None:
-        H = derive_generators(grp, params, rho, n_max)
+        H = derive_generators(grp, params, D.rho, n_max)
     g = grp.g
     pi = rand.permutation(n_max)
-    R = native.random_ring_array_native(grp, rand, n_max, NR)
+    R = native.random_ring_array_native(grp, rand, n_max, D.NR)
     U = native.permutation_commitment_native(grp, g, H, R, pi)
-    u_bt = U.toByteTree()
-    with open(pc_file(nizkp, l), "wb") as f:                                     # PermutationCommitment.java:364
-        f.write(u_bt)
-    P = native.PoSCBasicTW(grp, NV, NE, NR, rand=rand)                           # PoSCTW.prove :73-134
+    u_bt = _write(pc_file(nizkp, l), U.toByteTree())                             # PermutationCommitment.java:364
+    P = native.PoSCBasicTW(grp, D.NV, D.NE, D.NR, rand=rand)                     # PoSCTW.prove :73-134
     P.setInstance(g, H, U, R, pi)
     box = {}
 
     def commit(seed):
         P.setBatchVectorSeed(seed)
         box["com"] = P.commit()
-        bt = box["com"].native.toByteTree()
-        with open(poscc_file(nizkp, l), "wb") as f:
-            f.write(bt)
-        return bt
-    _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 3) + grp.element_tree(g), [H.toByteTree(), u_bt], commit, NV)
-    rep = P.reply(v)
-    with open(poscr_file(nizkp, l), "wb") as f:
-        f.write(rep.native.toByteTree())
+        return _write(poscc_file(nizkp, l), box["com"].native.toByteTree())
+    rep = P.reply(_seed_and_challenge(D, posc_seed_parts(grp.element_tree(g), H.toByteTree(), u_bt), commit))
+    _write(poscr_file(nizkp, l), rep.native.toByteTree())
     box.clear()
     rep = None
     P.free()
@@ -503,35 +529,27 @@ def write_committed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequenc
     (PermutationCommitment.java:390-471, keep list to its file), re-encrypt and permute (ShufflerElGamalSession.java:789-792),
     CCPoSW.prove (:75-158).  Returns w'.  `out_file`: where L_l goes instead of l_file(nizkp, l)."""
     out_file = out_file or l_file(nizkp, l)
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
+    D = _Derived.of(params)
     n, width = W[0].size(), len(W) // 2
-    hn = _hashname(params)
-    chal = fs.Challenger(global_prefix(params), hn)
     g = grp.g
     keep, pi_s = native.permutation_shrink_native(pi, n)
-    with open(kl_file(nizkp, l), "wb") as f:
-        f.write(_booleans_tree(keep))
+    _write(kl_file(nizkp, l), _booleans_tree(keep))
     U_s, R_s, H_s = U.extract(keep), R.copyOfRange(0, n), H.copyOfRange(0, n)
-    S = [native.random_ring_array_native(grp, rand, n, NR) for _ in range(width)]
+    S = [native.random_ring_array_native(grp, rand, n, D.NR) for _ in range(width)]
     WP = native.reencrypt_native(grp, pkey, W, S, pi_s)
     write_ciphertexts(out_file, WP, keywidth)
-    P = native.CCPoSBasicW(grp, NV, NE, NR, rand=rand)
+    P = native.CCPoSBasicW(grp, D.NV, D.NE, D.NR, rand=rand)
     P.setInstance(g, H_s, U_s, pkey, W, WP, R_s, pi_s, S)
     box = {}
 
     def commit(seed):
         P.setBatchVectorSeed(seed)
         box["com"] = P.commit()
-        bt = _keyed(box["com"].native, keywidth).toByteTree()
-        with open(ccposc_file(nizkp, l), "wb") as f:
-            f.write(bt)
-        return bt
-    _, _, v = _seed_and_challenge(chal, hn, fs._hdr(0, 6) + grp.element_tree(g),
-                                  [H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey, keywidth), l_file(nizkp, l - 1), out_file],
-                                  commit, NV)
-    rep = P.reply(v)
-    with open(ccposr_file(nizkp, l), "wb") as f:
-        f.write(_keyed(rep.native, keywidth).toByteTree())
+        return _write(ccposc_file(nizkp, l), _keyed(box["com"].native, keywidth).toByteTree())
+    parts = shuffle_seed_parts(grp.element_tree(g), H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey, keywidth),
+                               l_file(nizkp, l - 1), out_file)
+    rep = P.reply(_seed_and_challenge(D, parts, commit))
+    _write(ccposr_file(nizkp, l), _keyed(rep.native, keywidth).toByteTree())
     box.clear()
     rep = None
     P.free()
@@ -548,19 +566,15 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     verifiers' intermediates (PoSC.A/C/D, CCPoS.A, CCPoS.B: not printed by the reference; for diffing two builds of this code)."""
     tv = vectors if vectors is not None else {}
     width = len(pkey) // 2 // keywidth
-    hn = _hashname(params)
-    rho = global_prefix(params)
-    tv["der.rho"] = rho.hex()
-    chal = fs.Challenger(rho, hn)
-    bits = 8 * hashlib.new(hn).digest_size
-    g = grp.g
-    H = derive_generators(grp, params, rho, n_max)
+    D = _Derived.of(params)
+    tv["der.rho"] = D.rho.hex()
+    g_tree = grp.element_tree(grp.g)
+    H = derive_generators(grp, params, D.rho, n_max)
     u_bt = _read_file(pc_file(nizkp, l))                                         # readPermutationCommitment :618-636
     U = parse_commitment(grp, u_bt, n_max)
     if U is None:
         return False
-    if not posc_core(nizkp, l, grp, params, H, U, n_max,
-                     lambda: chal.challenge(fs._hdr(0, 3) + grp.element_tree(g) + H.toByteTree() + u_bt, bits), tv):
+    if not posc_core(nizkp, l, grp, params, H, U, n_max, lambda: D.seed(posc_seed_parts(g_tree, H.toByteTree(), u_bt)), tv):
         return False           # (the reference then takes the generators for u and goes on; a harness stops with the verdict)
     # ---- the lists, the keep list, verifyCCPoS :757-830
     W = read_ciphertexts(grp, l_file(nizkp, l - 1), width, 0, keywidth)
@@ -574,17 +588,8 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
     if keep is None:                                                             # shrinkPermComm :714-746 fails the party
         return False
     U_s, H_s = U.extract(keep), H.copyOfRange(0, n)
-
-    def seed2():
-        d = chal.start(bits)
-        d.update(fs._hdr(0, 6) + grp.element_tree(g))
-        d.update(H_s.toByteTree())
-        d.update(U_s.toByteTree())
-        d.update(fs.product_element_tree(grp, pkey, keywidth))
-        for path in (l_file(nizkp, l - 1), l_file(nizkp, l)):
-            with open(path, "rb") as f:
-                d.update(f.read())
-        return chal.finish(d, bits)
+    seed2 = lambda: D.seed(shuffle_seed_parts(g_tree, H_s.toByteTree(), U_s.toByteTree(), fs.product_element_tree(grp, pkey, keywidth),
+                                              l_file(nizkp, l - 1), l_file(nizkp, l)))
     verdict = ccpos_core(nizkp, l, grp, params, pkey, H_s, U_s, W, WP, seed2, tv, keywidth)
     for a in W + WP + [H, U, U_s, H_s]:
         a.free()
@@ -593,78 +598,71 @@ def verify_precomputed_shuffle(nizkp: str, l: int, grp, params: dict, pkey: Sequ
 
 def read_keep_list(nizkp: str, l: int, n_max: int, n: int):
     """The keep list of party l: n_max booleans of which n are set; None when the file is missing or is no such list."""
-    keep = _read_booleans(kl_file(nizkp, l), n_max) if os.path.exists(kl_file(nizkp, l)) else None
+    keep = _read_booleans(kl_file(nizkp, l), n_max)
     return keep if keep is not None and sum(keep) == n else None
+
+
+def _read_message(grp, path: str, kinds, sizes, keywidth: int = 1):
+    """(the bytes of a proof message's file, the message); (None, None) when the file is missing, (bytes, None) when its
+    bytes are no such message."""
+    bt = _read_file(path)
+    return bt, (native.Message.fromByteTree(grp, bt, kinds, sizes, keywidth) if bt is not None else None)
 
 
 def posc_core(nizkp: str, l: int, grp, params: dict, H, U, n_max: int, seed, tv: dict) -> bool:
     """verifyPoSC (:652-703) on loaded inputs: the generators H and the permutation commitment U (n_max elements each) as device
     arrays, `seed()` -> the seed of the batching vector.  Frees nothing it was given."""
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
-    chal = fs.Challenger(global_prefix(params), _hashname(params))
-    V = native.PoSCBasicTW(grp, NV, NE, NR)
+    D = _Derived.of(params)
+    V = native.PoSCBasicTW(grp, D.NV, D.NE, D.NR)
     try:
-        return _posc_core(V, nizkp, l, grp, chal, NV, H, U, n_max, seed, tv)
+        V.setInstance(grp.g, H, U)
+        seed = seed()
+        tv["PoSC.s"] = seed.hex()
+        V.setBatchVectorSeed(seed)
+        com_bt, com = _read_message(grp, poscc_file(nizkp, l), native.PoSCBasicTW._com_kinds, [n_max, 1, n_max, 1, 1])
+        if com is None:
+            return False
+        V.setCommitment(com)
+        v = D.challenge(seed, com_bt)
+        tv["PoSC.v"] = format(v, "x")
+        V.setChallenge(v)
+        _, rep = _read_message(grp, poscr_file(nizkp, l), native.PoSCBasicTW._rep_kinds, [1, n_max, 1, 1, n_max])
+        if rep is None:
+            return False
+        ok_posc = V.verify(rep)
+        tv["PoSC.A"], tv["PoSC.C"], tv["PoSC.D"] = _hex(V.getA()), _hex(V.getC()), _hex(V.getD())
+        return bool(ok_posc)
     finally:
         V.free()
-
-
-def _posc_core(V, nizkp, l, grp, chal, NV, H, U, n_max, seed, tv) -> bool:
-    V.setInstance(grp.g, H, U)
-    seed = seed()
-    tv["PoSC.s"] = seed.hex()
-    V.setBatchVectorSeed(seed)
-    com_bt = _read_file(poscc_file(nizkp, l))
-    com = native.Message.fromByteTree(grp, com_bt, native.PoSCBasicTW._com_kinds, [n_max, 1, n_max, 1, 1]) if com_bt is not None else None
-    if com is None:
-        return False
-    V.setCommitment(com)
-    v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")
-    tv["PoSC.v"] = format(v, "x")
-    V.setChallenge(v)
-    rep_bt = _read_file(poscr_file(nizkp, l))
-    rep = native.Message.fromByteTree(grp, rep_bt, native.PoSCBasicTW._rep_kinds, [1, n_max, 1, 1, n_max]) if rep_bt is not None else None
-    if rep is None:
-        return False
-    ok_posc = V.verify(rep)
-    tv["PoSC.A"], tv["PoSC.C"], tv["PoSC.D"] = _hex(V.getA()), _hex(V.getC()), _hex(V.getD())
-    return bool(ok_posc)
 
 
 def ccpos_core(nizkp: str, l: int, grp, params: dict, pkey: Sequence, H_s, U_s, W, WP, seed, tv: dict, keywidth: int = 1) -> bool:
     """verifyCCPoS (:757-830) on loaded inputs: the shrunk generators and permutation commitment and the two lists as device
     arrays, `seed()` -> the seed of the batching vector.  Frees nothing it was given."""
-    NV, NE, NR = int(params["vbitlenro"]), int(params["ebitlenro"]), int(params["rbitlen"])
-    chal = fs.Challenger(global_prefix(params), _hashname(params))
-    C = native.CCPoSBasicW(grp, NV, NE, NR)
+    D = _Derived.of(params)
+    n, width = W[0].size(), len(pkey) // 2
+    C = native.CCPoSBasicW(grp, D.NV, D.NE, D.NR)
     try:
-        return _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv, keywidth)
+        C.setInstance(grp.g, H_s, U_s, pkey, W, WP)
+        seed2 = seed()
+        tv["CCPoS.s"] = seed2.hex()
+        C.setBatchVectorSeed(seed2)
+        C.computeAB()
+        A, B = C.getAB()
+        tv["CCPoS.A"], tv["CCPoS.B"] = _hex(A), _hexes(B)
+        com_bt, com = _read_message(grp, ccposc_file(nizkp, l), native.CCPoSBasicW._com_kinds, [1, 2 * width], keywidth)
+        if com is None:
+            return False
+        C.setCommitment(com)
+        v2 = D.challenge(seed2, com_bt)
+        tv["CCPoS.v"] = format(v2, "x")
+        C.setChallenge(v2)
+        _, rep = _read_message(grp, ccposr_file(nizkp, l), native.CCPoSBasicW._rep_kinds, [1, width, n], keywidth)
+        if rep is None:
+            return False
+        return bool(C.verify(rep))
     finally:
         C.free()
-
-
-def _ccpos_core(C, nizkp, l, grp, chal, NV, pkey, H_s, U_s, W, WP, seed, tv, keywidth=1) -> bool:
-    n, width = W[0].size(), len(pkey) // 2
-    C.setInstance(grp.g, H_s, U_s, pkey, W, WP)
-    seed2 = seed()
-    tv["CCPoS.s"] = seed2.hex()
-    C.setBatchVectorSeed(seed2)
-    C.computeAB()
-    A, B = C.getAB()
-    tv["CCPoS.A"], tv["CCPoS.B"] = _hex(A), "(" + ", ".join(_hex(x) for x in B) + ")"
-    com_bt = _read_file(ccposc_file(nizkp, l))
-    com = native.Message.fromByteTree(grp, com_bt, native.CCPoSBasicW._com_kinds, [1, 2 * width], keywidth) if com_bt is not None else None
-    if com is None:
-        return False
-    C.setCommitment(com)
-    v2 = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed2) + com_bt, NV), "big")
-    tv["CCPoS.v"] = format(v2, "x")
-    C.setChallenge(v2)
-    rep_bt = _read_file(ccposr_file(nizkp, l))
-    rep = native.Message.fromByteTree(grp, rep_bt, native.CCPoSBasicW._rep_kinds, [1, width, n], keywidth) if rep_bt is not None else None
-    if rep is None:
-        return False
-    return bool(C.verify(rep))
 
 
 # =============================================================================================================================
@@ -709,62 +707,30 @@ def plaintexts_file(nizkp):
     return _p(nizkp, "Plaintexts.bt")
 
 
-def _prg_seed_bits(params: dict) -> int:
-    """8 * prg.minNoSeedBytes(): the digest length of the PRG's hash function (PRGHeuristic)."""
-    return 8 * hashlib.new({"SHA-256": "sha256", "SHA-384": "sha384", "SHA-512": "sha512"}[params.get("prg", "SHA-256")]).digest_size
-
-
 def _wide_array_tree(comps: Sequence[PGroupElementArray], keywidth: int = 1) -> bytes:
     """toByteTree() of an array of G^omega given as its omega component arrays, of (G^kappa)^omega given as its kappa omega."""
     return fs.nested_tree([a.toByteTree() for a in comps], keywidth)
 
 
-def _nested_reader(buf: bytes, pos: int, width: int, keywidth: int, item):
-    """The kappa * omega values of fs.nested_tree at buf[pos:], each read by item(buf, pos) -> (value, next pos) | None;
-    (values, next pos), or None when a node is not the one the widths ask for."""
-    def node(count):
-        nonlocal pos
-        if buf[pos:pos + 5] != fs._hdr(0, count):
-            return False
-        pos += 5
-        return True
-    if width > 1 and not node(width):
+def _member_arrays(comps):
+    """comps when every array lies in the group; else -- also when the check itself fails -- None, and the arrays are freed."""
+    if comps is None:
         return None
-    values = []
-    for _ in range(width):
-        if keywidth > 1 and not node(keywidth):
-            return None
-        for _ in range(keywidth):
-            got = item(buf, pos)
-            if got is None:
-                return None
-            values.append(got[0])
-            pos = got[1]
-    return values, pos
+    try:
+        if all(c.isMember() for c in comps):
+            return comps
+    except (ValueError, native.VmnError):
+        pass
+    for c in comps:
+        c.free()
+    return None
 
 
 def _read_wide_array(grp, path: str, width: int, n: int, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
     """The omega component arrays (kappa omega under a key of width kappa; n elements each) of such a file; None when the file
     is missing or is no such array."""
-    comps = []
-    try:
-        with open(path, "rb") as f:
-            buf = f.read()
-        size = grp.array_tree_size(n)
-
-        def array(b, at):
-            comps.append(grp.toElementArrayFromByteTree(b[at:at + size], n))
-            return comps[-1], at + size
-        got = _nested_reader(buf, 0, width, keywidth, array)
-        if got is None or got[1] != len(buf) or not all(c.isMember() for c in comps):
-            return None
-        return comps
-    except (OSError, ValueError, native.VmnError):
-        return None
-
-
-def _wide_element_tree(grp, els, keywidth: int = 1) -> bytes:
-    return fs.wide_element_tree(grp, els, keywidth)
+    buf = _read_file(path)
+    return _member_arrays(read_array_nests(grp, buf, 1, width, keywidth, n)) if buf is not None else None
 
 
 def _rows(x, keywidth: int):
@@ -772,8 +738,19 @@ def _rows(x, keywidth: int):
     return (x,) if keywidth == 1 else tuple(x)
 
 
+def _unrows(rows, keywidth: int):
+    """_rows back: the one row itself at kappa = 1, the tuple of the rows otherwise."""
+    return rows[0] if keywidth == 1 else tuple(rows)
+
+
+def _y_rows(pkey: Sequence, width: int, keywidth: int):
+    """y of a wide key of 2 * width rows (g repeated, then y_0 .. y_(kappa-1) repeated omega times): the element at kappa = 1,
+    else its kappa rows."""
+    return pkey[-1] if keywidth == 1 else tuple(pkey[width:width + keywidth])
+
+
 def _commitment_tree(grp, yp, Bp, keywidth: int = 1) -> bytes:
-    return fs._hdr(0, 2) + fs.nested_tree([grp.element_tree(e) for e in _rows(yp, keywidth)], keywidth) + _wide_element_tree(grp, Bp, keywidth)
+    return fs._hdr(0, 2) + fs.nested_tree([grp.element_tree(e) for e in _rows(yp, keywidth)], keywidth) + fs.wide_element_tree(grp, Bp, keywidth)
 
 
 def _reply_tree(grp, kx, keywidth: int = 1) -> bytes:
@@ -784,36 +761,36 @@ def _reply_tree(grp, kx, keywidth: int = 1) -> bytes:
 def _read_reply(grp, buf: bytes, keywidth: int = 1):
     """The reply of a DecrFactReply file's bytes (an integer, a kappa-tuple under a key of width kappa); None when the bytes are
     no such tree.  A row >= q is handed on: it costs the party its verdict, not the file its format (:606-613)."""
-    xb = grp.exp_bytes
-
-    def leaf(b, at):
-        if b[at:at + 5] != fs._hdr(1, xb) or len(b) < at + 5 + xb:
-            return None
-        return int.from_bytes(b[at + 5:at + 5 + xb], "big"), at + 5 + xb
-    got = _nested_reader(buf, 0, 1, keywidth, leaf)
-    if got is None or got[1] != len(buf):
+    try:
+        cur = fs.Cursor(buf)
+        rows = cur.nested(1, keywidth, lambda c: int.from_bytes(c.leaf(grp.exp_bytes), "big"))
+        cur.end()
+        return _unrows(rows, keywidth)
+    except fs.NoSuchTree:
         return None
-    return got[0][0] if keywidth == 1 else tuple(got[0])
+
+
+def _read_element_nests(grp, buf: Optional[bytes], widths: Sequence[int], keywidth: int):
+    """node(len(widths) nests) filling buf, nest i holding kappa * widths[i] element trees: the nests' elements, or None when
+    there are no bytes or the framing is wrong (over a curve also: a leaf that is not of the coordinate width, a point that is
+    not on the curve)."""
+    try:
+        if buf is None:
+            return None
+        cur = fs.Cursor(buf)
+        cur.node(len(widths))
+        nests = [cur.nested(w, keywidth, lambda c: c.item(grp.element_from_tree)) for w in widths]
+        cur.end()
+        return nests
+    except fs.NoSuchTree:
+        return None
 
 
 def _read_commitment(grp, path: str, width: int, keywidth: int = 1):
     """(y', (B'_0 .. B'_(omega-1))) of a commitment file as group elements (y' a kappa-tuple and B' kappa omega elements under a
-    key of width kappa); None when the framing is wrong (over a curve also: a leaf that is not of the coordinate width, a point
-    that is not on the curve)."""
-    try:
-        with open(path, "rb") as f:
-            buf = f.read()
-    except OSError:
-        return None
-    if buf[:5] != fs._hdr(0, 2):
-        return None
-    yp = _nested_reader(buf, 5, 1, keywidth, grp.element_from_tree)
-    if yp is None:
-        return None
-    Bp = _nested_reader(buf, yp[1], width, keywidth, grp.element_from_tree)
-    if Bp is None or Bp[1] != len(buf):
-        return None
-    return (yp[0][0] if keywidth == 1 else tuple(yp[0])), tuple(Bp[0])
+    key of width kappa); None when the file is missing or is no such tree."""
+    got = _read_element_nests(grp, _read_file(path), (1, width), keywidth)
+    return (_unrows(got[0], keywidth), tuple(got[1])) if got is not None else None
 
 
 def eval_polynomial_in_exponent(grp, coeffs: Sequence, l: int):
@@ -844,18 +821,10 @@ def _polynomial_tree(grp, poly: Sequence, keywidth: int = 1) -> bytes:
 def parse_polynomial(grp, buf: Optional[bytes], threshold: int, keywidth: int = 1):
     """The `threshold` coefficients of a PolynomialInExponent.bt file's bytes (kappa-tuples under a key of width kappa); None
     when the bytes are no such tree or a coefficient is outside the group."""
-    arrays = []
+    arrays = _member_arrays(read_array_nests(grp, buf, 1, 1, keywidth, threshold)) if buf is not None else None
+    if arrays is None:
+        return None
     try:
-        if buf is None:
-            return None
-        size = grp.array_tree_size(threshold)
-
-        def array(b, at):
-            arrays.append(grp.toElementArrayFromByteTree(b[at:at + size], threshold))
-            return arrays[-1], at + size
-        got = _nested_reader(buf, 0, 1, keywidth, array)
-        if got is None or got[1] != len(buf) or not all(a.isMember() for a in arrays):
-            return None
         rows = [a.toInts() for a in arrays]
         return rows[0] if keywidth == 1 else [tuple(r[d] for r in rows) for d in range(threshold)]
     except (ValueError, native.VmnError):
@@ -865,17 +834,12 @@ def parse_polynomial(grp, buf: Optional[bytes], threshold: int, keywidth: int = 
             a.free()
 
 
-def _decryption_seed(chal, grp, params, list_bytes: bytes, poly_bt: bytes, factor_trees: Sequence[bytes], keywidth: int = 1) -> bytes:
+def _decryption_seed(D: _Derived, grp, list_bytes: bytes, poly_bt: bytes, factors: Sequence, keywidth: int = 1) -> bytes:
     """challenge(node(node(g, ciphertexts), node(polynomial, node(factors of parties 1..k))), 8 * minNoSeedBytes)  :434-461;
-    g is plainPGroup.getg() = (g, .., g) (:1587)."""
-    bits = _prg_seed_bits(params)
-    d = chal.start(bits)
-    d.update(fs._hdr(0, 2) + fs._hdr(0, 2) + fs.nested_tree([grp.element_tree(grp.g)] * keywidth, keywidth))
-    d.update(list_bytes)
-    d.update(fs._hdr(0, 2) + poly_bt + fs._hdr(0, len(factor_trees)))
-    for t in factor_trees:
-        d.update(t)
-    return chal.finish(d, bits)
+    g is plainPGroup.getg() = (g, .., g) (:1587).  `factors`: every party's factors as device arrays."""
+    head = fs._hdr(0, 2) + fs._hdr(0, 2) + fs.nested_tree([grp.element_tree(grp.g)] * keywidth, keywidth)
+    trees = [_wide_array_tree(fl, keywidth) for fl in factors]
+    return D.seed([head, list_bytes, fs._hdr(0, 2) + poly_bt + fs._hdr(0, len(trees))] + trees, D.prg_bits)
 
 
 def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], poly: Sequence[int],
@@ -889,51 +853,41 @@ def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[
     factors party l publishes; `tamper_reply(l, k_x)` (tests): the reply it publishes.  Under a key of width `keywidth` = kappa
     W has 2 kappa omega arrays and a coefficient of `poly` and a share are kappa-tuples."""
     os.makedirs(_p(nizkp, "proofs"), exist_ok=True)
-    NV, NE = int(params["vbitlenro"]), int(params["ebitlenro"])
+    D = _Derived.of(params)
     width = len(W) // 2                                                            # components in all: kappa * omega
-    hn = _hashname(params)
-    chal = fs.Challenger(global_prefix(params), hn)
     U, V = list(W[:width]), list(W[width:])
-    y = pkey[-1] if keywidth == 1 else tuple(pkey[width:width + keywidth])
+    y = _y_rows(pkey, width, keywidth)
     keyed = {} if keywidth == 1 else {"keywidth": keywidth}
     ys = [None] + [eval_keys(grp, poly, l, keywidth) for l in range(1, k + 1)]
-    poly_bt = _polynomial_tree(grp, poly, keywidth)
-    with open(poly_file(nizkp), "wb") as f:
-        f.write(poly_bt)
+    poly_bt = _write(poly_file(nizkp), _polynomial_tree(grp, poly, keywidth))
     F: List[Optional[List[PGroupElementArray]]] = [None]
     for l in range(1, k + 1):                                                      # :384-399
         fl = native.decryptionFactors(U, shares[l] if keywidth == 1 else list(shares[l]), grp.q, k)
         if tamper is not None:
             fl = tamper(l, fl)
         F.append(fl)
-        with open(df_file(nizkp, l), "wb") as f:
-            f.write(_wide_array_tree(fl, keywidth))
+        _write(df_file(nizkp, l), _wide_array_tree(fl, keywidth))
     correct = [True] * (k + 1)
     comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)         # :406-410
-    seed = _decryption_seed(chal, grp, params, _ciphertexts_tree(W, keywidth), poly_bt, [_wide_array_tree(fl, keywidth) for fl in F[1:]],
-                            keywidth)
+    seed = _decryption_seed(D, grp, _ciphertexts_tree(W, keywidth), poly_bt, F[1:], keywidth)
     sessions = []
     for l in range(1, k + 1):
-        s = native.DistrElGamalSessionBasic(grp, l, k, threshold, NE, rand=rand)
+        s = native.DistrElGamalSessionBasic(grp, l, k, threshold, D.NE, rand=rand)
         s.setInstance(U, ys, F, **keyed)
         s.setBatchVectorSeed(seed)
         s.batchInput()
         sessions.append(s)
-    commitments = [None]
+    commitments, trees = [None], []
     for l in range(1, k + 1):                                                      # :469
-        yp, Bp = sessions[l - 1].commit(shares[l])
-        commitments.append((yp, Bp))
-        with open(dfc_file(nizkp, l), "wb") as f:
-            f.write(_commitment_tree(grp, yp, Bp, keywidth))
-    com_bt = fs._hdr(0, k) + b"".join(_commitment_tree(grp, *c, keywidth) for c in commitments[1:])
-    v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + com_bt, NV), "big")      # :474-480
+        commitments.append(sessions[l - 1].commit(shares[l]))
+        trees.append(_write(dfc_file(nizkp, l), _commitment_tree(grp, *commitments[l], keywidth)))
+    v = D.challenge(seed, fs._hdr(0, k) + b"".join(trees))                         # :474-480
     ver = sessions[0]
     for l in range(1, k + 1):                                                      # :483
         kx = sessions[l - 1].reply(v)
         if tamper_reply is not None:
             kx = tamper_reply(l, kx)
-        with open(dfr_file(nizkp, l), "wb") as f:
-            f.write(_reply_tree(grp, kx, keywidth))
+        _write(dfr_file(nizkp, l), _reply_tree(grp, kx, keywidth))
         if l != 1:
             ver.setCommitment(l, *commitments[l])
             ver.setReply(l, kx)
@@ -947,10 +901,8 @@ def write_decryption(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[
             a.free()
         comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)
     plain = native.plaintexts(V, comb)                                             # :536-538
-    with open(plaintexts_file(nizkp), "wb") as f:
-        f.write(_wide_array_tree(plain, keywidth))
-    with open(cr_file(nizkp), "wb") as f:                                          # :542
-        f.write(_booleans_tree(correct))
+    _write(plaintexts_file(nizkp), _wide_array_tree(plain, keywidth))
+    _write(cr_file(nizkp), _booleans_tree(correct))                                # :542
     for s in sessions:
         s.free()
     for a in comb + [c for fl in F[1:] for c in fl]:
@@ -982,80 +934,76 @@ def verify_decryption(nizkp: str, grp, params: dict, pkey: Sequence, list_file: 
 def dec_core(nizkp: str, grp, params: dict, pkey: Sequence, W: Sequence[PGroupElementArray], list_bytes, tv: dict, keywidth: int = 1):
     """The decryption branch on a loaded list: its 2 omega component arrays W and the bytes of its tree (what the seed is
     hashed over).  Returns (verdict, the correct indices read from CorrectIndices.bt or None); frees nothing it was given."""
-    NV, NE = int(params["vbitlenro"]), int(params["ebitlenro"])
+    D = _Derived.of(params)
     k, threshold = int(params["k"]), int(params["threshold"])
-    width = len(pkey) // 2
-    hn = _hashname(params)
-    chal = fs.Challenger(global_prefix(params), hn)
-    try:
-        with open(poly_file(nizkp), "rb") as f:
-            poly_bt = f.read()
-        correct = _read_booleans(cr_file(nizkp), k + 1)
-    except OSError:
-        return False, None
+    width = len(pkey) // 2                                                         # components in all, kappa * omega
+    n, omega = W[0].size(), width // keywidth
+    keyed = {} if keywidth == 1 else {"keywidth": keywidth}
+    poly_bt = _read_file(poly_file(nizkp))
+    correct = _read_booleans(cr_file(nizkp), k + 1) if poly_bt is not None else None
     if correct is None or sum(1 for l in range(1, k + 1) if correct[l]) < threshold:
         return False, correct
-    return _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct, keywidth), correct
-
-
-def _dec_core(nizkp, grp, params, pkey, W, list_bytes, tv, NV, NE, k, threshold, width, chal, poly_bt, correct, keywidth=1) -> bool:
-    n = W[0].size()                                                                # (width: components in all, kappa * omega)
-    omega = width // keywidth
-    keyed = {} if keywidth == 1 else {"keywidth": keywidth}
-    poly = parse_polynomial(grp, poly_bt, threshold, keywidth)
-    if poly is None:
-        return False
-    ys = [None] + [eval_keys(grp, poly, l, keywidth) for l in range(1, k + 1)]
-    for l in range(1, k + 1):
-        tv["Dec.y_%d" % l] = _hexk(ys[l], keywidth)
-    F: List[Optional[List[PGroupElementArray]]] = [None]
-    for l in range(1, k + 1):                                                      # getDecryptionFactors :1098-1114
-        fl = _read_wide_array(grp, df_file(nizkp, l), omega, n, keywidth)
-        if fl is None:
-            return False
-        F.append(fl)
-    U, V = W[:width], W[width:]
+    basic, made = None, []                                                         # the engine and the device arrays created here
     try:
-        comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)     # :1569-1574
-    except native.VmnError:
-        return False
-    seed = _decryption_seed(chal, grp, params, list_bytes, poly_bt, [_wide_array_tree(fl, keywidth) for fl in F[1:]], keywidth)
-    tv["Dec.s"] = seed.hex()                                                       # :1609
-    basic = native.DistrElGamalSessionBasic(grp, 1, k, threshold, NE)
-    basic.setInstance(U, ys, F, **keyed)
-    basic.setBatchVectorSeed(seed)
-    basic.batchInput()
-    trees = []
-    for l in range(1, k + 1):                                                      # readCommitments :1182-1190
-        c = _read_commitment(grp, dfc_file(nizkp, l), omega, keywidth)
-        if c is None:
-            return False
+        poly = parse_polynomial(grp, poly_bt, threshold, keywidth)
+        if poly is None:
+            return False, correct
+        ys = [None] + [eval_keys(grp, poly, l, keywidth) for l in range(1, k + 1)]
+        for l in range(1, k + 1):
+            tv["Dec.y_%d" % l] = _hexk(ys[l], keywidth)
+        F: List[Optional[List[PGroupElementArray]]] = [None]
+        for l in range(1, k + 1):                                                  # getDecryptionFactors :1098-1114
+            fl = _read_wide_array(grp, df_file(nizkp, l), omega, n, keywidth)
+            if fl is None:
+                return False, correct
+            F.append(fl)
+            made += fl
+        U, V = W[:width], W[width:]
         try:
-            basic.setCommitment(l, *c)
+            comb = native.combineDecryptionFactors(F, correct, k, threshold, grp.q)     # :1569-1574
         except native.VmnError:
-            return False
-        trees.append(_commitment_tree(grp, *c, keywidth))
-    v = int.from_bytes(chal.challenge(fs._hdr(0, 2) + fs.leaf(seed) + fs._hdr(0, k) + b"".join(trees), NV), "big")
-    tv["Dec.v"] = str(v)                                                           # :1634
-    for l in range(1, k + 1):                                                      # readReplies :1198-1206
-        buf = _read_file(dfr_file(nizkp, l))
-        kx = _read_reply(grp, buf, keywidth) if buf is not None else None
-        if kx is None:
-            return False
-        basic.setReply(l, kx)
-    try:
-        basic.combine(correct, pkey[-1] if keywidth == 1 else tuple(pkey[width:width + keywidth]), comb)       # :1640-1644
-        basic.batchCombined()
-        verdict = basic.verifyCombined(v)
-    except native.VmnError:
-        return False
-    computed = native.plaintexts(V, comb)                                          # :1652-1663
-    plain = _read_wide_array(grp, plaintexts_file(nizkp), omega, n, keywidth)
-    ok = bool(verdict) and plain is not None and all(a.equals(b) for a, b in zip(plain, computed))
-    basic.free()
-    for a in comb + computed + (plain or []) + [c for fl in F[1:] for c in fl]:
-        a.free()
-    return ok
+            return False, correct
+        made += comb
+        seed = _decryption_seed(D, grp, list_bytes, poly_bt, F[1:], keywidth)
+        tv["Dec.s"] = seed.hex()                                                   # :1609
+        basic = native.DistrElGamalSessionBasic(grp, 1, k, threshold, D.NE)
+        basic.setInstance(U, ys, F, **keyed)
+        basic.setBatchVectorSeed(seed)
+        basic.batchInput()
+        trees = []
+        for l in range(1, k + 1):                                                  # readCommitments :1182-1190
+            c = _read_commitment(grp, dfc_file(nizkp, l), omega, keywidth)
+            if c is None:
+                return False, correct
+            try:
+                basic.setCommitment(l, *c)
+            except native.VmnError:
+                return False, correct
+            trees.append(_commitment_tree(grp, *c, keywidth))
+        v = D.challenge(seed, fs._hdr(0, k) + b"".join(trees))
+        tv["Dec.v"] = str(v)                                                       # :1634
+        for l in range(1, k + 1):                                                  # readReplies :1198-1206
+            buf = _read_file(dfr_file(nizkp, l))
+            kx = _read_reply(grp, buf, keywidth) if buf is not None else None
+            if kx is None:
+                return False, correct
+            basic.setReply(l, kx)
+        try:
+            basic.combine(correct, _y_rows(pkey, width, keywidth), comb)           # :1640-1644
+            basic.batchCombined()
+            verdict = basic.verifyCombined(v)
+        except native.VmnError:
+            return False, correct
+        computed = native.plaintexts(V, comb)                                      # :1652-1663
+        made += computed
+        plain = _read_wide_array(grp, plaintexts_file(nizkp), omega, n, keywidth)
+        made += plain or []
+        return bool(verdict) and plain is not None and all(a.equals(b) for a, b in zip(plain, computed)), correct
+    finally:
+        if basic is not None:
+            basic.free()
+        for a in made:
+            a.free()
 
 
 # =============================================================================================================================
@@ -1109,8 +1057,7 @@ def mc_file(nizkp):
 
 def write_string(path: str, value: str) -> None:
     """A small session file ([NOT-IN-REF]: ExtIO's own format is VCR code): UTF-8 text, no trailing newline."""
-    with open(path, "wb") as f:
-        f.write(value.encode("utf-8"))
+    _write(path, value.encode("utf-8"))
 
 
 def write_int(path: str, value: int) -> None:
@@ -1302,17 +1249,8 @@ class SessionEngines:
 # ---- the engines on the GPU ---------------------------------------------------------------------------------------------------
 def _gpu_read_pkey(ctx, path):
     """An element of getCiphPGroup(plainPGroup, 1): node(g', y), each half node(kappa element trees) when kappa > 1."""
-    buf = _read_file(path)
-    if buf is None or buf[:5] != fs._hdr(0, 2):
-        return None
-    pos, els = 5, []
-    for _ in range(2):
-        got = _nested_reader(buf, pos, 1, ctx.keywidth, ctx.grp.element_from_tree)
-        if got is None:
-            return None
-        els.append(got[0][0] if ctx.keywidth == 1 else tuple(got[0]))
-        pos = got[1]
-    return els if pos == len(buf) else None
+    got = _read_element_nests(ctx.grp, _read_file(path), (1, 1), ctx.keywidth)
+    return [_unrows(rows, ctx.keywidth) for rows in got] if got is not None else None
 
 
 def _gpu_read_poly(ctx, path, threshold):
@@ -1327,16 +1265,6 @@ def _gpu_derive_generators(ctx, rho, n):
 def _gpu_shrink(ctx, l, U, n_max, n):
     keep = read_keep_list(ctx.nizkp, l, n_max, n)
     return U.extract(keep) if keep is not None else None
-
-
-def _gpu_hash_seed(ctx, kind, l, parts):
-    hn = _hashname(ctx.params)
-    chal = fs.Challenger(global_prefix(ctx.params), hn)
-    bits = 8 * hashlib.new(hn).digest_size
-    d = chal.start(bits)
-    for part in parts:
-        d.update(part)
-    return chal.finish(d, bits)
 
 
 def _gpu_free(ctx, arrays):
@@ -1356,7 +1284,7 @@ GPU_ENGINES = SessionEngines(
     verify_ccpos=lambda ctx, l, H_s, U_s, W, WP, seed, tv: ccpos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, H_s, U_s, W, WP, seed, tv, ctx.keywidth),
     verify_pos=lambda ctx, l, H, U, W, WP, seed, tv, with_arrays: pos_core(ctx.nizkp, l, ctx.grp, ctx.params, ctx.pkey, W, WP, H, U, seed, tv, with_arrays, ctx.keywidth),
     verify_dec=lambda ctx, W, data, tv: dec_core(ctx.nizkp, ctx.grp, ctx.params, ctx.pkey, W, data, tv, ctx.keywidth),
-    hash_seed=_gpu_hash_seed,
+    hash_seed=lambda ctx, kind, l, parts: _Derived.of(ctx.params).seed(parts),
     show=lambda ctx, a: "(" + ", ".join(_arr(c) for c in a) + ")" if isinstance(a, list) else _arr(a),
     free=_gpu_free)
 
@@ -1557,7 +1485,7 @@ def run_session(nizkp: str, grp, params: dict, expected: SessionParams, eng: Ses
         def posc_job(l):
             def job():
                 u_bt = files.get(pc_file(nizkp, l))
-                return eng.hash_seed(ctx, "PoSC", l, [fs._hdr(0, 3) + g_tree, H_bt, u_bt]) if u_bt is not None else None
+                return eng.hash_seed(ctx, "PoSC", l, posc_seed_parts(g_tree, H_bt, u_bt)) if u_bt is not None else None
             return job
 
         def shuffle_job(l, src, dst, source):
@@ -1567,12 +1495,12 @@ def run_session(nizkp: str, grp, params: dict, expected: SessionParams, eng: Ses
                 if u_bt is None or a is None or b is None:
                     return None
                 if not precomp:
-                    return eng.hash_seed(ctx, "PoS", l, [fs._hdr(0, 6) + g_tree, H_bt, u_bt, pk_tree, a, b])
+                    return eng.hash_seed(ctx, "PoS", l, shuffle_seed_parts(g_tree, H_bt, u_bt, pk_tree, a, b))
                 keep = read_keep_list(nizkp, l, maxciph, n)
                 if keep is None:
                     return None
-                return eng.hash_seed(ctx, "CCPoS", l, [fs._hdr(0, 6) + g_tree, _tree_prefix(grp, H_bt, n), _tree_extract(grp, u_bt, keep),
-                                                       pk_tree, a, b])
+                return eng.hash_seed(ctx, "CCPoS", l, shuffle_seed_parts(g_tree, _tree_prefix(grp, H_bt, n), _tree_extract(grp, u_bt, keep),
+                                                                         pk_tree, a, b))
             return job
 
         def hash_ahead(l, src):
