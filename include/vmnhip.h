@@ -227,6 +227,32 @@ int vmn_garrays_from_jsonlines(vmn_group* grp, size_t width, const char* text, s
                                size_t* n_out, int* format_ok, size_t* first_bad_line, int* all_in_range);
 int vmn_garrays_to_jsonlines(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written);
 int vmn_garrays_to_jsonplain(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written);
+/* Plaintexts as text: messages encoded as group elements and decoded again -- the text interface behind a session (the
+ * reference ends an election with `vmnc -plain -outi native`: ProtocolElGamalInterfaceString.decodePlaintexts, :197-236; its
+ * demoCiphertexts, :315-428, is built on pGroup.encode).  [NOT-IN-REF: VCR ModPGroup, safe-prime encoding; unpinned -- encode,
+ * decode and getEncodeLength are VCR code; csrc/encode_layout.h states the rule built here, on integers.]
+ * vmn_group_encode_length: L = floor((bits(p) - 2) / 8) - 4, the bytes one element holds (59 / 123 / 251 / 379 / 507 at 512 / 1024 /
+ * 2048 / 3072 / 4096 bits), for a modular group with p = 2q + 1 and L >= 1; 0 for every other group (curves, other cofactors, a
+ * null group), over which the two functions below return VMN_ERR_UNSUPPORTED.
+ * An element holds be32(len) || message || zeros on L + 4 bytes as an integer v (the empty message with a 1 behind the length),
+ * stored as v or p - v, whichever is a quadratic residue (one Jacobi symbol per element, on the GPU).  Decoding folds e to
+ * min(e, p - e); the element is ill-formed, its message empty, when that is 2^(8 (L + 4)) or more or its length word exceeds L.
+ * A message over ncomp = keywidth * width components (flat order; 1..65536) is cut into pieces of L bytes, the later components
+ * holding the empty message; decoding concatenates the components' messages whatever their lengths.
+ * from_textlines: a line is its bytes; lines end as Java's readLine ends them (\n, \r, \r\n once), an empty line is the empty
+ * message, text behind the last terminator is a line if not empty.  out receives ncomp arrays of *n_out elements and *fits = 1;
+ * when a line has more than ncomp L bytes *fits = 0, every out[] slot is NULL and *first_long_line is the zero-based index of the
+ * first such line.  A text without lines gives ncomp empty arrays.
+ * to_textlines: line i is the concatenated message of element i with every 0x0A and 0x0D byte removed, then \n.
+ * *all_wellformed = 0 when some element was ill-formed; *all_utf8 = 0 when some line's concatenation, BEFORE the removal (Java
+ * decodes, then strips), is not well-formed UTF-8 (Unicode table 3-7) -- such a line is written byte for byte [NOT-IN-REF: Java
+ * substitutes U+FFFD].  Both may be NULL.  *written receives the bytes written; no NUL; VMN_ERR_ARG, writing nothing, when cap is
+ * too small for these lines: a cap of n (ncomp L + 1) always suffices.  Never writes behind cap. */
+size_t vmn_group_encode_length(const vmn_group* grp);
+int vmn_garrays_from_textlines(vmn_group* grp, size_t ncomp, const char* text, size_t len, vmn_garray** out, size_t* n_out, int* fits,
+                               size_t* first_long_line);
+int vmn_garrays_to_textlines(const vmn_garray* const* comps, size_t ncomp, char* out, size_t cap, size_t* written, int* all_wellformed,
+                             int* all_utf8);
 size_t vmn_garray_size(const vmn_garray* a);
 /* the group an array belongs to (PGroupElementArray.getPGroup(), PRingElementArray.getPRing()): a binding sizes the host
  * buffers of vmn_*_to_be / _get / _prod ... from it (jni/: every byte[] is checked against the bytes the callee touches) */

@@ -173,6 +173,51 @@ final class GPUArrays {
         return buf;
     }
 
+    /** Lines of text as a list of plaintexts (pGroup.encode over a safe-prime group, include/vmnhip.h: vmn_garrays_from_textlines):
+     *  line i, cut into pieces of vmn_group_encode_length bytes, is element i of the {@code ncomp} component arrays.  A line of more
+     *  than ncomp times that many bytes is no list: {@code firstLongLine[0]} (may be null) receives its zero-based index and the
+     *  call throws. */
+    static PGroupElementArrayGPU[] encodePlaintexts(final GPUGroup group, final ByteBuffer text, final long len, final int ncomp,
+                                                    final long[] firstLongLine) {
+        final long[] out = new long[ncomp];
+        final long[] lines = new long[1];
+        final long[] longLine = new long[1];
+        final int[] fits = new int[1];
+        VMNException.check(VMNHip.vmn_garrays_from_textlinesDirect(group.grp, ncomp, text, len, out, lines, fits, longLine));
+        if (firstLongLine != null) {
+            firstLongLine[0] = longLine[0];
+        }
+        if (fits[0] == 0) {
+            throw new VMNException(VMNException.ERR_FORMAT);
+        }
+        final PGroupElementArrayGPU[] comps = new PGroupElementArrayGPU[ncomp];
+        for (int c = 0; c < ncomp; c++) {
+            comps[c] = new PGroupElementArrayGPU(group, out[c]);
+        }
+        return comps;
+    }
+
+    /** decodePlaintexts of the native interface (ProtocolElGamalInterfaceString.java:197-236): line i is the message of plaintext
+     *  i -- its components' messages one after the other -- without its \n and \r bytes, into a fresh direct buffer limited to
+     *  the bytes written.  {@code verdicts} (may be null) receives {all well-formed, all UTF-8}: an element that holds no
+     *  message gives an empty piece, a line that is not UTF-8 is written byte for byte. */
+    static ByteBuffer decodePlaintextsNative(final GPUGroup group, final PGroupElementArrayGPU[] plaintexts, final boolean[] verdicts) {
+        final long[] h = handles(plaintexts);
+        final long lines = plaintexts.length == 0 ? 0 : VMNHip.vmn_garray_size(h[0]);
+        final long cap = Math.max(1L, lines * (plaintexts.length * VMNHip.vmn_group_encode_length(group.grp) + 1));
+        final ByteBuffer buf = ByteBuffer.allocateDirect((int) cap);
+        final long[] written = new long[1];
+        final int[] wellformed = new int[1];
+        final int[] utf8 = new int[1];
+        VMNException.check(VMNHip.vmn_garrays_to_textlinesDirect(h, plaintexts.length, buf, cap, written, wellformed, utf8));
+        if (verdicts != null) {
+            verdicts[0] = wellformed[0] != 0;
+            verdicts[1] = utf8[0] != 0;
+        }
+        buf.limit((int) written[0]);
+        return buf;
+    }
+
     /** The reverse (CiphertextWriterLine): lowercase digits, every line ended by a newline, into a fresh direct buffer. */
     static ByteBuffer writeCiphertextsNative(final PGroupElementArrayGPU[] comps) {
         final long[] h = handles(comps);

@@ -12,7 +12,8 @@ The wrappers are mechanical (the C ABI was designed for it: opaque pointers, pla
     vmn_X**  (result handles)           long[]      (one slot per result; vmn_shuffle_reencrypt fills 2 * width)
     const vmn_Xarray* const*            long[]
     const uint8_t* / uint8_t*           byte[]      (big-endian rows, byte trees; results are written back)
-    const char* text, size_t len        byte[]      (a whole text file: vmn_garrays_from_hexlines, vmn_garrays_from_jsonlines)
+    const char* text, size_t len        byte[]      (a whole text file: vmn_garrays_from_hexlines, vmn_garrays_from_jsonlines,
+                                                     vmn_garrays_from_textlines)
     const uint32_t* / uint32_t*         int[]       (permutation tables)
     int* / size_t* / long* / double*    int[] / long[] / long[] / double[]   (verdicts, counts, timings)
     const char* / char*                 String / byte[]
@@ -50,13 +51,14 @@ BULK = {"vmn_garray_from_be": ["be"], "vmn_rarray_from_be": ["be"], "vmn_garray_
         "vmn_rarray_from_bytetree": ["bt"], "vmn_msg_to_bytetree": ["out"], "vmn_msg_from_bytetree": ["bt"],
         "vmn_garrays_from_hexlines": ["text"], "vmn_garrays_to_hexlines": ["out"],
         "vmn_garrays_from_hexlines_keyed": ["text"], "vmn_garrays_to_hexlines_keyed": ["out"], "vmn_msg_from_bytetree_keyed": ["bt"],
-        "vmn_garrays_from_jsonlines": ["text"], "vmn_garrays_to_jsonlines": ["out"], "vmn_garrays_to_jsonplain": ["out"]}
+        "vmn_garrays_from_jsonlines": ["text"], "vmn_garrays_to_jsonlines": ["out"], "vmn_garrays_to_jsonplain": ["out"],
+        "vmn_garrays_from_textlines": ["text"], "vmn_garrays_to_textlines": ["out"]}
 # objects created with a random source keep calling it: the bridge lives until the object's _free
 RS_OWNERS = {"vmn_pos_create": "vmn_pos_free", "vmn_posc_create": "vmn_posc_free", "vmn_ccpos_create": "vmn_ccpos_free",
              "vmn_decproof_create": "vmn_decproof_free", "vmn_igen_create": "vmn_igen_free"}
 # `const char*` is a String elsewhere (a curve name, a family); these are whole files of `len` bytes: byte[] / direct buffers, sized
 TEXT_AS_BYTES = {("vmn_garrays_from_hexlines", "text"): "bytes_in", ("vmn_garrays_from_jsonlines", "text"): "bytes_in",
-                 ("vmn_garrays_from_hexlines_keyed", "text"): "bytes_in"}
+                 ("vmn_garrays_from_hexlines_keyed", "text"): "bytes_in", ("vmn_garrays_from_textlines", "text"): "bytes_in"}
 HAND_WRITTEN = {"vmn_msg_item_bytes"}          # const uint8_t** result: returns a byte[] (see the template below)
 
 
@@ -195,12 +197,16 @@ def need_expr(name, ptype, pname, plist):
             return "2 * (size_t)width"
         if name == "vmn_garrays_from_hexlines_keyed" and pname == "out":
             return "2 * (size_t)keywidth * (size_t)width"
+        if name == "vmn_garrays_from_textlines" and pname == "out":       # the components of a list of plaintexts
+            return "(size_t)ncomp"
         return {"wp_out": "2 * (size_t)width", "factors_out": "2 * (size_t)width", "s_out": "(size_t)width"}.get(pname, "1")
     if k == "handles_in":
         if pname in ("xs", "ys"):
             return "(size_t)k"
         if name == "vmn_garrays_to_jsonplain" and pname == "comps":     # a list of plaintexts: width arrays
             return "(size_t)width"
+        if name == "vmn_garrays_to_textlines" and pname == "comps":
+            return "(size_t)ncomp"
         if name.endswith("_keyed") and pname == "comps":                # a list under a key of width keywidth
             return "2 * (size_t)keywidth * (size_t)width"
         if pname in ("w", "wp", "w_full", "factors", "comps"):
@@ -273,7 +279,7 @@ def need_expr(name, ptype, pname, plist):
             return "vmn_garrays_hexlines_size((const vmn_garray* const*)c_comps, (size_t)width)"
         if name == "vmn_garrays_to_hexlines_keyed" and pname == "out":
             return "vmn_garrays_hexlines_size_keyed((const vmn_garray* const*)c_comps, (size_t)keywidth, (size_t)width)"
-        if name in ("vmn_garrays_to_jsonlines", "vmn_garrays_to_jsonplain") and pname == "out":
+        if name in ("vmn_garrays_to_jsonlines", "vmn_garrays_to_jsonplain", "vmn_garrays_to_textlines") and pname == "out":
             return "(size_t)cap"
         if name == "vmn_prg_bytes" and pname == "out":
             return "(size_t)nbytes"

@@ -72,10 +72,13 @@
                                                                       vmn::u32, const vmn::u32*, vmn::u32);
 
 // subgroup membership: one element per lane (LPE = 1) or the element's own lanes (LPE > 1, base geometries only)
-#define VMN_MEMBER_INSTANCE_ONE_LANE(KW, S_, LPE_) \
-    KW __global__ void vmn::k_jacobi_member<vmn::Cfg<S_, LPE_>>(const vmn::u32*, size_t, const vmn::u32*, vmn::u32*);
-#define VMN_MEMBER_INSTANCE_LANES(KW, S_, LPE_) \
-    KW __global__ void vmn::k_jacobi_member_lanes<vmn::Cfg<S_, LPE_>>(const vmn::u32*, size_t, const vmn::u32*, vmn::u32*);
+// (with each, the residue fix of the safe-prime encoding in the same geometry: k_jacobi_fix / k_jacobi_fix_lanes)
+#define VMN_MEMBER_INSTANCE_ONE_LANE(KW, S_, LPE_)                                                                      \
+    KW __global__ void vmn::k_jacobi_member<vmn::Cfg<S_, LPE_>>(const vmn::u32*, size_t, const vmn::u32*, vmn::u32*); \
+    KW __global__ void vmn::k_jacobi_fix<vmn::Cfg<S_, LPE_>>(vmn::u32*, size_t, const vmn::u32*);
+#define VMN_MEMBER_INSTANCE_LANES(KW, S_, LPE_)                                                                               \
+    KW __global__ void vmn::k_jacobi_member_lanes<vmn::Cfg<S_, LPE_>>(const vmn::u32*, size_t, const vmn::u32*, vmn::u32*); \
+    KW __global__ void vmn::k_jacobi_fix_lanes<vmn::Cfg<S_, LPE_>>(vmn::u32*, size_t, const vmn::u32*);
 
 // The geometries (limbs, packed words, lanes per element; see VMN_FOR_SIZES in vmnhip.hip), grouped into the instantiation units
 #define VMN_UNIT_SMALL(KW)                                                                                             \

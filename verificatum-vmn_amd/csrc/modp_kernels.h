@@ -1342,17 +1342,13 @@ k_bucket_level(u32* __restrict__ out, size_t out_stride, LevelInputs ins, unsign
 // (zero included).  ref: the membership test VCR makes when an array is read (pGroup.toElementArray), e.g.
 // P/hvzk/PoSBasicTW.java:787-792.
 // ---------------------------------------------------------------------------------------------
+// The row of element ec and the modulus, all S limbs of each in ONE lane's registers (2 S <= 148 VGPRs).  (The loads also read
+// the two-share layout of Cfg<110, 2>; 3072-bit moduli use the lanes form since that proved three times faster.)
 template <class C>
-__global__ void __launch_bounds__(BLOCK, 2)
-k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmod, u32* __restrict__ flags) {
-    // ONE lane holds the whole element: a and m in registers (2 S <= 148 VGPRs), updated in place.  (The loads below also
-    // read the two-share layout of Cfg<110, 2>; 3072-bit moduli use k_jacobi_member_lanes since that proved three times faster.)
+__device__ __forceinline__ void jacobi_load_one_lane(u32 (&a)[C::S], u32 (&m)[C::S], const u32* __restrict__ x, size_t ec,
+                                                     const u32* __restrict__ nmod) {
     static_assert(C::LPE <= 2, "the element must fit one lane");
-    constexpr int S = C::S, L = C::L, LW = C::LW;
-    size_t el = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    bool live = el < n;
-    size_t ec = live ? el : n - 1;
-    u32 a[S], m[S];
+    constexpr int L = C::L, LW = C::LW;
 #pragma unroll
     for (int h = 0; h < C::LPE; ++h) {
         const uint4* q = reinterpret_cast<const uint4*>(x + ec * C::W + h * LW);
@@ -1366,7 +1362,16 @@ k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmo
             if (4 * k + 3 < L) { a[h * L + 4 * k + 3] = v.w; m[h * L + 4 * k + 3] = w.w; }
         }
     }
-    u32 t = 0;                                   // parity of the sign flips: symbol = (-1)^t
+}
+// The Jacobi symbol (a / m): 1, -1, or 0 when the two share a factor (a = 0 included); m odd, 0 <= a < m.  The binary algorithm
+// in place: both arrays are destroyed.  The one copy of the loop for one lane per element (k_jacobi_member, k_jacobi_fix).
+// The registers hold a and m and little else at 74 limbs: the parity is a predicate, not a vector register, and the limb passes
+// are scheduled eight limbs at a time (sched_barrier) -- free to reorder a whole pass the compiler spills.  The same form in
+// every geometry: with the parity a word and no pacing below 20 limbs, hipcc (ROCm 7.2) compiled the comparison chain of
+// Cfg<10, 1> to read limb 6 from a register it had just reused for the borrow (tests/test_gpu_jacobi_edges.py, 256 bits, found it).
+template <int S>
+__device__ __forceinline__ int jacobi_symbol(u32 (&a)[S], u32 (&m)[S]) {
+    bool t = false;                              // parity of the sign flips: symbol = (-1)^t (a predicate: no vector register)
     u32 nz = 0;
 #pragma unroll
     for (int j = 0; j < S; ++j) nz |= a[j];
@@ -1384,11 +1389,12 @@ k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmo
         int k = __builtin_ctz(low);
         if (k) {
             u32 m8 = m[0] & 7u;
-            if ((k & 1) && (m8 == 3u || m8 == 5u)) t ^= 1u;
+            if ((k & 1) && (m8 == 3u || m8 == 5u)) t = !t;
 #pragma unroll
             for (int j = 0; j < S; ++j) {
                 u32 hi = j + 1 < S ? a[j + 1] : 0u;
                 a[j] = ((a[j] >> k) | (hi << (LIMB_BITS - k))) & LIMB_MASK;
+                if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);
             }
         }
         // a odd now: compare (borrow of a - m), then subtract in place in the right direction
@@ -1402,9 +1408,10 @@ k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmo
                 int32_t v = (int32_t)a[j] - (int32_t)m[j] + c;
                 a[j] = (u32)v & LIMB_MASK;
                 c = v >> LIMB_BITS;
+                if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);
             }
         } else {                                 // a < m: swap by reciprocity, (a, m) := (m - a, a)
-            if ((a[0] & 3u) == 3u && (m[0] & 3u) == 3u) t ^= 1u;
+            if ((a[0] & 3u) == 3u && (m[0] & 3u) == 3u) t = !t;
             int32_t c = 0;
 #pragma unroll
             for (int j = 0; j < S; ++j) {
@@ -1413,6 +1420,7 @@ k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmo
                 a[j] = (u32)v & LIMB_MASK;
                 c = v >> LIMB_BITS;
                 m[j] = old;
+                if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);
             }
         }
         nz = 0;
@@ -1423,7 +1431,18 @@ k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmo
     u32 rest = m[0] ^ 1u;
 #pragma unroll
     for (int j = 1; j < S; ++j) rest |= m[j];
-    bool member = !zero_in && rest == 0 && t == 0;
+    return (zero_in || rest != 0) ? 0 : t ? -1 : 1;
+}
+template <class C>
+__global__ void __launch_bounds__(BLOCK, 2)
+k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmod, u32* __restrict__ flags) {
+    // ONE lane holds the whole element: a and m in registers, updated in place
+    size_t el = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    bool live = el < n;
+    size_t ec = live ? el : n - 1;
+    u32 a[C::S], m[C::S];
+    jacobi_load_one_lane<C>(a, m, x, ec, nmod);
+    bool member = jacobi_symbol<C::S>(a, m) == 1;
     if (live && !member) atomicOr(flags, 1u);
 }
 
@@ -1431,19 +1450,14 @@ k_jacobi_member(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmo
 // lanes of an element run the binary algorithm in lockstep: every decision is taken from lane 0's low limbs (broadcast),
 // the right shifts pull the next lane's low limb in (DPP), comparison and subtraction are the element-wide borrow chains
 // of canonicalize() (sub_full: LPE sweeps).  ~1200 instructions per step, at most 2 * bits(p) steps: a tenth of x^q.
+// (jacobi_symbol_lanes: the one copy of that loop -- k_jacobi_member_lanes, k_jacobi_fix_lanes; the symbol on every lane of the
+// element, a and m destroyed)
 template <class C>
-__global__ void __launch_bounds__(BLOCK, 2)
-k_jacobi_member_lanes(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmod, u32* __restrict__ flags) {
-    static_assert(C::LPE > 1 && !C::WIDE, "one lane per element uses k_jacobi_member");
+__device__ __forceinline__ int jacobi_symbol_lanes(u32 (&a)[C::L], u32 (&m)[C::L], const Lane<C>& ln) {
+    static_assert(C::LPE > 1 && !C::WIDE, "one lane per element uses jacobi_symbol");
     constexpr int L = C::L, LPE = C::LPE;
-    Lane<C> ln(nullptr);
-    size_t el = (size_t)blockIdx.x * C::EPB + ln.eslot;
-    bool live = el < n;
-    size_t ec = live ? el : n - 1;
-    u32 a[L], m[L], d[L];
-    load_elem<C>(a, x + ec * C::W, ln);
-    load_modulus<C>(m, nmod, ln);
-    u32 t = 0;
+    u32 d[L];
+    bool t = false;
     auto any = [&](const u32 (&v)[L]) {
         u32 nz = 0;
 #pragma unroll
@@ -1465,7 +1479,7 @@ k_jacobi_member_lanes(const u32* __restrict__ x, size_t n, const u32* __restrict
         const int k = __builtin_ctz(low);
         if (k) {
             const u32 m8 = from_lane0<LPE>(m[0]) & 7u;
-            if ((k & 1) && (m8 == 3u || m8 == 5u)) t ^= 1u;
+            if ((k & 1) && (m8 == 3u || m8 == 5u)) t = !t;
 #pragma unroll
             for (int j = 0; j < L; ++j) {
                 const u32 hi = j + 1 < L ? a[j + 1] : up;
@@ -1478,7 +1492,7 @@ k_jacobi_member_lanes(const u32* __restrict__ x, size_t n, const u32* __restrict
             for (int j = 0; j < L; ++j) a[j] = d[j];
         } else {                                 // a < m: swap by reciprocity, (a, m) := (m - a, a)
             const u32 a0 = from_lane0<LPE>(a[0]), m0 = from_lane0<LPE>(m[0]);
-            if ((a0 & 3u) == 3u && (m0 & 3u) == 3u) t ^= 1u;
+            if ((a0 & 3u) == 3u && (m0 & 3u) == 3u) t = !t;
             sub_full<C>(d, m, a, ln);
 #pragma unroll
             for (int j = 0; j < L; ++j) {
@@ -1493,8 +1507,77 @@ k_jacobi_member_lanes(const u32* __restrict__ x, size_t n, const u32* __restrict
 #pragma unroll
     for (int j = 1; j < L; ++j) rest |= m[j];
     rest = or_all<LPE>(rest);
-    const bool member = !zero_in && rest == 0 && t == 0;
+    return (zero_in || rest != 0) ? 0 : t ? -1 : 1;
+}
+template <class C>
+__global__ void __launch_bounds__(BLOCK, 2)
+k_jacobi_member_lanes(const u32* __restrict__ x, size_t n, const u32* __restrict__ nmod, u32* __restrict__ flags) {
+    constexpr int L = C::L;
+    Lane<C> ln(nullptr);
+    size_t el = (size_t)blockIdx.x * C::EPB + ln.eslot;
+    bool live = el < n;
+    size_t ec = live ? el : n - 1;
+    u32 a[L], m[L];
+    load_elem<C>(a, x + ec * C::W, ln);
+    load_modulus<C>(m, nmod, ln);
+    const bool member = jacobi_symbol_lanes<C>(a, m, ln) == 1;
     if (live && ln.half == 0 && !member) atomicOr(flags, 1u);
+}
+
+// The residue fix of the safe-prime encoding (csrc/encode_layout.h): row i := p - row i where the Jacobi symbol of the row is -1,
+// in place, so that every row is a quadratic residue (-1 is none: p = 3 mod 4).  Rows are in Montgomery form: (R / p) = 1, and
+// negation is p - row in either form.  The symbol's loop destroys its copy of the row, which is therefore read again for the
+// store -- no second copy in registers.  A row whose symbol is 0 (zero; never an encoded value) stays.
+// (reread: the same address, but one the compiler knows nothing about -- it would otherwise keep the values of the first loads
+// alive across the loop, the second copy the registers have no room for, instead of loading them again)
+__device__ __forceinline__ const u32* reread(const u32* p) {
+    asm volatile("" : "+v"(p));
+    return p;
+}
+__device__ __forceinline__ const u32* reread_uniform(const u32* p) {         // (a wave-uniform address stays in scalar registers)
+    asm volatile("" : "+s"(p));
+    return p;
+}
+template <class C>
+__global__ void __launch_bounds__(BLOCK, 2)
+k_jacobi_fix(u32* __restrict__ x, size_t n, const u32* __restrict__ nmod) {
+    static_assert(C::LPE == 1, "one lane per element");
+    constexpr int S = C::S;
+    size_t el = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    bool live = el < n;
+    size_t ec = live ? el : n - 1;
+    u32 a[S], m[S];
+    jacobi_load_one_lane<C>(a, m, x, ec, nmod);
+    // (nothing of a lane's own is kept across the loop, which fills the registers: the element's index is put together again
+    // from the wave's first thread, a scalar, and the lane's number)
+    const u32 wave_first = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
+    if (jacobi_symbol<S>(a, m) != -1) return;
+    const u32 lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    el = (size_t)blockIdx.x * BLOCK + wave_first + lane;
+    if (el >= n) return;
+    Lane<C> ln(nullptr);
+    load_elem<C>(a, reread(x + el * C::W), ln);
+    load_modulus<C>(m, reread_uniform(nmod), ln);
+    borrow_sweep<S>(a, m, a, 0);                 // p - row, row < p
+    store_elem<C>(x + el * C::W, a, ln);
+}
+template <class C>
+__global__ void __launch_bounds__(BLOCK, 2)
+k_jacobi_fix_lanes(u32* __restrict__ x, size_t n, const u32* __restrict__ nmod) {
+    constexpr int L = C::L;
+    Lane<C> ln(nullptr);
+    size_t el = (size_t)blockIdx.x * C::EPB + ln.eslot;
+    bool live = el < n;
+    size_t ec = live ? el : n - 1;
+    u32 a[L], m[L];
+    load_elem<C>(a, x + ec * C::W, ln);
+    load_modulus<C>(m, nmod, ln);
+    const bool negate = jacobi_symbol_lanes<C>(a, m, ln) == -1;      // (the same on all lanes of the element)
+    load_elem<C>(a, reread(x + ec * C::W), ln);
+    load_modulus<C>(m, reread(nmod), ln);
+    u32 d[L];
+    sub_full<C>(d, m, a, ln);                    // every lane of the wave takes part in the cross-lane borrows
+    if (live && negate) store_elem<C>(x + el * C::W, d, ln);
 }
 
 }  // namespace vmn

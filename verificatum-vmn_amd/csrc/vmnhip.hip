@@ -17,6 +17,7 @@
 #include "ec_instances.h"
 #include "light_kernels.h"
 #include "decimal_kernels.h"
+#include "encode_kernels.h"
 #include "vmnhip_internal.h"
 #include "sha256.h"
 #include "sha512.h"
@@ -2498,6 +2499,151 @@ extern "C" int vmn_garrays_to_jsonplain(const vmn_garray* const* comps, size_t w
     ARG_CHECK(comps && written && jsonlines_width_ok(width), "null argument or width out of range");
     ARG_CHECK(jsonlines_comps_ok(comps, width), "width arrays of one group and one size are needed");
     return jsonlines_write(comps, width, 1, out, cap, written);
+}
+
+// ---- messages as group elements and back: the text interface behind a session (csrc/encode_layout.h, csrc/encode_kernels.h) -----
+// [NOT-IN-REF: VCR ModPGroup, safe-prime encoding; unpinned]
+static bool safe_prime_group(const vmn_group* g) {
+    if (!g || g->curve) return false;
+    Big twoq = g->Q.n_words;
+    hostbig::dbl_mod(twoq, g->P.n_words);
+    Big pm1 = g->P.n_words;
+    pm1[0] -= 1;
+    return hostbig::cmp(twoq, pm1) == 0;
+}
+extern "C" size_t vmn_group_encode_length(const vmn_group* grp) {
+    if (!safe_prime_group(grp)) return 0;
+    return encode::encode_length((size_t)hostbig::bit_length(grp->P.n_words));
+}
+static bool textlines_ncomp_ok(size_t ncomp) { return ncomp >= 1 && ncomp <= encode::MAX_COMPONENTS; }
+#define ENCODE_GROUP_CHECK(grp, L)                                                                                             \
+    do {                                                                                                                       \
+        if ((L) == 0) {                                                                                                        \
+            set_error("%s: messages are encoded over a modular group with p = 2q + 1 that holds at least one byte", __func__);  \
+            return VMN_ERR_UNSUPPORTED;                                                                                        \
+        }                                                                                                                      \
+    } while (0)
+
+extern "C" int vmn_garrays_from_textlines(vmn_group* grp, size_t ncomp, const char* text, size_t len, vmn_garray** out, size_t* n_out,
+                                          int* fits, size_t* first_long_line) {
+    ARG_CHECK(grp && out && n_out && fits && first_long_line && (text || len == 0), "null argument");
+    ARG_CHECK(textlines_ncomp_ok(ncomp), "ncomp out of range");
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    for (size_t c = 0; c < ncomp; ++c) out[c] = nullptr;
+    *n_out = 0;
+    *fits = 0;
+    *first_long_line = 0;
+    const size_t L = vmn_group_encode_length(grp), nbytes = grp->nbytes;
+    ENCODE_GROUP_CHECK(grp, L);
+    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
+
+    TextLines lines(ctx, "textlines");
+    VMN_TRY(lines.count(ctx, utext, len));
+    const size_t nlines = lines.nlines, total = nlines * ncomp;
+
+    // text -> records of all components, the longest admissible line checked on the way
+    DevTmp rec(ctx);
+    if (nlines) {
+        ARG_CHECK(total / ncomp == nlines && total < ((size_t)1 << 40), "too many elements");
+        const size_t blocks = (total * TEXTLINES_LANES + BLOCK - 1) / BLOCK;
+        ARG_CHECK(blocks < ((size_t)1 << 31), "too many elements");
+        VMN_TRY(rec.alloc(total * nbytes + 16));
+        VMN_TRY(lines.walk(ctx));
+        VMN_TRY(launch_light(ctx, "textlines", k_textlines_records, (unsigned)blocks, rec.as<uint8_t>(), lines.text(), (const u64*)lines.starts.p,
+                             (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)ncomp, (uint32_t)nbytes, (uint32_t)L, lines.first_bad()));
+        uint32_t bad = 0;
+        VMN_TRY(lines.read_first_bad(ctx, &bad));
+        if (bad != 0xffffffffu) {
+            *first_long_line = bad;
+            return VMN_OK;
+        }
+    }
+
+    // the records through the import kernel, then v or p - v by the Jacobi symbol of every row, in place
+    std::vector<vmn_garray*> arrays(ncomp, nullptr);
+    int rc = VMN_OK;
+    for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    const vmn_modulus& m = grp->P;
+    for (size_t c = 0; c < ncomp && rc == VMN_OK && nlines; ++c) {
+        note_work(ctx, m, (double)nlines);
+        rc = import_rows_launch(ctx, m, nbytes, rec.as<uint8_t>() + c * nlines * nbytes, nbytes, 0, nlines, arrays[c]->d);
+        if (rc == VMN_OK)
+            rc = with_cfg(m, [&]<class C, class W>(C, W) -> int {
+                if constexpr (C::LPE == 1)
+                    return launch_light(ctx, "encode_residue", k_jacobi_fix<C>, grid_for(nlines), arrays[c]->d, nlines, (const uint32_t*)m.d_n);
+                else if constexpr (!C::WIDE)
+                    return launch_light(ctx, "encode_residue", k_jacobi_fix_lanes<C>, egrid(m, nlines), arrays[c]->d, nlines,
+                                        (const uint32_t*)m.d_n);
+                else
+                    return VMN_ERR_ARG;
+            });
+    }
+    if (rc != VMN_OK) {
+        for (vmn_garray* a : arrays) vmn_garray_free(a);
+        return rc;
+    }
+    for (size_t c = 0; c < ncomp; ++c) out[c] = arrays[c];
+    *n_out = nlines;
+    *fits = 1;
+    return VMN_OK;
+}
+
+extern "C" int vmn_garrays_to_textlines(const vmn_garray* const* comps, size_t ncomp, char* out, size_t cap, size_t* written, int* all_wellformed,
+                                        int* all_utf8) {
+    ARG_CHECK(comps && written && textlines_ncomp_ok(ncomp), "null argument or ncomp out of range");
+    ARG_CHECK(jsonlines_comps_ok(comps, ncomp), "ncomp arrays of one group and one size are needed");
+    vmn_group* grp = comps[0]->grp;
+    const size_t n = comps[0]->n, nbytes = grp->nbytes;
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    *written = 0;
+    if (all_wellformed) *all_wellformed = 1;
+    if (all_utf8) *all_utf8 = 1;
+    const size_t L = vmn_group_encode_length(grp);
+    ENCODE_GROUP_CHECK(grp, L);
+    if (n == 0) return VMN_OK;
+    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
+    const size_t total = n * ncomp;
+    ARG_CHECK(total / ncomp == n && total < ((size_t)1 << 40), "too many elements");
+    // p and q as records, for the fold
+    std::vector<uint8_t> primes(2 * nbytes);
+    hostbig::to_be(grp->P.n_words, primes.data(), nbytes);
+    {
+        Big q = grp->Q.n_words;
+        q.resize(grp->P.n_words.size(), 0);
+        hostbig::to_be(q, primes.data() + nbytes, nbytes);
+    }
+    const size_t groups = (n + BLOCK - 1) / BLOCK;
+    DevTmp rec(ctx), dprimes(ctx), plen(ctx), lens(ctx), bsum(ctx), dtext(ctx);
+    VMN_TRY(rec.alloc(total * nbytes + 16));
+    VMN_TRY(dprimes.alloc(primes.size()));
+    VMN_TRY(plen.alloc(total * sizeof(uint32_t)));
+    VMN_TRY(lens.alloc(n * sizeof(uint32_t)));
+    VMN_TRY(bsum.alloc((groups + 1) * sizeof(uint64_t)));
+    VMN_TRY(h2d(ctx, dprimes.p, primes.data(), primes.size()));
+    VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
+    for (size_t c = 0; c < ncomp; ++c) VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, rec.as<uint8_t>() + c * n * nbytes, nbytes, 0));
+    VMN_TRY(launch_light(ctx, "textlines", k_textlines_fold, grid_for(total), rec.as<uint8_t>(), plen.as<uint32_t>(), total, (uint32_t)nbytes,
+                         (uint32_t)L, (const uint8_t*)dprimes.as<uint8_t>(), (const uint8_t*)dprimes.as<uint8_t>() + nbytes, ctx->flags));
+    VMN_TRY(launch_light(ctx, "textlines", k_textlines_lengths, (unsigned)groups, lens.as<uint32_t>(), (u64*)bsum.p,
+                         (const uint8_t*)rec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n, (uint32_t)ncomp, (uint32_t)nbytes,
+                         (uint32_t)L, ctx->flags));
+    VMN_TRY(launch_light(ctx, "textlines", k_jsonlines_offsets, 1u, (u64*)bsum.p, groups, (u64*)bsum.p + groups));
+    uint64_t text_bytes = 0;
+    VMN_TRY(d2h(ctx, &text_bytes, (const u64*)bsum.p + groups, sizeof(text_bytes)));
+    ARG_CHECK(text_bytes <= cap && out, "the buffer is too small for these lines");
+    VMN_TRY(dtext.alloc(text_bytes + 16));
+    VMN_TRY(launch_light(ctx, "textlines", k_textlines_emit, (unsigned)groups, dtext.as<uint8_t>(), (const u64*)bsum.p,
+                         (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)rec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n,
+                         (uint32_t)ncomp, (uint32_t)nbytes, (uint32_t)L));
+    uint32_t fl = 0;
+    VMN_TRY(read_flag(ctx, &fl));
+    VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));
+    *written = (size_t)text_bytes;
+    if (all_wellformed) *all_wellformed = (fl & TEXTLINES_ILL_FORMED) ? 0 : 1;
+    if (all_utf8) *all_utf8 = (fl & TEXTLINES_NOT_UTF8) ? 0 : 1;
+    return VMN_OK;
 }
 
 extern "C" int vmn_garray_to_be(const vmn_garray* a, uint8_t* be_out) {

@@ -18,6 +18,13 @@ The json text is converted from and to decimal on the GPU as well (``vmn_garrays
 apply one policy to what enters here from outside: a format defect, a value out of range or an element outside the group is no
 list (``None``).
 
+Behind a session the plaintexts are text (``vmnc -plain -outi native``, ProtocolElGamalInterfaceString.decodePlaintexts): a
+message of up to ``encode_length`` bytes per component is an element of a safe-prime group (csrc/encode_layout.h states the
+encoding).  ``encode_texts`` / ``decode_texts`` convert whole lists on the GPU (``vmn_garrays_from_textlines`` /
+``vmn_garrays_to_textlines``, csrc/encode_kernels.h), ``read_texts`` / ``write_decoded_plaintexts`` are their file functions, and
+``demo_texts`` / ``demo_ciphertexts`` are the reference's dummy messages and their encryptions.  ``write_plaintexts`` and
+``PLAINTEXT_FORMATS`` keep to ``json`` and ``raw``.
+
 Under a public key of width kappa (``keywidth``, 1 by default) a ciphertext of ``width`` omega has 2 kappa omega components and
 every half of a list or of a line one more node level (``proofdir``'s head, ``vmn_garrays_from_hexlines_keyed``); ``native`` and
 ``raw`` take it, ``json`` does not: the reference's JSON classes cast the components to elements of a modular group, so they
@@ -295,3 +302,84 @@ def read_public_key_json(path: str) -> dict:
     if not (0 < y < p and pow(y, q, p) == 1):
         raise ValueError("no json public key: y is not in the group")
     return {"p": p, "q": q, "g": g, "y": y, "encoding": encoding}
+
+
+# ---- plaintexts as text: messages encoded as group elements (csrc/encode_layout.h) ------------------------------------------------
+def encode_length(grp) -> int:
+    """L: the bytes of a message one element of ``grp`` holds (``pGroup.getEncodeLength()``): floor((bits(p) - 2) / 8) - 4 over a
+    modular group with p = 2q + 1; 0 over every other group, which ``encode_texts`` / ``decode_texts`` refuse."""
+    return lib().vmn_group_encode_length(grp._h)
+
+
+def encode_texts(grp, text, ncomp: int = 1, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+    """The ``ncomp`` arrays that hold the lines of ``text`` (``bytes`` or a host buffer object), line i cut into pieces of
+    ``encode_length`` bytes over the components of element i; ``None`` when a line has more than ncomp * L bytes.  Lines end
+    with \\n, \\r or \\r\\n; an empty line is the empty message.  ``report`` receives ``fits``, ``first_long_line``
+    (zero-based; only meaningful when ``fits`` is false) and ``lines``."""
+    blk = host_block(text) or host_block(bytes(text))
+    hs = (C.c_void_p * ncomp)()
+    n, long_line, fits = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+    _check(lib().vmn_garrays_from_textlines(grp._h, C.c_size_t(ncomp), blk[0], C.c_size_t(blk[1]), hs, C.byref(n), C.byref(fits),
+                                            C.byref(long_line)))
+    if report is not None:
+        report.update(fits=bool(fits.value), first_long_line=long_line.value, lines=n.value)
+    if not fits.value:
+        return None
+    return [PGroupElementArray(grp, C.c_void_p(h)) for h in hs]
+
+
+def decode_texts(comps: Sequence[PGroupElementArray], report: Optional[dict] = None) -> bytes:
+    """decodePlaintexts: one line per element -- the messages of its components one after the other, \\n and \\r removed, then
+    \\n.  ``report`` receives ``all_wellformed`` (no element without a message: such a one gives an empty piece) and
+    ``all_utf8`` (every line well-formed UTF-8 before the removal; a line that is not is written byte for byte)."""
+    if not comps:
+        raise ValueError("no arrays")
+    grp, n = comps[0].group, comps[0].size()
+    hs = (C.c_void_p * len(comps))(*[a._h for a in comps])
+    cap = max(1, n * (len(comps) * encode_length(grp) + 1))
+    out = C.create_string_buffer(cap)
+    written, wf, utf8 = C.c_size_t(0), C.c_int(1), C.c_int(1)
+    _check(lib().vmn_garrays_to_textlines(hs, C.c_size_t(len(comps)), out, C.c_size_t(cap), C.byref(written), C.byref(wf), C.byref(utf8)))
+    if report is not None:
+        report.update(all_wellformed=bool(wf.value), all_utf8=bool(utf8.value))
+    return out.raw[:written.value]
+
+
+def write_decoded_plaintexts(path: str, comps: Sequence[PGroupElementArray]) -> None:
+    """``vmnc -plain -outi native``: the list of plaintexts given as its component arrays, as lines of text."""
+    data = decode_texts(comps)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def read_texts(grp, path: str, ncomp: int, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+    """The lines of the file at ``path`` as ``ncomp`` arrays; ``None`` when it is missing or a line does not fit."""
+    buf = proofdir._read_file(path)
+    if buf is None:
+        return None
+    return encode_texts(grp, buf, ncomp, report)
+
+
+def demo_texts(n: int, ncomp_L: int) -> bytes:
+    """The reference's dummy messages (ProtocolElGamalInterfaceString.java:315-372) for elements that hold ``ncomp_L`` bytes: line
+    i is the decimal i zero-padded to the full encode length when ``len(str(n))`` fits it, else the letter chr(65 + i % 26)."""
+    if len(str(n)) <= ncomp_L:
+        return b"".join(b"%0*d\n" % (ncomp_L, i) for i in range(n))
+    return b"".join(b"%c\n" % (65 + i % 26) for i in range(n))
+
+
+def demo_ciphertexts(grp, y, n: int, rand, width: int = 1) -> List[PGroupElementArray]:
+    """demoCiphertexts (:374-428): the ``n`` dummy messages encrypted under the key (g, ``y``): u = g^r, v = y^r encode(text), the
+    exponents from ``rand`` (``ring_array(n)``, once per component).  Returns the 2 * width arrays u_1..u_w, v_1..v_w."""
+    msgs = encode_texts(grp, demo_texts(n, width * encode_length(grp)), width)
+    if msgs is None:
+        raise ValueError("the group holds no message")
+    us, vs = [], []
+    for m in msgs:
+        r = grp.ringArray(rand.ring_array(n))
+        t = grp.exp(y, r)
+        us.append(grp.exp(grp.g, r))
+        vs.append(t.mul(m))
+        for a in (r, t, m):
+            a.free()
+    return us + vs
