@@ -247,12 +247,32 @@ int vmn_garrays_to_jsonplain(const vmn_garray* const* comps, size_t width, char*
  * *all_wellformed = 0 when some element was ill-formed; *all_utf8 = 0 when some line's concatenation, BEFORE the removal (Java
  * decodes, then strips), is not well-formed UTF-8 (Unicode table 3-7) -- such a line is written byte for byte [NOT-IN-REF: Java
  * substitutes U+FFFD].  Both may be NULL.  *written receives the bytes written; no NUL; VMN_ERR_ARG, writing nothing, when cap is
- * too small for these lines: a cap of n (ncomp L + 1) always suffices.  Never writes behind cap. */
+ * too small for these lines: a cap of n (ncomp L + 1) always suffices.  Never writes behind cap.
+ * Over a curve group the same interface is vmn_ec_group_encode_length / vmn_ec_arrays_from_textlines / _to_textlines, below. */
 size_t vmn_group_encode_length(const vmn_group* grp);
 int vmn_garrays_from_textlines(vmn_group* grp, size_t ncomp, const char* text, size_t len, vmn_garray** out, size_t* n_out, int* fits,
                                size_t* first_long_line);
 int vmn_garrays_to_textlines(const vmn_garray* const* comps, size_t ncomp, char* out, size_t cap, size_t* written, int* all_wellformed,
                              int* all_utf8);
+/* The same over curve groups: a message is a point.  [NOT-IN-REF: VCR ECqPGroup; unpinned -- csrc/ec_encode_layout.h states the
+ * rule built here, on integers.]
+ * vmn_ec_group_encode_length: L = floor((bits(p) - 2) / 8) - 5 for the field prime p of a curve group (18 / 22 / 24 / 26 / 34 / 42 /
+ * 58 / 59 at 192 / 224 / 239 / 256 / 320 / 384 / 512 / 521 bits) when that is at least 1; 0 for a modular group and a null group, over
+ * which the two functions below return VMN_ERR_UNSUPPORTED.
+ * A point holds T = be32(len) || message || zeros on L + 4 bytes (the empty message with a 1 behind the length) in its x coordinate:
+ * x = 256 T + c with c the least counter in 0..255 for which x^3 + a x + b is a nonzero square mod p, y the smaller of the two
+ * roots as integers (one Jacobi symbol per counter and one square root per point, on the GPU).  Decoding reads x alone: the point
+ * is ill-formed, its message empty, when it is the point at infinity, when x >= 2^(8 (L + 5)) or when the length word of
+ * floor(x / 256) exceeds L; the counter byte and y are ignored.
+ * Arguments, results and contracts are those of vmn_garrays_from_textlines / _to_textlines word for word (fits and
+ * first_long_line, all_wellformed and all_utf8, a cap of n (ncomp L + 1) always suffices, never a byte behind cap, nothing left
+ * allocated on failure, ncomp in 1..65536).  Should no counter of the 256 fit a record (chance 2^-256), from_textlines returns
+ * VMN_ERR_FORMAT and names the line in vmn_last_error(). */
+size_t vmn_ec_group_encode_length(const vmn_group* grp);
+int vmn_ec_arrays_from_textlines(vmn_group* grp, size_t ncomp, const char* text, size_t len, vmn_garray** out, size_t* n_out, int* fits,
+                                 size_t* first_long_line);
+int vmn_ec_arrays_to_textlines(const vmn_garray* const* comps, size_t ncomp, char* out, size_t cap, size_t* written, int* all_wellformed,
+                               int* all_utf8);
 size_t vmn_garray_size(const vmn_garray* a);
 /* the group an array belongs to (PGroupElementArray.getPGroup(), PRingElementArray.getPRing()): a binding sizes the host
  * buffers of vmn_*_to_be / _get / _prod ... from it (jni/: every byte[] is checked against the bytes the callee touches) */

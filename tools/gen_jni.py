@@ -13,7 +13,7 @@ The wrappers are mechanical (the C ABI was designed for it: opaque pointers, pla
     const vmn_Xarray* const*            long[]
     const uint8_t* / uint8_t*           byte[]      (big-endian rows, byte trees; results are written back)
     const char* text, size_t len        byte[]      (a whole text file: vmn_garrays_from_hexlines, vmn_garrays_from_jsonlines,
-                                                     vmn_garrays_from_textlines)
+                                                     vmn_garrays_from_textlines, vmn_ec_arrays_from_textlines)
     const uint32_t* / uint32_t*         int[]       (permutation tables)
     int* / size_t* / long* / double*    int[] / long[] / long[] / double[]   (verdicts, counts, timings)
     const char* / char*                 String / byte[]
@@ -52,13 +52,15 @@ BULK = {"vmn_garray_from_be": ["be"], "vmn_rarray_from_be": ["be"], "vmn_garray_
         "vmn_garrays_from_hexlines": ["text"], "vmn_garrays_to_hexlines": ["out"],
         "vmn_garrays_from_hexlines_keyed": ["text"], "vmn_garrays_to_hexlines_keyed": ["out"], "vmn_msg_from_bytetree_keyed": ["bt"],
         "vmn_garrays_from_jsonlines": ["text"], "vmn_garrays_to_jsonlines": ["out"], "vmn_garrays_to_jsonplain": ["out"],
-        "vmn_garrays_from_textlines": ["text"], "vmn_garrays_to_textlines": ["out"]}
+        "vmn_garrays_from_textlines": ["text"], "vmn_garrays_to_textlines": ["out"],
+        "vmn_ec_arrays_from_textlines": ["text"], "vmn_ec_arrays_to_textlines": ["out"]}
 # objects created with a random source keep calling it: the bridge lives until the object's _free
 RS_OWNERS = {"vmn_pos_create": "vmn_pos_free", "vmn_posc_create": "vmn_posc_free", "vmn_ccpos_create": "vmn_ccpos_free",
              "vmn_decproof_create": "vmn_decproof_free", "vmn_igen_create": "vmn_igen_free"}
 # `const char*` is a String elsewhere (a curve name, a family); these are whole files of `len` bytes: byte[] / direct buffers, sized
 TEXT_AS_BYTES = {("vmn_garrays_from_hexlines", "text"): "bytes_in", ("vmn_garrays_from_jsonlines", "text"): "bytes_in",
-                 ("vmn_garrays_from_hexlines_keyed", "text"): "bytes_in", ("vmn_garrays_from_textlines", "text"): "bytes_in"}
+                 ("vmn_garrays_from_hexlines_keyed", "text"): "bytes_in", ("vmn_garrays_from_textlines", "text"): "bytes_in",
+                 ("vmn_ec_arrays_from_textlines", "text"): "bytes_in"}
 HAND_WRITTEN = {"vmn_msg_item_bytes"}          # const uint8_t** result: returns a byte[] (see the template below)
 
 
@@ -197,7 +199,7 @@ def need_expr(name, ptype, pname, plist):
             return "2 * (size_t)width"
         if name == "vmn_garrays_from_hexlines_keyed" and pname == "out":
             return "2 * (size_t)keywidth * (size_t)width"
-        if name == "vmn_garrays_from_textlines" and pname == "out":       # the components of a list of plaintexts
+        if name in ("vmn_garrays_from_textlines", "vmn_ec_arrays_from_textlines") and pname == "out":       # the components of a list of plaintexts
             return "(size_t)ncomp"
         return {"wp_out": "2 * (size_t)width", "factors_out": "2 * (size_t)width", "s_out": "(size_t)width"}.get(pname, "1")
     if k == "handles_in":
@@ -205,7 +207,7 @@ def need_expr(name, ptype, pname, plist):
             return "(size_t)k"
         if name == "vmn_garrays_to_jsonplain" and pname == "comps":     # a list of plaintexts: width arrays
             return "(size_t)width"
-        if name == "vmn_garrays_to_textlines" and pname == "comps":
+        if name in ("vmn_garrays_to_textlines", "vmn_ec_arrays_to_textlines") and pname == "comps":
             return "(size_t)ncomp"
         if name.endswith("_keyed") and pname == "comps":                # a list under a key of width keywidth
             return "2 * (size_t)keywidth * (size_t)width"
@@ -279,7 +281,7 @@ def need_expr(name, ptype, pname, plist):
             return "vmn_garrays_hexlines_size((const vmn_garray* const*)c_comps, (size_t)width)"
         if name == "vmn_garrays_to_hexlines_keyed" and pname == "out":
             return "vmn_garrays_hexlines_size_keyed((const vmn_garray* const*)c_comps, (size_t)keywidth, (size_t)width)"
-        if name in ("vmn_garrays_to_jsonlines", "vmn_garrays_to_jsonplain", "vmn_garrays_to_textlines") and pname == "out":
+        if name in ("vmn_garrays_to_jsonlines", "vmn_garrays_to_jsonplain", "vmn_garrays_to_textlines", "vmn_ec_arrays_to_textlines") and pname == "out":
             return "(size_t)cap"
         if name == "vmn_prg_bytes" and pname == "out":
             return "(size_t)nbytes"

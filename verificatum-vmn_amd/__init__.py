@@ -83,7 +83,7 @@ def lib() -> C.CDLL:
         for name in ("vmn_group_elem_bytes", "vmn_group_exp_bytes", "vmn_garray_size", "vmn_rarray_size", "vmn_group_table_bytes",
                      "vmn_garray_bytetree_size", "vmn_rarray_bytetree_size", "vmn_pending_bytes", "vmn_hexlines_line_bytes",
                      "vmn_garrays_hexlines_size", "vmn_jsonlines_max_line_bytes", "vmn_hexlines_line_bytes_keyed",
-                     "vmn_garrays_hexlines_size_keyed", "vmn_group_encode_length"):
+                     "vmn_garrays_hexlines_size_keyed", "vmn_group_encode_length", "vmn_ec_group_encode_length"):
             getattr(_lib, name).restype = C.c_size_t
     return _lib
 

@@ -18,6 +18,7 @@
 #include "light_kernels.h"
 #include "decimal_kernels.h"
 #include "encode_kernels.h"
+#include "ec_encode_kernels.h"
 #include "vmnhip_internal.h"
 #include "sha256.h"
 #include "sha512.h"
@@ -1043,6 +1044,8 @@ struct CurveParams {
     const char* gy;
     const char* a = nullptr;   // curve coefficient a (absent: a = -3, the NIST curves)
 };
+// Every curve of this table has cofactor 1 (tests/test_point_encode_catalogue.py asks libcrypto): a point on the curve is a group
+// element, which the message encoding over curves relies on (csrc/ec_encode_layout.h: any x on the curve will do).
 static const CurveParams kCurves[] = {
     {"P-224", 224, 9, 7, "ffffffffffffffffffffffffffffffff000000000000000000000001",
      "ffffffffffffffffffffffffffff16a2e0b8f03e13dd29455c5c2a3d",
@@ -2637,6 +2640,145 @@ extern "C" int vmn_garrays_to_textlines(const vmn_garray* const* comps, size_t n
     VMN_TRY(launch_light(ctx, "textlines", k_textlines_emit, (unsigned)groups, dtext.as<uint8_t>(), (const u64*)bsum.p,
                          (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)rec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n,
                          (uint32_t)ncomp, (uint32_t)nbytes, (uint32_t)L));
+    uint32_t fl = 0;
+    VMN_TRY(read_flag(ctx, &fl));
+    VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));
+    *written = (size_t)text_bytes;
+    if (all_wellformed) *all_wellformed = (fl & TEXTLINES_ILL_FORMED) ? 0 : 1;
+    if (all_utf8) *all_utf8 = (fl & TEXTLINES_NOT_UTF8) ? 0 : 1;
+    return VMN_OK;
+}
+
+// ---- the same over curve groups: messages as points (csrc/ec_encode_layout.h, csrc/ec_encode_kernels.h) ---------------------------
+// [NOT-IN-REF: VCR ECqPGroup; unpinned]
+extern "C" size_t vmn_ec_group_encode_length(const vmn_group* grp) {
+    if (!grp || !grp->curve) return 0;
+    return encode::point_encode_length((size_t)hostbig::bit_length(grp->curve->p_words));
+}
+#define EC_ENCODE_GROUP_CHECK(grp, L)                                                                        \
+    do {                                                                                                     \
+        if ((L) == 0) {                                                                                      \
+            set_error("%s: messages are encoded as points over a curve group that holds at least one byte", __func__); \
+            return VMN_ERR_UNSUPPORTED;                                                                      \
+        }                                                                                                    \
+    } while (0)
+
+extern "C" int vmn_ec_arrays_from_textlines(vmn_group* grp, size_t ncomp, const char* text, size_t len, vmn_garray** out, size_t* n_out,
+                                            int* fits, size_t* first_long_line) {
+    ARG_CHECK(grp && out && n_out && fits && first_long_line && (text || len == 0), "null argument");
+    ARG_CHECK(textlines_ncomp_ok(ncomp), "ncomp out of range");
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    for (size_t c = 0; c < ncomp; ++c) out[c] = nullptr;
+    *n_out = 0;
+    *fits = 0;
+    *first_long_line = 0;
+    const size_t L = vmn_ec_group_encode_length(grp), tbytes = L + encode::LENGTH_BYTES;
+    EC_ENCODE_GROUP_CHECK(grp, L);
+    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
+
+    TextLines lines(ctx, "textlines");
+    VMN_TRY(lines.count(ctx, utext, len));
+    const size_t nlines = lines.nlines, total = nlines * ncomp;
+
+    // text -> the records T of all components (L + 4 bytes each), the longest admissible line checked on the way
+    DevTmp rec(ctx);
+    if (nlines) {
+        ARG_CHECK(total / ncomp == nlines && total < ((size_t)1 << 40), "too many elements");
+        const size_t blocks = (total * TEXTLINES_LANES + BLOCK - 1) / BLOCK;
+        ARG_CHECK(blocks < ((size_t)1 << 31), "too many elements");
+        VMN_TRY(rec.alloc(total * tbytes + 16));
+        VMN_TRY(lines.walk(ctx));
+        VMN_TRY(launch_light(ctx, "textlines", k_textlines_records, (unsigned)blocks, rec.as<uint8_t>(), lines.text(), (const u64*)lines.starts.p,
+                             (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)ncomp, (uint32_t)tbytes, (uint32_t)L, lines.first_bad()));
+        uint32_t bad = 0;
+        VMN_TRY(lines.read_first_bad(ctx, &bad));
+        if (bad != 0xffffffffu) {
+            *first_long_line = bad;
+            return VMN_OK;
+        }
+    }
+
+    // per component: the counter search into the rows (x, x^3 + a x + b), then the smaller root in place.  The word that named
+    // the first long line (0xffffffff here) now receives the first line whose search or root failed.
+    std::vector<vmn_garray*> arrays(ncomp, nullptr);
+    int rc = VMN_OK;
+    for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    const vmn_modulus& m = grp->P;
+    const double sqrt_products = grp->curve->ts_s ? 2.0 * (double)m.nbits : (double)m.nbits;      // (Tonelli-Shanks: priced, not counted)
+    for (size_t c = 0; c < ncomp && rc == VMN_OK && nlines; ++c) {
+        rc = with_curve(m, [&]<class E>(E) -> int {
+            note_work(ctx, m, (1.0 + 2.0 * 4.0) * (double)nlines);                // two counters expected, four products each
+            VMN_TRY(launch_light(ctx, "encode_search", k_ec_encode_search<E::S, E::NW, E::KIND>, grid_for(nlines), arrays[c]->d,
+                                 (const uint8_t*)rec.as<uint8_t>() + c * nlines * tbytes, nlines, (uint32_t)tbytes, ecdev(m.ec), lines.first_bad()));
+            note_work(ctx, m, 5.0 * (double)nlines, sqrt_products * (double)nlines);
+            if (m.ec->ts_s != 0) {                                                 // p = 1 mod 4: P-224, secp224k1
+                if constexpr (E::S == 9)
+                    return launch_light(ctx, "encode_root", k_ec_encode_root<E::S, E::KIND, true>, grid_for(nlines), arrays[c]->d, nlines,
+                                        ecdev(m.ec), lines.first_bad());
+                else
+                    return VMN_ERR_UNSUPPORTED;
+            }
+            return launch_light(ctx, "encode_root", k_ec_encode_root<E::S, E::KIND, false>, grid_for(nlines), arrays[c]->d, nlines, ecdev(m.ec),
+                                lines.first_bad());
+        });
+    }
+    uint32_t failed = 0xffffffffu;
+    if (rc == VMN_OK && nlines) rc = lines.read_first_bad(ctx, &failed);
+    if (rc == VMN_OK && failed != 0xffffffffu) {
+        set_error("%s: line %u: no counter gives a point on the curve", __func__, failed);
+        rc = VMN_ERR_FORMAT;
+    }
+    if (rc != VMN_OK) {
+        for (vmn_garray* a : arrays) vmn_garray_free(a);
+        return rc;
+    }
+    for (size_t c = 0; c < ncomp; ++c) out[c] = arrays[c];
+    *n_out = nlines;
+    *fits = 1;
+    return VMN_OK;
+}
+
+extern "C" int vmn_ec_arrays_to_textlines(const vmn_garray* const* comps, size_t ncomp, char* out, size_t cap, size_t* written,
+                                          int* all_wellformed, int* all_utf8) {
+    ARG_CHECK(comps && written && textlines_ncomp_ok(ncomp), "null argument or ncomp out of range");
+    ARG_CHECK(jsonlines_comps_ok(comps, ncomp), "ncomp arrays of one group and one size are needed");
+    vmn_group* grp = comps[0]->grp;
+    const size_t n = comps[0]->n, nbytes = grp->nbytes;
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    *written = 0;
+    if (all_wellformed) *all_wellformed = 1;
+    if (all_utf8) *all_utf8 = 1;
+    const size_t L = vmn_ec_group_encode_length(grp), tbytes = L + encode::LENGTH_BYTES;
+    EC_ENCODE_GROUP_CHECK(grp, L);
+    if (n == 0) return VMN_OK;
+    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
+    const size_t total = n * ncomp;
+    ARG_CHECK(total / ncomp == n && total < ((size_t)1 << 40), "too many elements");
+    const size_t groups = (n + BLOCK - 1) / BLOCK;
+    DevTmp rec(ctx), trec(ctx), plen(ctx), lens(ctx), bsum(ctx), dtext(ctx);
+    VMN_TRY(rec.alloc(total * 2 * nbytes + 16));
+    VMN_TRY(trec.alloc(total * tbytes + 16));
+    VMN_TRY(plen.alloc(total * sizeof(uint32_t)));
+    VMN_TRY(lens.alloc(n * sizeof(uint32_t)));
+    VMN_TRY(bsum.alloc((groups + 1) * sizeof(uint64_t)));
+    VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
+    for (size_t c = 0; c < ncomp; ++c)
+        VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, rec.as<uint8_t>() + c * n * 2 * nbytes, 2 * nbytes, 0));
+    VMN_TRY(launch_light(ctx, "textlines", k_ec_textlines_fold, grid_for(total), trec.as<uint8_t>(), plen.as<uint32_t>(),
+                         (const uint8_t*)rec.as<uint8_t>(), total, (uint32_t)nbytes, (uint32_t)L, ctx->flags));
+    VMN_TRY(launch_light(ctx, "textlines", k_textlines_lengths, (unsigned)groups, lens.as<uint32_t>(), (u64*)bsum.p,
+                         (const uint8_t*)trec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n, (uint32_t)ncomp, (uint32_t)tbytes,
+                         (uint32_t)L, ctx->flags));
+    VMN_TRY(launch_light(ctx, "textlines", k_jsonlines_offsets, 1u, (u64*)bsum.p, groups, (u64*)bsum.p + groups));
+    uint64_t text_bytes = 0;
+    VMN_TRY(d2h(ctx, &text_bytes, (const u64*)bsum.p + groups, sizeof(text_bytes)));
+    ARG_CHECK(text_bytes <= cap && out, "the buffer is too small for these lines");
+    VMN_TRY(dtext.alloc(text_bytes + 16));
+    VMN_TRY(launch_light(ctx, "textlines", k_textlines_emit, (unsigned)groups, dtext.as<uint8_t>(), (const u64*)bsum.p,
+                         (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)trec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n,
+                         (uint32_t)ncomp, (uint32_t)tbytes, (uint32_t)L));
     uint32_t fl = 0;
     VMN_TRY(read_flag(ctx, &fl));
     VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));

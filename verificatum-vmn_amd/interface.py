@@ -23,7 +23,10 @@ message of up to ``encode_length`` bytes per component is an element of a safe-p
 encoding).  ``encode_texts`` / ``decode_texts`` convert whole lists on the GPU (``vmn_garrays_from_textlines`` /
 ``vmn_garrays_to_textlines``, csrc/encode_kernels.h), ``read_texts`` / ``write_decoded_plaintexts`` are their file functions, and
 ``demo_texts`` / ``demo_ciphertexts`` are the reference's dummy messages and their encryptions.  ``write_plaintexts`` and
-``PLAINTEXT_FORMATS`` keep to ``json`` and ``raw``.
+``PLAINTEXT_FORMATS`` keep to ``json`` and ``raw``.  Over a curve group a message of up to ``point_encode_length`` bytes is the x
+coordinate of a point under a one-byte counter (csrc/ec_encode_layout.h); ``encode_point_texts`` / ``decode_point_texts``,
+``read_point_texts`` / ``write_decoded_point_plaintexts`` and ``demo_point_ciphertexts`` are the namesakes there
+(``vmn_ec_arrays_from_textlines`` / ``vmn_ec_arrays_to_textlines``, csrc/ec_encode_kernels.h); the functions above keep refusing curves.
 
 Under a public key of width kappa (``keywidth``, 1 by default) a ciphertext of ``width`` omega has 2 kappa omega components and
 every half of a list or of a line one more node level (``proofdir``'s head, ``vmn_garrays_from_hexlines_keyed``); ``native`` and
@@ -372,6 +375,77 @@ def demo_ciphertexts(grp, y, n: int, rand, width: int = 1) -> List[PGroupElement
     """demoCiphertexts (:374-428): the ``n`` dummy messages encrypted under the key (g, ``y``): u = g^r, v = y^r encode(text), the
     exponents from ``rand`` (``ring_array(n)``, once per component).  Returns the 2 * width arrays u_1..u_w, v_1..v_w."""
     msgs = encode_texts(grp, demo_texts(n, width * encode_length(grp)), width)
+    if msgs is None:
+        raise ValueError("the group holds no message")
+    us, vs = [], []
+    for m in msgs:
+        r = grp.ringArray(rand.ring_array(n))
+        t = grp.exp(y, r)
+        us.append(grp.exp(grp.g, r))
+        vs.append(t.mul(m))
+        for a in (r, t, m):
+            a.free()
+    return us + vs
+
+
+# ---- the same over curve groups: messages as points (csrc/ec_encode_layout.h) ----------------------------------------------------------
+def point_encode_length(grp) -> int:
+    """L over a curve group: floor((bits(p) - 2) / 8) - 5 for the field prime p (26 over P-256); 0 over a modular group, which
+    ``encode_point_texts`` / ``decode_point_texts`` refuse."""
+    return lib().vmn_ec_group_encode_length(grp._h)
+
+
+def encode_point_texts(grp, text, ncomp: int = 1, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+    """``encode_texts`` over a curve group: line i is cut into pieces of ``point_encode_length`` bytes, each the x coordinate of a
+    point under the least counter that puts it on the curve (``vmn_ec_arrays_from_textlines``).  ``None`` when a line has more
+    than ncomp * L bytes; ``report`` receives ``fits``, ``first_long_line`` and ``lines``."""
+    blk = host_block(text) or host_block(bytes(text))
+    hs = (C.c_void_p * ncomp)()
+    n, long_line, fits = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+    _check(lib().vmn_ec_arrays_from_textlines(grp._h, C.c_size_t(ncomp), blk[0], C.c_size_t(blk[1]), hs, C.byref(n), C.byref(fits),
+                                              C.byref(long_line)))
+    if report is not None:
+        report.update(fits=bool(fits.value), first_long_line=long_line.value, lines=n.value)
+    if not fits.value:
+        return None
+    return [PGroupElementArray(grp, C.c_void_p(h)) for h in hs]
+
+
+def decode_point_texts(comps: Sequence[PGroupElementArray], report: Optional[dict] = None) -> bytes:
+    """``decode_texts`` over a curve group (``vmn_ec_arrays_to_textlines``): the message of a point is read from its x coordinate;
+    ``report`` receives ``all_wellformed`` and ``all_utf8``."""
+    if not comps:
+        raise ValueError("no arrays")
+    grp, n = comps[0].group, comps[0].size()
+    hs = (C.c_void_p * len(comps))(*[a._h for a in comps])
+    cap = max(1, n * (len(comps) * point_encode_length(grp) + 1))
+    out = C.create_string_buffer(cap)
+    written, wf, utf8 = C.c_size_t(0), C.c_int(1), C.c_int(1)
+    _check(lib().vmn_ec_arrays_to_textlines(hs, C.c_size_t(len(comps)), out, C.c_size_t(cap), C.byref(written), C.byref(wf), C.byref(utf8)))
+    if report is not None:
+        report.update(all_wellformed=bool(wf.value), all_utf8=bool(utf8.value))
+    return out.raw[:written.value]
+
+
+def write_decoded_point_plaintexts(path: str, comps: Sequence[PGroupElementArray]) -> None:
+    """``vmnc -plain -outi native`` of a curve session: the list of plaintexts given as its component arrays, as lines of text."""
+    data = decode_point_texts(comps)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def read_point_texts(grp, path: str, ncomp: int, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
+    """The lines of the file at ``path`` as ``ncomp`` arrays of points; ``None`` when it is missing or a line does not fit."""
+    buf = proofdir._read_file(path)
+    if buf is None:
+        return None
+    return encode_point_texts(grp, buf, ncomp, report)
+
+
+def demo_point_ciphertexts(grp, y, n: int, rand, width: int = 1) -> List[PGroupElementArray]:
+    """``demo_ciphertexts`` over a curve group: the ``n`` dummy messages of ``demo_texts`` as points, encrypted under (g, ``y``).
+    Returns the 2 * width arrays u_1..u_w, v_1..v_w."""
+    msgs = encode_point_texts(grp, demo_texts(n, width * point_encode_length(grp)), width)
     if msgs is None:
         raise ValueError("the group holds no message")
     us, vs = [], []
