@@ -455,6 +455,19 @@ int vmn_rarray_from_prg(vmn_group* grp, const uint8_t* seed, size_t seedlen, siz
 int vmn_rarray_from_prg_range(vmn_group* grp, const uint8_t* seed, size_t seedlen, size_t first, size_t n, int bits, vmn_rarray** out);
 int vmn_rarray_from_prg_gather(vmn_group* grp, const uint8_t* seed, size_t seedlen, const uint32_t* idx, size_t n, int bits,
                                vmn_rarray** out);
+/* A prover's secret permutation, drawn on the device: Permutation.random(size, randomSource, rbitlen) of
+ * mixnet/ShufflerElGamalSession.java:408-409 and mixnet/PermutationCommitment.java:209 [NOT-IN-REF: VCR Permutation.random;
+ * unpinned -- the rule is stated in csrc/permutation_layout.h].  Key i = the i-th key_bytes bytes of PRG(seed), leading bits
+ * cleared (vmn_rarray_from_prg's convention), with kb = rbitlen + 2 ceil(log2(max(n, 2))) key bits and key_bytes = ceil(kb / 8);
+ * pi[j] = the index of rank j in the order (key, index), inv[pi[j]] = j.  Within 2^-rbitlen of uniform.  n < 2^32 (n = 0 and 1
+ * are valid), rbitlen 0 .. 256.  The sort is a radix sort of the indices on the device (csrc/permutation_kernels.h), exact and
+ * the same bytes on every run and every rank; the tables come back as HOST tables, which is what every entry point that takes
+ * `const uint32_t* pi` expects.  Either table may be NULL, not both.  Bad arguments: VMN_ERR_ARG, nothing written. */
+size_t vmn_permutation_key_bytes(size_t n, int rbitlen);               /* 0 when the arguments are out of range */
+/* the same order for keys the caller holds: n big-endian rows of key_bytes bytes (1 .. 64) */
+int vmn_permutation_from_keys(vmn_ctx* ctx, const uint8_t* keys_be, size_t key_bytes, size_t n, uint32_t* pi_out, uint32_t* inv_out);
+int vmn_permutation_from_prg(vmn_ctx* ctx, const uint8_t* seed, size_t seedlen, size_t n, int rbitlen, uint32_t* pi_out,
+                             uint32_t* inv_out);
 /* Independent generators: pGroup.randomElementArray(n, prg, rbitlen) of a ModPGroup, generated on the
  * device.  ref: P/distr/IndependentGeneratorsRO.java:117-130 (seed = RO(globalPrefix || bytetree(sid))).
  * t_i = the i-th ceil((bits(p) + rbitlen)/8) bytes, leading bits cleared; h_i = t_i^((p-1)/q) mod p -- a squaring for

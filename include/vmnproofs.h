@@ -64,6 +64,13 @@ typedef struct vmn_random_source {
 /* pRing.randomElementArray(n, randomSource, rbitlen) for a caller that needs such an array itself -- the re-encryption
  * exponents, ShufflerElGamalSession.java:400-409 (:408-409); the commitment exponents, PermutationCommitment.java:189-199. */
 int vmn_rarray_random(vmn_group* grp, const vmn_random_source* rs, size_t n, int rbitlen, vmn_rarray** out);
+/* Permutation.random(size, randomSource, rbitlen) -- the shuffler's secret permutation, ShufflerElGamalSession.java:408-409,
+ * PermutationCommitment.java:209: the source is asked for ONE 32-byte seed (whatever n), and the table is drawn on the device
+ * by vmn_permutation_from_prg (vmnhip.h; the rule: csrc/permutation_layout.h).  pi_out / inv_out: host tables of n entries,
+ * either may be NULL, not both.  A source without `array_seed` is answered with VMN_ERR_UNSUPPORTED and is not called: its
+ * `integers` rows have the width of a group's exponents, which a key of rbitlen + 2 log2(n) bits need not fit, and this call
+ * has no group.  Draw the keys yourself and use vmn_permutation_from_keys then. */
+int vmn_permutation_random(vmn_ctx* ctx, const vmn_random_source* rs, size_t n, int rbitlen, uint32_t* pi_out, uint32_t* inv_out);
 
 /* ---- messages: ordered items, each an element array, a ring array, k group elements or k ring elements ----
  *   PoS  commitment (PoSBasicTW.java:694-699):  B[N], A', B'[N], C', D', F'[2w]

@@ -25,6 +25,16 @@ final class GPUArrays {
         return table;
     }
 
+    /** {@code Permutation.random(n, randomSource, rbitlen)} drawn on the device from one PRG seed (32 / 48 / 64 bytes of the
+     *  party's RandomSource; vmn_permutation_from_prg, the rule is stated in csrc/permutation_layout.h): the result is used
+     *  where {@link #gatherTable} of a host permutation would be -- out[k] = X[table[k]].  The inverse of a uniform
+     *  permutation is uniform, so the table is the secret permutation itself; no host Permutation object is built. */
+    static int[] randomPermutation(final GPUGroup group, final byte[] seed, final int n, final int rbitlen) {
+        final int[] table = new int[n];
+        VMNException.check(VMNHip.vmn_permutation_from_prg(group.ctx, seed, seed.length, n, rbitlen, table, null));
+        return table;
+    }
+
     static ByteBuffer direct(final ByteTreeBasic bt) {
         final byte[] bytes = bt.toByteArray();
         final ByteBuffer buf = ByteBuffer.allocateDirect(bytes.length);

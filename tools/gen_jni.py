@@ -240,7 +240,7 @@ def need_expr(name, ptype, pname, plist):
             return "(size_t)k" if name == "vmn_garray_expprod_arrays" else "(size_t)threshold"
         if pname == "verdicts5":
             return "5"
-        if pname == "pi_out":
+        if pname in ("pi_out", "inv_out"):                  # (inv_out: the inverse table of vmn_permutation_*)
             return "(size_t)n"
         if pname == "pi":
             if name == "vmn_permutation_shrink":
@@ -264,6 +264,8 @@ def need_expr(name, ptype, pname, plist):
             return "(size_t)(keep_len > n_max ? keep_len : n_max)"       # the trivial list is written over n_max entries
         if pname in explicit and explicit[pname] in names:
             return f"(size_t){explicit[pname]}"
+        if pname == "keys_be":                                                # the sort keys of vmn_permutation_from_keys
+            return "(size_t)n * (size_t)key_bytes"
         if pname == "exps_be":
             return f"{asize} * (size_t)ebytes"
         if pname == "es_be":                                                  # a row per array
@@ -399,7 +401,8 @@ def c_wrapper(cls, ret, name, plist, direct=()):
         elif k == "rs":
             args.append(f"jobject {pname}")
             # the bridge checks every row block the source hands back against n rows of the group's exponent width
-            pre.append(f"    vmn_jrs* h_{pname} = {pname} ? vmn_jrs_new(env, {pname}, vmnjni_xb({group_expr(name, plist)})) : NULL;")
+            # (a call without a group -- vmn_permutation_random -- asks the source for seeds only: no row width)
+            pre.append(f"    vmn_jrs* h_{pname} = {pname} ? vmn_jrs_new(env, {pname}, vmnjni_xb({group_expr(name, plist) or 'NULL'})) : NULL;")
             pre.append(f"    vmn_random_source s_{pname};")
             pre.append(f"    if (h_{pname}) vmn_jrs_fill(h_{pname}, &s_{pname});")
             call.append(f"h_{pname} ? &s_{pname} : NULL")

@@ -52,7 +52,7 @@ def main():
     nizkp = tempfile.mkdtemp(prefix="session_ab_")
     try:
         t0 = time.perf_counter()
-        params, _ = proofdir.write_session(nizkp, grp, params, proofdir.MIX_TYPE, W, y, randomsource.SecureRandomSource(q), K, THR,
+        params, _ = proofdir.write_session(nizkp, grp, params, proofdir.MIX_TYPE, W, y, randomsource.SecureRandomSource(q, ctx=ctx), K, THR,
                                            poly=poly, shares=shares)
         print(f"wrote the session in {time.perf_counter() - t0:.1f} s", flush=True)
         pkey = [g, y]

@@ -149,7 +149,7 @@ def demo_session(args, vmn, ctx, proofdir, randomsource, stdgroups):
     M = [grp.exp(g, grp.ringArray(rnd.ring_array(args.n))) for _ in range(kw * width)]
     W = [grp.exp(g, t) for t in T] + [m.mul(grp.exp(y[c % kw], t)) for c, (m, t) in enumerate(zip(M, T))]
     typ = proofdir.SHUFFLE_TYPE if args.shuffle else proofdir.DECRYPT_TYPE if args.decrypt else proofdir.MIX_TYPE
-    proofdir.write_session(args.nizkp, grp, params, typ, W, poly[0], randomsource.SecureRandomSource(q), k, thr,
+    proofdir.write_session(args.nizkp, grp, params, typ, W, poly[0], randomsource.SecureRandomSource(q, ctx=ctx), k, thr,
                            active=args.active or thr, n0=args.precomputed, poly=poly, shares=shares, keywidth=kw)
     print(f"wrote {args.nizkp}: a {typ} session, {args.n} ciphertexts of width {width}, key width {kw}, {k} parties, threshold {thr}",
           file=sys.stderr)
@@ -264,7 +264,7 @@ def main():
         W = [grp.exp(g, T), M.mul(grp.exp(y, T))]
         params["N_0"] = args.precomputed
         proofdir.write_inputs(args.nizkp, grp, params, pkey, W)
-        prover = randomsource.SecureRandomSource(q)
+        prover = randomsource.SecureRandomSource(q, ctx=ctx)
         if args.precomputed:
             pi, R, U, H = proofdir.write_precomputation(args.nizkp, args.l, grp, params, args.precomputed, prover)
             proofdir.write_committed_shuffle(args.nizkp, args.l, grp, params, pkey, W, prover, pi, R, U, H)

@@ -203,6 +203,44 @@ class Context:
         return n.value, ms.value
 
 
+# ---- a prover's secret permutation, drawn on the device (vmn_permutation_*; the rule: csrc/permutation_layout.h) -----------------
+def _u32_tables(n: int):
+    if _np is None:                     # pragma: no cover
+        raise VmnError(-1, "the permutation tables are numpy arrays: numpy is missing")
+    pi, inv = _np.empty(n, dtype=_np.uint32), _np.empty(n, dtype=_np.uint32)
+    return pi, inv, pi.ctypes.data_as(C.POINTER(C.c_uint32)), inv.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def permutation_key_bytes(n: int, rbitlen: int) -> int:
+    """``vmn_permutation_key_bytes``: the bytes of a sort key for a table of n entries (0: arguments out of range)."""
+    fn = lib().vmn_permutation_key_bytes
+    fn.restype = C.c_size_t
+    return 0 if not 0 <= n < 1 << 64 else fn(C.c_size_t(n), C.c_int(rbitlen))
+
+
+def permutation_from_prg(ctx: "Context", seed: bytes, n: int, rbitlen: int):
+    """``vmn_permutation_from_prg``: ``(pi, inv)`` as numpy ``uint32`` arrays -- ``Permutation.random(n, source, rbitlen)`` drawn on
+    the GPU from one PRG seed (32 / 48 / 64 bytes: SHA-256 / 384 / 512); pi[j] = the index of rank j in the order (key, index)."""
+    if not 0 <= n < 1 << 32:
+        raise VmnError(-1, "permutation_from_prg: n must be below 2^32")
+    seed = bytes(seed)
+    pi, inv, ppi, pinv = _u32_tables(n)
+    _check(lib().vmn_permutation_from_prg(ctx._h, seed, C.c_size_t(len(seed)), C.c_size_t(n), C.c_int(rbitlen), ppi, pinv))
+    return pi, inv
+
+
+def permutation_from_keys(ctx: "Context", keys, key_bytes: int):
+    """``vmn_permutation_from_keys``: the same order for keys the caller holds -- a block of n big-endian rows of ``key_bytes``
+    bytes (``bytes`` or a numpy ``uint8`` array); ``(pi, inv)`` as numpy ``uint32`` arrays."""
+    blk = host_block(keys)
+    if blk is None or key_bytes < 1 or blk[1] % key_bytes:
+        raise VmnError(-1, "permutation_from_keys: keys must be a block of whole rows of key_bytes bytes")
+    n = blk[1] // key_bytes
+    pi, inv, ppi, pinv = _u32_tables(n)
+    _check(lib().vmn_permutation_from_keys(ctx._h, blk[0], C.c_size_t(key_bytes), C.c_size_t(n), ppi, pinv))
+    return pi, inv
+
+
 class ModPGroup:
     """``com.verificatum.arithm.ModPGroup``: the order-q subgroup of Z_p^* with generator g."""
 

@@ -19,6 +19,7 @@
 #include "decimal_kernels.h"
 #include "encode_kernels.h"
 #include "ec_encode_kernels.h"
+#include "permutation_kernels.h"
 #include "vmnhip_internal.h"
 #include "sha256.h"
 #include "sha512.h"
@@ -4466,6 +4467,75 @@ extern "C" int vmn_rarray_from_prg_gather(vmn_group* grp, const uint8_t* seed, s
     ARG_CHECK(grp && out && bits > 0 && (idx || n == 0), "bad argument");
     VMN_ENTER(LANE(grp->ctx));
     return rarray_from_prg_sel(grp, seed, seedlen, 0, idx, n, bits, out);
+}
+
+// ---- a prover's secret permutation (csrc/permutation_layout.h, csrc/permutation_kernels.h) ----------------------------------------
+static_assert(permutation::SORT_BLOCK == BLOCK, "the sort kernels are launched with the helpers' block");
+// pi (and its inverse) of the order (key, index) over n big-endian key rows on the device: one radix pass per key byte,
+// every temporary from the lane's pool.  The tables are copied out at the end only.
+static int permutation_sort(vmn_ctx* ctx, const uint8_t* d_rows, size_t key_bytes, size_t n, uint32_t* pi_out, uint32_t* inv_out) {
+    if (n == 0) return VMN_OK;
+    using namespace permutation;
+    const size_t ntiles = (n + SORT_TILE - 1) / SORT_TILE, bins = (size_t)RADIX * ntiles;
+    const size_t scan_blocks = (bins + (size_t)BLOCK * SCAN_ITEMS - 1) / ((size_t)BLOCK * SCAN_ITEMS);
+    DevTmp planes(ctx), idx_a(ctx), idx_b(ctx), dig(ctx), hist(ctx), offs(ctx), bsum(ctx);
+    VMN_TRY(planes.alloc(n * key_bytes));
+    VMN_TRY(idx_a.alloc(n * sizeof(uint32_t)));
+    VMN_TRY(idx_b.alloc(n * sizeof(uint32_t)));
+    VMN_TRY(dig.alloc(n));
+    VMN_TRY(hist.alloc(bins * sizeof(uint32_t)));
+    VMN_TRY(offs.alloc((bins + 1) * sizeof(uint32_t)));
+    VMN_TRY(bsum.alloc((scan_blocks + 1) * sizeof(uint32_t)));
+    uint32_t *cur = idx_a.as<uint32_t>(), *nxt = idx_b.as<uint32_t>();
+    VMN_TRY(launch_light(ctx, "permutation", k_perm_planes, grid_for(n), planes.as<uint8_t>(), cur, d_rows, key_bytes, n));
+    for (size_t d = 0; d < key_bytes; ++d) {
+        VMN_TRY(launch_light(ctx, "permutation", k_perm_hist, (unsigned)ntiles, hist.as<uint32_t>(), dig.as<uint8_t>(), (const uint32_t*)cur,
+                             (const uint8_t*)planes.as<uint8_t>() + plane_at(n, d, 0), n, (uint32_t)ntiles));
+        VMN_TRY(launch_light(ctx, "permutation", k_u32_blocksum, (unsigned)scan_blocks, bsum.as<uint32_t>(), (const uint32_t*)hist.as<uint32_t>(), bins));
+        VMN_TRY(launch_light(ctx, "permutation", k_u32_scan_top, 1u, bsum.as<uint32_t>(), scan_blocks, bsum.as<uint32_t>() + scan_blocks));
+        VMN_TRY(launch_light(ctx, "permutation", k_u32_scan_apply, (unsigned)scan_blocks, offs.as<uint32_t>(), (uint32_t*)nullptr,
+                             (const uint32_t*)hist.as<uint32_t>(), (const uint32_t*)bsum.as<uint32_t>(), bins));
+        VMN_TRY(launch_light(ctx, "permutation", k_perm_scatter, (unsigned)ntiles, nxt, (const uint32_t*)cur, (const uint8_t*)dig.as<uint8_t>(),
+                             (const uint32_t*)offs.as<uint32_t>(), n, (uint32_t)ntiles));
+        std::swap(cur, nxt);
+    }
+    if (inv_out) {
+        VMN_TRY(launch_light(ctx, "permutation", k_perm_inverse, grid_for(n), nxt, (const uint32_t*)cur, n));
+        VMN_TRY(d2h(ctx, inv_out, nxt, n * sizeof(uint32_t)));
+    }
+    if (pi_out) VMN_TRY(d2h(ctx, pi_out, cur, n * sizeof(uint32_t)));
+    return VMN_OK;
+}
+extern "C" size_t vmn_permutation_key_bytes(size_t n, int rbitlen) { return permutation::key_bytes(n, rbitlen); }
+extern "C" int vmn_permutation_from_keys(vmn_ctx* ctx, const uint8_t* keys_be, size_t key_bytes, size_t n, uint32_t* pi_out,
+                                         uint32_t* inv_out) {
+    ARG_CHECK(ctx && (pi_out || inv_out), "null context, or neither table wanted");
+    ARG_CHECK(key_bytes >= 1 && key_bytes <= permutation::MAX_KEY_BYTES, "key_bytes must be 1 .. 64");
+    ARG_CHECK(n <= permutation::MAX_N && (keys_be || n == 0), "null keys, or n >= 2^32");
+    ctx = LANE(ctx);
+    VMN_ENTER(ctx);
+    if (n == 0) return VMN_OK;
+    DevTmp rows(ctx);
+    VMN_TRY(rows.alloc(n * key_bytes));
+    VMN_TRY(h2d(ctx, rows.p, keys_be, n * key_bytes));
+    return permutation_sort(ctx, rows.as<uint8_t>(), key_bytes, n, pi_out, inv_out);
+}
+extern "C" int vmn_permutation_from_prg(vmn_ctx* ctx, const uint8_t* seed, size_t seedlen, size_t n, int rbitlen, uint32_t* pi_out,
+                                        uint32_t* inv_out) {
+    ARG_CHECK(ctx && (pi_out || inv_out), "null context, or neither table wanted");
+    ARG_CHECK(seed && (seedlen == 32 || seedlen == 48 || seedlen == 64), "the seed must be 32, 48 or 64 bytes");
+    const int kb = permutation::key_bits(n, rbitlen);
+    ARG_CHECK(kb > 0, "n must be below 2^32 and rbitlen 0 .. 256");
+    const size_t key_bytes = permutation::key_bytes(n, rbitlen);
+    ARG_CHECK(n <= (((size_t)1 << 32) * seedlen) / key_bytes, "PRG stream position beyond the 32-bit block counter of PRGHeuristic");
+    ctx = LANE(ctx);
+    VMN_ENTER(ctx);
+    if (n == 0) return VMN_OK;
+    PrgSeed w;
+    VMN_TRY(prg_seed_words(seed, seedlen, w));
+    DevTmp rows(ctx);
+    VMN_TRY(prg_rows(ctx, w, n, key_bytes, kb, 0, key_bytes, key_bytes, rows));
+    return permutation_sort(ctx, rows.as<uint8_t>(), key_bytes, n, pi_out, inv_out);
 }
 
 // Random curve points from a PRG seed (see k_ec_random_points): candidates in batches, kept rows compacted in order.

@@ -3022,6 +3022,17 @@ int vmn_rarray_random(vmn_group* grp, const vmn_random_source* rs, size_t n, int
     return VMN_OK;
 }
 
+// Permutation.random(size, randomSource, rbitlen), ShufflerElGamalSession.java:408-409: one seed of the source, whatever n
+int vmn_permutation_random(vmn_ctx* ctx, const vmn_random_source* rs, size_t n, int rbitlen, uint32_t* pi_out, uint32_t* inv_out) {
+    if (!ctx || !rs || (!pi_out && !inv_out)) return fail(VMN_ERR_ARG, "vmn_permutation_random: bad argument");
+    if (vmn_permutation_key_bytes(n, rbitlen) == 0) return fail(VMN_ERR_ARG, "vmn_permutation_random: n must be below 2^32 and rbitlen 0 .. 256");
+    if (!rs->array_seed)
+        return fail(VMN_ERR_UNSUPPORTED, "vmn_permutation_random: the source has no array_seed (host rows have the group's width, keys do not)");
+    uint8_t seed[32];
+    if (rs->array_seed(rs->user, seed) != 0) return fail(VMN_ERR_ARG, "random source failed");
+    return vmn_permutation_from_prg(ctx, seed, 32, n, rbitlen, pi_out, inv_out);
+}
+
 int vmn_permutation_shrink(const uint32_t* pi, size_t n_max, size_t n, uint8_t* keep_out, uint32_t* pi_out) {
     if (!pi || !keep_out || !pi_out || n > n_max) return fail(VMN_ERR_ARG, "vmn_permutation_shrink: bad argument");
     if (!is_permutation(pi, n_max)) return fail(VMN_ERR_ARG, "vmn_permutation_shrink: pi is not a permutation of [0, n_max)");

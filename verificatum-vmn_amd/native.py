@@ -677,6 +677,40 @@ def random_ring_array_native(group, tape, n: int, rbitlen: int):
     return PRingElementArray(group, out)
 
 
+def random_permutation(ctx, rand, n: int, rbitlen: int):
+    """``vmn_permutation_random``: ``Permutation.random(n, randomSource, rbitlen)`` -- ONE ``array_seed()`` of the source, the table
+    drawn on the device; ``(pi, inv)`` as numpy ``uint32`` arrays.  A source without ``array_seed`` is answered with
+    VMN_ERR_UNSUPPORTED (include/vmnproofs.h says why)."""
+    import numpy as np
+
+    class _State:
+        error = None
+    st = _State()
+
+    def seed_cb(_user, out):
+        try:
+            seed = bytes(rand.array_seed())
+            if len(seed) != 32:
+                raise ValueError("array_seed() must return 32 bytes")
+            C.memmove(out, seed, 32)
+            return 0
+        except Exception as exc:       # pragma: no cover - re-raised below
+            st.error = exc
+            return 1
+
+    cb = _SEED_CB(seed_cb) if hasattr(rand, "array_seed") else _SEED_CB()
+    rs = _RandomSourceStruct(None, _ROWS_CB(), _INTS_CB(), cb)
+    if not 0 <= n < 1 << 32:
+        raise VmnError(-1, "random_permutation: n must be below 2^32")
+    pi, inv = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+    rc = plib().vmn_permutation_random(ctx._h, C.byref(rs), C.c_size_t(n), C.c_int(rbitlen), pi.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       inv.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != 0 and st.error is not None:
+        raise st.error
+    _check(rc)
+    return pi, inv
+
+
 # ---- verifiable threshold decryption (the interface of elgamal.py over the C++ drivers) -------------------------------
 def _flags(correct):
     return bytes(1 if c else 0 for c in correct)

@@ -32,12 +32,14 @@ class SecureRandomSource:
     with ``rbitlen`` bits of slack and reduced (statistical distance 2^-rbitlen from uniform); the N-sized draws of a
     proof are expanded on the GPU from 32 fresh bytes each (``array_seed``, see ``vmn_random_source`` in
     include/vmnproofs.h), so no N-sized host buffer exists.  ``ring_array`` / ``int_array`` remain for drivers that
-    want host rows (the Python mirror)."""
+    want host rows (the Python mirror).  With a ``Context`` the permutation is drawn there too: 32 fresh bytes, the keys and the
+    sort on the GPU (``permutation_from_prg``; the rule is stated in csrc/permutation_layout.h); without one it is the host's
+    ``SystemRandom().shuffle``."""
 
-    def __init__(self, q: int, rbitlen: int = 100):
+    def __init__(self, q: int, rbitlen: int = 100, ctx=None):
         import os
         self._urandom = os.urandom
-        self.q, self.rbitlen = q, rbitlen
+        self.q, self.rbitlen, self.ctx = q, rbitlen, ctx
 
     def array_seed(self) -> bytes:
         return self._urandom(32)
@@ -54,7 +56,10 @@ class SecureRandomSource:
         mask = (1 << bits) - 1
         return [int.from_bytes(self._urandom(nb), "big") & mask for _ in range(n)]
 
-    def permutation(self, n: int) -> List[int]:
+    def permutation(self, n: int):
+        if self.ctx is not None:
+            from . import permutation_from_prg
+            return permutation_from_prg(self.ctx, self.array_seed(), n, self.rbitlen)[0]       # a numpy uint32 table
         import random
         pi = list(range(n))
         random.SystemRandom().shuffle(pi)
