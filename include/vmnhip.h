@@ -391,6 +391,14 @@ int vmn_garray_shift_push(const vmn_garray* x, const uint8_t* el_be, vmn_garray*
 int vmn_garray_copy_range(const vmn_garray* x, size_t from, size_t to, vmn_garray** out);
 int vmn_garray_extract(const vmn_garray* x, const uint8_t* keep_host, vmn_garray** out);
 int vmn_garray_get(const vmn_garray* x, size_t i, uint8_t* out_be);
+/* pGroup.toElementArray(PGroupElementArray[]) and copyOfRange in one: out holds the rows [from[k], to[k]) of src[k], k = 0 .. nseg-1,
+ * one segment after the other.  Segments may be empty, may overlap, and one array may be named more than once; the sources are
+ * read only.  nseg == 0 gives the empty array of grp.  VMN_ERR_ARG and no array (*out = NULL) for a null argument, a source of
+ * another group, from[k] > to[k], to[k] > the size of src[k], nseg > 65536, or a row total that overflows.  One launch per call
+ * whatever nseg is (csrc/light_kernels.h k_rows_segments), also for one segment.
+ * ref: ProtocolElGamalRear.java:430-473, ProtocolElGamalInterfaceSeq.java:181. */
+int vmn_garray_from_segments(vmn_group* grp, const vmn_garray* const* src, const size_t* from, const size_t* to, size_t nseg,
+                             vmn_garray** out);
 /* Subgroup membership of every element; *all_members = 1/0.  Part of K10 (the check pGroup.toElementArray makes
  * when an array is read).  Safe-prime groups up to 3072 bits: Jacobi symbol (x / p) = 1 by the binary algorithm,
  * one element per lane (10^6 elements in 46 ms); otherwise x^q = 1 (749 ms); curves: the import's on-curve check

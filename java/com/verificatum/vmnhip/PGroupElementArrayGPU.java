@@ -110,6 +110,21 @@ public final class PGroupElementArrayGPU {
         return wrap(out);
     }
 
+    /** pGroup.toElementArray(PGroupElementArray[]): the arrays one after the other, in one launch (a list read in batches
+     *  becomes one array; ProtocolElGamalInterfaceSeq.java:181). */
+    public static PGroupElementArrayGPU concat(final GPUGroup group, final PGroupElementArrayGPU[] arrays) {
+        final long[] src = new long[arrays.length];
+        final long[] from = new long[arrays.length];
+        final long[] to = new long[arrays.length];
+        for (int i = 0; i < arrays.length; i++) {
+            src[i] = arrays[i].handle;
+            to[i] = arrays[i].size();
+        }
+        final long[] out = new long[1];
+        VMNException.check(VMNHip.vmn_garray_from_segments(group.grp, src, from, to, arrays.length, out));
+        return new PGroupElementArrayGPU(group, out[0]);
+    }
+
     public PGroupElementArrayGPU extract(final boolean[] keep) {
         final byte[] k = new byte[keep.length];
         for (int i = 0; i < keep.length; i++) {

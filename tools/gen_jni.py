@@ -205,6 +205,8 @@ def need_expr(name, ptype, pname, plist):
     if k == "handles_in":
         if pname in ("xs", "ys"):
             return "(size_t)k"
+        if name == "vmn_garray_from_segments" and pname == "src":        # one source and one range per segment
+            return "(size_t)nseg"
         if name == "vmn_garrays_to_jsonplain" and pname == "comps":     # a list of plaintexts: width arrays
             return "(size_t)width"
         if name in ("vmn_garrays_to_textlines", "vmn_ec_arrays_to_textlines") and pname == "comps":
@@ -254,6 +256,8 @@ def need_expr(name, ptype, pname, plist):
             return None
         return "1"                                  # verdicts, flags, bit counts
     if k in ("longs_in", "longs_out"):
+        if name == "vmn_garray_from_segments" and pname in ("from", "to"):
+            return "(size_t)nseg"
         return "(size_t)items" if pname == "counts" else "1"
     if k == "doubles_out":
         return "1"

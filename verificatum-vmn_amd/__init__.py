@@ -422,6 +422,24 @@ class ModPGroup:
                                                C.c_int(bitLength), C.byref(h)))
         return PGroupElementArray(self, h)
 
+    def fromSegments(self, arrays, froms, tos) -> "PGroupElementArray":
+        """Rows ``[froms[k], tos[k])`` of ``arrays[k]``, one segment after the other, as one new array
+        (``vmn_garray_from_segments``: ``copyOfRange`` and ``pGroup.toElementArray(PGroupElementArray[])`` in one launch).
+        Segments may be empty and may overlap, and one array may be named more than once."""
+        k = len(arrays)
+        if len(froms) != k or len(tos) != k:
+            raise ValueError("fromSegments needs one range per array")
+        hs = (C.c_void_p * max(k, 1))(*[a._h for a in arrays])
+        lo = (C.c_size_t * max(k, 1))(*[int(v) for v in froms])
+        hi = (C.c_size_t * max(k, 1))(*[int(v) for v in tos])
+        h = C.c_void_p()
+        _check(lib().vmn_garray_from_segments(self._h, hs, lo, hi, C.c_size_t(k), C.byref(h)))
+        return PGroupElementArray(self, h)
+
+    def concat(self, arrays) -> "PGroupElementArray":
+        """``pGroup.toElementArray(PGroupElementArray[])``: the arrays one after the other."""
+        return self.fromSegments(arrays, [0] * len(arrays), [a.size() for a in arrays])
+
     def toElementArrayFromByteTree(self, bt: bytes, size: int = 0) -> "PGroupElementArray":
         """``pGroup.toElementArray(size, byteTreeReader)`` (size 0 = any), the reference's wire format."""
         return self._from_bytetree("vmn_garray_from_bytetree", PGroupElementArray, bt, size)

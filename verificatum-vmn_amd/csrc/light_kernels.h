@@ -100,6 +100,40 @@ __global__ void __launch_bounds__(BLOCK) k_fill_rows(uint4* __restrict__ out, co
     }
 }
 
+// out = the rows of several arrays, one segment after the other (pGroup.toElementArray(PGroupElementArray[]) and copyOfRange in
+// one).  Segment k begins at output row seg[k].first and is read from seg[k].src, the source's row from[k]; the table holds the
+// non-empty segments only, so `first` rises strictly and seg[0].first = 0.  One thread per 16-byte chunk of an output row, as
+// k_gather: consecutive lanes write consecutive chunks, and read consecutive chunks too wherever they share a segment.  The
+// segment of a row is found by binary search (lanes of a wave that straddles a boundary take different branches THERE, over
+// a table that sits in cache); the copy itself is one load and one store issued by the whole wave after the search.
+struct RowSegment {
+    u64 first;               // first output row of the segment
+    const uint4* src;        // row from[k] of its source
+};
+static_assert(sizeof(RowSegment) == 16, "a table entry is one 16-byte load");
+__global__ void __launch_bounds__(BLOCK) k_rows_segments(uint4* __restrict__ out, const RowSegment* __restrict__ seg, u32 nseg,
+                                                         size_t n_out, int chunks_per_row) {
+    size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    size_t total = n_out * (size_t)chunks_per_row;
+    for (; t < total; t += (size_t)gridDim.x * BLOCK) {
+        size_t row;
+        int c;
+        split_chunk(t, chunks_per_row, row, c);
+        u32 lo = 0, hi = nseg;                       // seg[lo].first <= row < seg[hi].first (seg[nseg].first = n_out, not stored)
+        while (hi - lo > 1) {
+            const u32 mid = lo + ((hi - lo) >> 1);
+            if (seg[mid].first <= (u64)row) lo = mid;
+            else hi = mid;
+        }
+        const RowSegment s = seg[lo];
+        // (a pointer read from memory is a generic one to the compiler: said to be global, the load is global_load_dwordx4, not flat_)
+        typedef u32 chunk_t __attribute__((ext_vector_type(4)));
+        const auto* src = (const __attribute__((address_space(1))) chunk_t*)s.src;
+        const chunk_t v = src[(row - (size_t)s.first) * (size_t)chunks_per_row + c];
+        out[t] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // K2 fixed base.  Table T[k][d] = base^(d * 2^(w*k)), k < nwin, d < 2^w, rows of W words at
 // (k*2^w + d)*W.  The host supplies sq[j] = base^(2^j) (the sequential squaring chain); level l

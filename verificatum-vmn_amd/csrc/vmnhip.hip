@@ -3647,6 +3647,50 @@ extern "C" int vmn_garray_copy_range(const vmn_garray* x, size_t from, size_t to
     *out = r;
     return VMN_OK;
 }
+// One launch whatever nseg is, and no second path for one segment: the small calls run the kernel that the large ones run.
+extern "C" int vmn_garray_from_segments(vmn_group* grp, const vmn_garray* const* src, const size_t* from, const size_t* to, size_t nseg,
+                                        vmn_garray** out) {
+    ARG_CHECK(out, "null argument");
+    *out = nullptr;
+    ARG_CHECK(grp && (nseg == 0 || (src && from && to)), "null argument");
+    ARG_CHECK(nseg <= 65536, "more than 65536 segments");
+    const size_t W = elem_words(grp->P);
+    size_t total = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        ARG_CHECK(src[k], "null argument");
+        ARG_CHECK(src[k]->grp == grp, "a source belongs to another group");
+        ARG_CHECK(from[k] <= to[k] && to[k] <= src[k]->n, "range out of bounds");
+        ARG_CHECK(to[k] - from[k] <= SIZE_MAX / (W * sizeof(uint32_t)) - total, "the row total overflows");
+        total += to[k] - from[k];
+    }
+    vmn_ctx* ctx = LANE(grp->ctx);
+    VMN_ENTER(ctx);
+    std::vector<RowSegment> table;
+    size_t first = 0;
+    for (size_t k = 0; k < nseg; ++k) {
+        if (to[k] == from[k]) continue;
+        table.push_back(RowSegment{(u64)first, reinterpret_cast<const uint4*>(src[k]->d + from[k] * W)});
+        first += to[k] - from[k];
+    }
+    vmn_garray* r = nullptr;
+    VMN_TRY(new_garray(grp, total, &r));
+    int rc = VMN_OK;
+    if (total) {
+        DevTmp dseg(ctx);
+        rc = dseg.alloc(table.size() * sizeof(RowSegment));
+        if (rc == VMN_OK) rc = h2d(ctx, dseg.p, table.data(), table.size() * sizeof(RowSegment));
+        const int cpr = (int)(W / 4);
+        if (rc == VMN_OK)
+            rc = launch_light(ctx, "segments", k_rows_segments, light_grid(ctx, total * cpr), reinterpret_cast<uint4*>(r->d),
+                              (const RowSegment*)dseg.as<RowSegment>(), (uint32_t)table.size(), total, cpr);
+    }
+    if (rc != VMN_OK) {
+        vmn_garray_free(r);
+        return rc;
+    }
+    *out = r;
+    return VMN_OK;
+}
 extern "C" int vmn_garray_extract(const vmn_garray* x, const uint8_t* keep_host, vmn_garray** out) {
     ARG_CHECK(x && out && (keep_host || x->n == 0), "null argument");
     VMN_ENTER(LANE(x->grp->ctx));
