@@ -66,13 +66,16 @@ vmn_ctx* vmn::lane_of(vmn_ctx* c) { return (c && tl_helper_of == c && c->helper)
 extern "C" void vmn_report_error(const char* message) { vmn::set_error("%s", message ? message : ""); }
 extern "C" const char* vmn_version(void) { return "vmnhip 0.1 (gfx950, radix-2^28 lazy-carry Montgomery)"; }
 
-#define ARG_CHECK(cond, msg)             \
-    do {                                 \
-        if (!(cond)) {                   \
-            vmn::set_error("%s: %s", __func__, msg); \
-            return VMN_ERR_ARG;          \
-        }                                \
+// A refusal: the message behind the name of the entry point (a helper that checks for its callers is given their name as `fn`).
+#define REFUSE_IF(cond, fn, code, msg)            \
+    do {                                          \
+        if (cond) {                               \
+            vmn::set_error("%s: %s", fn, msg);    \
+            return code;                          \
+        }                                         \
     } while (0)
+#define ARG_CHECK(cond, msg) REFUSE_IF(!(cond), __func__, VMN_ERR_ARG, msg)
+#define UNSUPPORTED_IF(cond, msg) REFUSE_IF(cond, __func__, VMN_ERR_UNSUPPORTED, msg)
 
 // ------------------------------------------------------------------------------------------------
 // size dispatch
@@ -2106,9 +2109,60 @@ static int hexlines_upload_layout(vmn_ctx* ctx, const hexlines::Layout& L, DevTm
 }
 static unsigned hexlines_grid(size_t nlines) { return (unsigned)((nlines * HEXLINES_LANES + BLOCK - 1) / BLOCK); }
 
-// Where the lines of a text are (both line interfaces): count() uploads the text and counts its lines -- terminators per chunk
-// and their scan --, walk() writes where every line begins and ends.  misc: u64 terminators | u32 first bad line | u32 scan total.
+// ---- what the text interfaces share ("One reader and one writer behind the text interfaces") --------------------------
+// The count checks, named by the entry point that asks.
+static int lines_fit(const char* fn, size_t n) {
+    REFUSE_IF(n >= 0xffffffffull, fn, VMN_ERR_ARG, "2^32 lines or more");
+    return VMN_OK;
+}
+static int total_fits(const char* fn, size_t n, size_t ncomp, const char* too_many) {
+    const size_t total = n * ncomp;
+    REFUSE_IF(total / ncomp != n || total >= ((size_t)1 << 40), fn, VMN_ERR_ARG, too_many);
+    return VMN_OK;
+}
+static int blocks_fit(const char* fn, size_t blocks, const char* too_many) {
+    REFUSE_IF(blocks >= ((size_t)1 << 31), fn, VMN_ERR_ARG, too_many);
+    return VMN_OK;
+}
+// ncomp arrays of one group and one size
+static bool same_group_and_size(const vmn_garray* const* comps, size_t ncomp) {
+    if (!comps || !comps[0]) return false;
+    for (size_t c = 0; c < ncomp; ++c)
+        if (!comps[c] || comps[c]->grp != comps[0]->grp || comps[c]->n != comps[0]->n) return false;
+    return true;
+}
+
+// The arrays a reader gives out: k of n rows over one group.  What release_to() has not handed over is freed.
+struct OutArrays {
+    std::vector<vmn_garray*> a;
+    OutArrays() = default;
+    OutArrays(const OutArrays&) = delete;
+    ~OutArrays() {
+        for (vmn_garray* x : a) vmn_garray_free(x);
+    }
+    int alloc(vmn_group* grp, size_t k, size_t n) {
+        a.assign(k, nullptr);
+        for (size_t c = 0; c < k; ++c) VMN_TRY(new_garray(grp, n, &a[c]));
+        return VMN_OK;
+    }
+    void release_to(vmn_garray** out) {
+        std::copy(a.begin(), a.end(), out);
+        a.clear();
+    }
+};
+// what a reader leaves behind when it gives out no arrays
+static void reader_outs_clear(vmn_garray** out, size_t k, size_t* n_out, int* ok, size_t* bad_line) {
+    std::fill(out, out + k, nullptr);
+    *n_out = 0;
+    *ok = 0;
+    *bad_line = 0;
+}
+
+// Where the lines of a text are (all line interfaces): count() uploads the text and counts its lines -- terminators per chunk
+// and their scan --, walk() writes where every line begins and ends, refused() names the first line the interface's kernel
+// turned down.  misc: u64 terminators | u32 first bad line | u32 scan total.
 struct TextLines {
+    static constexpr uint32_t NO_LINE = 0xffffffffu;
     DevTmp dtext, counts, first, bsum, misc, starts, ends;
     const char* family;
     size_t len = 0, nchunks = 0, nlines = 0;
@@ -2119,7 +2173,8 @@ struct TextLines {
         set_error("reading %s: %s", family, why);
         return VMN_ERR_ARG;
     }
-    int count(vmn_ctx* ctx, const uint8_t* utext, size_t text_len) {
+    int count(vmn_ctx* ctx, const char* chars, size_t text_len) {
+        const uint8_t* utext = reinterpret_cast<const uint8_t*>(chars);
         len = text_len;
         nchunks = (len + HEXLINES_CHUNK - 1) / HEXLINES_CHUNK;
         if (nchunks >= ((size_t)1 << 31)) return refuse("text too long");
@@ -2131,7 +2186,7 @@ struct TextLines {
         VMN_TRY(first.alloc((nchunks + 1) * sizeof(uint32_t)));
         VMN_TRY(bsum.alloc((scan_blocks + 1) * sizeof(uint32_t)));
         VMN_TRY(misc.alloc(16));
-        const uint32_t misc_init[4] = {0, 0, 0xffffffffu, 0};
+        const uint32_t misc_init[4] = {0, 0, NO_LINE, 0};
         VMN_TRY(h2d(ctx, misc.p, misc_init, sizeof(misc_init)));
         VMN_TRY(launch_light(ctx, family, k_hexlines_count, (unsigned)nchunks, counts.as<uint32_t>(), (unsigned long long*)misc.p, text(), len));
         VMN_TRY(launch_light(ctx, family, k_u32_blocksum, (unsigned)scan_blocks, bsum.as<uint32_t>(), (const uint32_t*)counts.as<uint32_t>(),
@@ -2154,8 +2209,62 @@ struct TextLines {
         return launch_light(ctx, family, k_hexlines_walk, (unsigned)nchunks, (u64*)starts.p, (u64*)ends.p, text(), len,
                             (const uint32_t*)first.as<uint32_t>(), (uint32_t)nlines);
     }
-    int read_first_bad(vmn_ctx* ctx, uint32_t* bad) { return d2h(ctx, bad, first_bad(), sizeof(*bad)); }
+    // a list of another length than the expected one (0: any length): the line to name is the first that is missing or too many
+    bool miscounted(size_t expected_n, size_t* bad_line) const {
+        if (expected_n == 0 || nlines == expected_n) return false;
+        *bad_line = std::min(nlines, expected_n);
+        return true;
+    }
+    // the first line a kernel has written to first_bad(), if any
+    int refused(vmn_ctx* ctx, bool* any, size_t* bad_line) {
+        uint32_t bad = NO_LINE;
+        VMN_TRY(d2h(ctx, &bad, first_bad(), sizeof(bad)));
+        *any = bad != NO_LINE;
+        if (*any) *bad_line = bad;
+        return VMN_OK;
+    }
 };
+
+// The records of arrays.a.size() components through the import kernels -- component c from base + offset(c), `stride` apart,
+// leaf headers as `mode` says -- and then(c) behind each.
+template <class Offset, class Then>
+static int import_components(vmn_ctx* ctx, vmn_group* grp, const uint8_t* base, Offset offset, size_t stride, int mode, size_t n,
+                             const OutArrays& arrays, Then then) {
+    for (size_t c = 0; c < arrays.a.size(); ++c) {
+        note_work(ctx, grp->P, (grp->P.ec ? 7.0 : 1.0) * (double)n);
+        VMN_TRY(import_rows_launch(ctx, grp->P, grp->nbytes, base + offset(c), stride, mode, n, arrays.a[c]->d));
+        VMN_TRY(then(c));
+    }
+    return VMN_OK;
+}
+// the same between clearing and reading the flags of the import kernels (bit 0: a value out of range, bit 2: a bad leaf header)
+template <class Offset>
+static int import_components_flagged(vmn_ctx* ctx, vmn_group* grp, const uint8_t* base, Offset offset, size_t stride, int mode, size_t n,
+                                     const OutArrays& arrays, uint32_t* flags) {
+    *flags = 0;
+    if (!n) return VMN_OK;
+    VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
+    VMN_TRY(import_components(ctx, grp, base, offset, stride, mode, n, arrays, [](size_t) { return VMN_OK; }));
+    return read_flag(ctx, flags);
+}
+
+// The end of a writer whose lines differ in length, behind its lengths kernel (bsum: the bytes of every group of lines and one
+// word more): where every group begins, the length of the text to the host, the caller's buffer judged, emit(text) -- the
+// interface's launch --, the text to the host.
+template <class Emit>
+static int write_text_tail(const char* fn, vmn_ctx* ctx, const char* family, DevTmp& bsum, size_t groups, char* out, size_t cap,
+                           const char* too_small, size_t* written, Emit emit) {
+    VMN_TRY(launch_light(ctx, family, k_jsonlines_offsets, 1u, (u64*)bsum.p, groups, (u64*)bsum.p + groups));
+    uint64_t text_bytes = 0;
+    VMN_TRY(d2h(ctx, &text_bytes, (const u64*)bsum.p + groups, sizeof(text_bytes)));
+    REFUSE_IF(text_bytes > cap || !out, fn, VMN_ERR_ARG, too_small);
+    DevTmp dtext(ctx);
+    VMN_TRY(dtext.alloc(text_bytes + 16));
+    VMN_TRY(emit(dtext.as<uint8_t>()));
+    VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));
+    *written = (size_t)text_bytes;
+    return VMN_OK;
+}
 
 extern "C" size_t vmn_hexlines_line_bytes_keyed(const vmn_group* grp, size_t keywidth, size_t width) {
     return grp && hexlines_width_ok(grp, keywidth, width) ? hexlines::line_bytes(grp->curve != nullptr, grp->nbytes, keywidth, width) : 0;
@@ -2168,22 +2277,14 @@ extern "C" int vmn_garrays_from_hexlines_keyed(vmn_group* grp, size_t keywidth, 
     const size_t width = keywidth * omega;                     // components of a half: the nesting is in the layout alone
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
-    for (size_t c = 0; c < 2 * width; ++c) out[c] = nullptr;
-    *n_out = 0;
-    *format_ok = 0;
-    *first_bad_line = 0;
+    reader_outs_clear(out, 2 * width, n_out, format_ok, first_bad_line);
     if (all_in_range) *all_in_range = 1;
     const hexlines::Layout L = hexlines::make_layout(grp->curve != nullptr, grp->nbytes, keywidth, omega);
-    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
 
-    // where the lines are: terminators per chunk, their scan, then the starts and ends
     TextLines lines(ctx, "hexlines");
-    VMN_TRY(lines.count(ctx, utext, len));
+    VMN_TRY(lines.count(ctx, text, len));
     const size_t nlines = lines.nlines;
-    if (expected_n != 0 && nlines != expected_n) {
-        *first_bad_line = std::min(nlines, expected_n);
-        return VMN_OK;
-    }
+    if (lines.miscounted(expected_n, first_bad_line)) return VMN_OK;
 
     // digits -> records, the text and the outer framing judged on the way
     DevTmp rec(ctx), layout(ctx);
@@ -2195,35 +2296,19 @@ extern "C" int vmn_garrays_from_hexlines_keyed(vmn_group* grp, size_t keywidth, 
         VMN_TRY(launch_light(ctx, "hexlines", k_hexlines_decode, hexlines_grid(nlines), rec.as<uint8_t>(), lines.text(), len,
                              (const u64*)lines.starts.p, (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)L.B, d_tmpl, d_mask,
                              lines.first_bad()));
-        uint32_t bad = 0;
-        VMN_TRY(lines.read_first_bad(ctx, &bad));
-        if (bad != 0xffffffffu) {
-            *first_bad_line = bad;
-            return VMN_OK;
-        }
+        bool refused = false;
+        VMN_TRY(lines.refused(ctx, &refused, first_bad_line));
+        if (refused) return VMN_OK;
     }
 
     // the records, component by component, through the import kernels (leaf headers on, one record apart)
-    std::vector<vmn_garray*> arrays(2 * width, nullptr);
-    auto drop = [&] {
-        for (vmn_garray* a : arrays) vmn_garray_free(a);
-    };
-    int rc = VMN_OK;
-    for (size_t c = 0; c < 2 * width && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    OutArrays arrays;
+    VMN_TRY(arrays.alloc(grp, 2 * width, nlines));
     uint32_t fl = 0;
-    if (rc == VMN_OK && nlines) {
-        rc = dev_zero(ctx, ctx->flags, sizeof(uint32_t));
-        for (size_t c = 0; c < 2 * width && rc == VMN_OK; ++c) {
-            note_work(ctx, grp->P, (grp->P.ec ? 7.0 : 1.0) * (double)nlines);
-            rc = import_rows_launch(ctx, grp->P, grp->nbytes, rec.as<uint8_t>() + L.offset[c], L.B, 1, nlines, arrays[c]->d);
-        }
-        if (rc == VMN_OK) rc = read_flag(ctx, &fl);
-    }
-    if (rc != VMN_OK || (fl & 4u)) {            // (a leaf header the decode passed and the import refuses: cannot happen, and is no array)
-        drop();
-        return rc;
-    }
-    for (size_t c = 0; c < 2 * width; ++c) out[c] = arrays[c];
+    VMN_TRY(import_components_flagged(ctx, grp, rec.as<uint8_t>(), [&](size_t c) { return L.offset[c]; }, L.B, 1, nlines, arrays, &fl));
+    // (bit 2 -- a leaf header the decode passed and the import refuses, which cannot happen -- is VMN_OK without a list, format_ok = 0)
+    if (fl & 4u) return VMN_OK;
+    arrays.release_to(out);
     *n_out = nlines;
     *format_ok = 1;
     if (all_in_range) *all_in_range = (fl & 1u) ? 0 : 1;
@@ -2236,10 +2321,8 @@ extern "C" int vmn_garrays_from_hexlines(vmn_group* grp, size_t width, const cha
 
 // the arrays of a ciphertext list: 2 * keywidth * width of them, of one group and one size
 static bool hexlines_comps_ok(const vmn_garray* const* comps, size_t keywidth, size_t width) {
-    if (!comps || !comps[0] || !hexlines_width_ok(comps[0]->grp, keywidth, width)) return false;
-    for (size_t c = 0; c < 2 * keywidth * width; ++c)
-        if (!comps[c] || comps[c]->grp != comps[0]->grp || comps[c]->n != comps[0]->n) return false;
-    return true;
+    if (!comps || !comps[0] || !hexlines_width_ok(comps[0]->grp, keywidth, width)) return false;       // (the widths bound the count below)
+    return same_group_and_size(comps, 2 * keywidth * width);
 }
 extern "C" size_t vmn_garrays_hexlines_size_keyed(const vmn_garray* const* comps, size_t keywidth, size_t width) {
     if (!hexlines_comps_ok(comps, keywidth, width)) return 0;
@@ -2253,7 +2336,7 @@ extern "C" int vmn_garrays_to_hexlines_keyed(const vmn_garray* const* comps, siz
     vmn_group* grp = comps[0]->grp;
     const size_t n = comps[0]->n;
     ARG_CHECK(out || n == 0, "null argument");
-    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
+    VMN_TRY(lines_fit(__func__, n));
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
     if (n == 0) return VMN_OK;
@@ -2359,13 +2442,7 @@ static int decimal_tables(vmn_group* grp, const vmn_group::DecimalTables** out) 
     return VMN_OK;
 }
 static bool jsonlines_width_ok(size_t width) { return width >= 1 && width <= jsonlines::MAX_WIDTH; }
-#define JSON_GROUP_CHECK(grp)                                                                                  \
-    do {                                                                                                       \
-        if ((grp)->curve) {                                                                                    \
-            set_error("%s: the json interface covers modular groups only (as the reference's)", __func__);     \
-            return VMN_ERR_UNSUPPORTED;                                                                        \
-        }                                                                                                      \
-    } while (0)
+static const char* const JSON_NO_CURVES = "the json interface covers modular groups only (as the reference's)";
 
 extern "C" size_t vmn_jsonlines_max_line_bytes(const vmn_group* grp, size_t width) {
     if (!grp || grp->curve || !jsonlines_width_ok(width)) return 0;
@@ -2378,69 +2455,45 @@ extern "C" int vmn_garrays_from_jsonlines(vmn_group* grp, size_t width, const ch
     ARG_CHECK(jsonlines_width_ok(width), "width out of range");
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
-    for (size_t c = 0; c < 2 * width; ++c) out[c] = nullptr;
-    *n_out = 0;
-    *format_ok = 0;
-    *first_bad_line = 0;
+    reader_outs_clear(out, 2 * width, n_out, format_ok, first_bad_line);
     if (all_in_range) *all_in_range = 1;
-    JSON_GROUP_CHECK(grp);
+    UNSUPPORTED_IF(grp->curve, JSON_NO_CURVES);
     const vmn_group::DecimalTables* T = nullptr;
     VMN_TRY(decimal_tables(grp, &T));
-    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
     const size_t ncomp = 2 * width, nbytes = grp->nbytes;
 
     TextLines lines(ctx, "jsonlines");
-    VMN_TRY(lines.count(ctx, utext, len));
+    VMN_TRY(lines.count(ctx, text, len));
     const size_t nlines = lines.nlines;
-    if (expected_n != 0 && nlines != expected_n) {
-        *first_bad_line = std::min(nlines, expected_n);
-        return VMN_OK;
-    }
+    if (lines.miscounted(expected_n, first_bad_line)) return VMN_OK;
 
     // the grammar of every line and the digit spans of its numbers; then decimal -> records of nbytes, component by component
     DevTmp span_at(ctx), span_len(ctx), rec(ctx);
     const size_t total = nlines * ncomp;
     if (nlines) {
-        ARG_CHECK(total / ncomp == nlines && total < ((size_t)1 << 40), "too many numbers");
+        VMN_TRY(total_fits(__func__, nlines, ncomp, "too many numbers"));
         VMN_TRY(span_at.alloc(total * sizeof(uint64_t)));
         VMN_TRY(span_len.alloc(total * sizeof(uint32_t)));
         VMN_TRY(lines.walk(ctx));
         VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_scan, grid_for(nlines), (u64*)span_at.p, span_len.as<uint32_t>(), lines.text(), len,
                              (const u64*)lines.starts.p, (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)width, lines.first_bad()));
-        uint32_t bad = 0;
-        VMN_TRY(lines.read_first_bad(ctx, &bad));
-        if (bad != 0xffffffffu) {
-            *first_bad_line = bad;
-            return VMN_OK;
-        }
+        bool refused = false;
+        VMN_TRY(lines.refused(ctx, &refused, first_bad_line));
+        if (refused) return VMN_OK;
         VMN_TRY(rec.alloc(total * nbytes + 16));
         const size_t blocks = (total + DEC_VPB - 1) / DEC_VPB;
-        ARG_CHECK(blocks < ((size_t)1 << 31), "too many numbers");
+        VMN_TRY(blocks_fit(__func__, blocks, "too many numbers"));
         VMN_TRY(launch_light(ctx, "jsonlines", k_dec_to_rows, (unsigned)blocks, rec.as<uint8_t>(), (uint32_t)nbytes, lines.text(),
                              (const u64*)span_at.p, (const uint32_t*)span_len.as<uint32_t>(), (uint32_t)nlines, (uint32_t)ncomp, T->dmax, T->nwa,
                              (const uint32_t*)T->d_pow10));
     }
 
-    std::vector<vmn_garray*> arrays(ncomp, nullptr);
-    auto drop = [&] {
-        for (vmn_garray* a : arrays) vmn_garray_free(a);
-    };
-    int rc = VMN_OK;
-    for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    // the records through the import kernels (no leaf headers, the components one after the other)
+    OutArrays arrays;
+    VMN_TRY(arrays.alloc(grp, ncomp, nlines));
     uint32_t fl = 0;
-    if (rc == VMN_OK && nlines) {
-        rc = dev_zero(ctx, ctx->flags, sizeof(uint32_t));
-        for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) {
-            note_work(ctx, grp->P, (double)nlines);
-            rc = import_rows_launch(ctx, grp->P, nbytes, rec.as<uint8_t>() + c * nlines * nbytes, nbytes, 0, nlines, arrays[c]->d);
-        }
-        if (rc == VMN_OK) rc = read_flag(ctx, &fl);
-    }
-    if (rc != VMN_OK) {
-        drop();
-        return rc;
-    }
-    for (size_t c = 0; c < ncomp; ++c) out[c] = arrays[c];
+    VMN_TRY(import_components_flagged(ctx, grp, rec.as<uint8_t>(), [&](size_t c) { return c * nlines * nbytes; }, nbytes, 0, nlines, arrays, &fl));
+    arrays.release_to(out);                     // (bit 2 of the flags is not looked at here: these records have no leaf headers)
     *n_out = nlines;
     *format_ok = 1;
     if (all_in_range) *all_in_range = (fl & 1u) ? 0 : 1;
@@ -2455,20 +2508,20 @@ static int jsonlines_write(const vmn_garray* const* comps, size_t width, int pla
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
     *written = 0;
-    JSON_GROUP_CHECK(grp);
+    UNSUPPORTED_IF(grp->curve, JSON_NO_CURVES);
     if (n == 0) return VMN_OK;
-    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
+    VMN_TRY(lines_fit(__func__, n));
     const vmn_group::DecimalTables* T = nullptr;
     VMN_TRY(decimal_tables(grp, &T));
     const size_t total = n * ncomp;
-    ARG_CHECK(total / ncomp == n && total < ((size_t)1 << 40), "too many numbers");
-    DevTmp rec(ctx), digits(ctx), counts(ctx), lens(ctx), bsum(ctx), dtext(ctx);
+    VMN_TRY(total_fits(__func__, n, ncomp, "too many numbers"));
+    DevTmp rec(ctx), digits(ctx), counts(ctx), lens(ctx), bsum(ctx);
     VMN_TRY(rec.alloc(total * nbytes + 16));
     VMN_TRY(digits.alloc(total * T->dmax + 16));
     VMN_TRY(counts.alloc(total * sizeof(uint32_t)));
     for (size_t c = 0; c < ncomp; ++c) VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, rec.as<uint8_t>() + c * n * nbytes, nbytes, 0));
     const size_t blocks = (total + DEC_VPB - 1) / DEC_VPB;
-    ARG_CHECK(blocks < ((size_t)1 << 31), "too many numbers");
+    VMN_TRY(blocks_fit(__func__, blocks, "too many numbers"));
     VMN_TRY(launch_light(ctx, "jsonlines", k_rows_to_dec, (unsigned)blocks, digits.as<uint8_t>(), counts.as<uint32_t>(),
                          (const uint8_t*)rec.as<uint8_t>(), (uint32_t)nbytes, total, T->dmax, T->nc, T->nw, (const uint32_t*)T->d_pow2));
     const size_t groups = (n + BLOCK - 1) / BLOCK;
@@ -2476,32 +2529,20 @@ static int jsonlines_write(const vmn_garray* const* comps, size_t width, int pla
     VMN_TRY(bsum.alloc((groups + 1) * sizeof(uint64_t)));
     VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_lengths, (unsigned)groups, lens.as<uint32_t>(), (u64*)bsum.p,
                          (const uint32_t*)counts.as<uint32_t>(), (uint32_t)n, (uint32_t)width, plain));
-    VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_offsets, 1u, (u64*)bsum.p, groups, (u64*)bsum.p + groups));
-    uint64_t text_bytes = 0;
-    VMN_TRY(d2h(ctx, &text_bytes, (const u64*)bsum.p + groups, sizeof(text_bytes)));
-    ARG_CHECK(text_bytes <= cap && out, "the buffer is too small for this list");
-    VMN_TRY(dtext.alloc(text_bytes + 16));
-    VMN_TRY(launch_light(ctx, "jsonlines", k_jsonlines_emit, (unsigned)((n * JSONLINES_LANES + BLOCK - 1) / BLOCK), dtext.as<uint8_t>(),
-                         (const u64*)bsum.p, (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)digits.as<uint8_t>(),
-                         (const uint32_t*)counts.as<uint32_t>(), (uint32_t)n, (uint32_t)width, T->dmax, plain));
-    VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));
-    *written = (size_t)text_bytes;
-    return VMN_OK;
-}
-static bool jsonlines_comps_ok(const vmn_garray* const* comps, size_t ncomp) {
-    if (!comps || !comps[0]) return false;
-    for (size_t c = 0; c < ncomp; ++c)
-        if (!comps[c] || comps[c]->grp != comps[0]->grp || comps[c]->n != comps[0]->n) return false;
-    return true;
+    return write_text_tail(__func__, ctx, "jsonlines", bsum, groups, out, cap, "the buffer is too small for this list", written, [&](uint8_t* dtext) {
+        return launch_light(ctx, "jsonlines", k_jsonlines_emit, (unsigned)((n * JSONLINES_LANES + BLOCK - 1) / BLOCK), dtext, (const u64*)bsum.p,
+                            (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)digits.as<uint8_t>(), (const uint32_t*)counts.as<uint32_t>(),
+                            (uint32_t)n, (uint32_t)width, T->dmax, plain);
+    });
 }
 extern "C" int vmn_garrays_to_jsonlines(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written) {
     ARG_CHECK(comps && written && jsonlines_width_ok(width), "null argument or width out of range");
-    ARG_CHECK(jsonlines_comps_ok(comps, 2 * width), "2 * width arrays of one group and one size are needed");
+    ARG_CHECK(same_group_and_size(comps, 2 * width), "2 * width arrays of one group and one size are needed");
     return jsonlines_write(comps, width, 0, out, cap, written);
 }
 extern "C" int vmn_garrays_to_jsonplain(const vmn_garray* const* comps, size_t width, char* out, size_t cap, size_t* written) {
     ARG_CHECK(comps && written && jsonlines_width_ok(width), "null argument or width out of range");
-    ARG_CHECK(jsonlines_comps_ok(comps, width), "width arrays of one group and one size are needed");
+    ARG_CHECK(same_group_and_size(comps, width), "width arrays of one group and one size are needed");
     return jsonlines_write(comps, width, 1, out, cap, written);
 }
 
@@ -2520,13 +2561,74 @@ extern "C" size_t vmn_group_encode_length(const vmn_group* grp) {
     return encode::encode_length((size_t)hostbig::bit_length(grp->P.n_words));
 }
 static bool textlines_ncomp_ok(size_t ncomp) { return ncomp >= 1 && ncomp <= encode::MAX_COMPONENTS; }
-#define ENCODE_GROUP_CHECK(grp, L)                                                                                             \
-    do {                                                                                                                       \
-        if ((L) == 0) {                                                                                                        \
-            set_error("%s: messages are encoded over a modular group with p = 2q + 1 that holds at least one byte", __func__);  \
-            return VMN_ERR_UNSUPPORTED;                                                                                        \
-        }                                                                                                                      \
-    } while (0)
+
+// Both readers of plaintexts as text: the lines of `text` as records of `rbytes` for all components (k_textlines_records judges
+// the longest admissible line on the way), then convert(lines, records, nlines, arrays) -- the interface's own step from the
+// records to the elements of the ncomp arrays.  (These readers neither clear nor read the flags of the import kernels.)
+template <class Convert>
+static int textlines_read(const char* fn, vmn_group* grp, size_t ncomp, const char* text, size_t len, size_t rbytes, size_t L,
+                          vmn_garray** out, size_t* n_out, int* fits, size_t* first_long_line, Convert convert) {
+    vmn_ctx* ctx = LANE(grp->ctx);
+    TextLines lines(ctx, "textlines");
+    VMN_TRY(lines.count(ctx, text, len));
+    const size_t nlines = lines.nlines, total = nlines * ncomp;
+    DevTmp rec(ctx);
+    if (nlines) {
+        VMN_TRY(total_fits(fn, nlines, ncomp, "too many elements"));
+        const size_t blocks = (total * TEXTLINES_LANES + BLOCK - 1) / BLOCK;
+        VMN_TRY(blocks_fit(fn, blocks, "too many elements"));
+        VMN_TRY(rec.alloc(total * rbytes + 16));
+        VMN_TRY(lines.walk(ctx));
+        VMN_TRY(launch_light(ctx, "textlines", k_textlines_records, (unsigned)blocks, rec.as<uint8_t>(), lines.text(), (const u64*)lines.starts.p,
+                             (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)ncomp, (uint32_t)rbytes, (uint32_t)L, lines.first_bad()));
+        bool refused = false;
+        VMN_TRY(lines.refused(ctx, &refused, first_long_line));
+        if (refused) return VMN_OK;
+    }
+    OutArrays arrays;
+    VMN_TRY(arrays.alloc(grp, ncomp, nlines));
+    if (nlines) VMN_TRY(convert(lines, (const uint8_t*)rec.as<uint8_t>(), nlines, arrays));
+    arrays.release_to(out);
+    *n_out = nlines;
+    *fits = 1;
+    return VMN_OK;
+}
+// Both writers of plaintexts as text.  stage(first, second, &rec, total) allocates the interface's two buffers, uploads what its
+// fold reads and says where the records will be; fold(first, second, plen, n, total), behind the clearing of the flags, exports
+// the arrays and leaves their messages as records of `rbytes` at rec and the length of every piece in plen.  The lengths of the
+// lines, the text and the two verdicts follow.  (Two steps, so that allocations and launches keep the order they always had.)
+template <class Stage, class Fold>
+static int textlines_write(const char* fn, vmn_ctx* ctx, size_t n, size_t ncomp, size_t rbytes, size_t L, char* out, size_t cap,
+                           size_t* written, int* all_wellformed, int* all_utf8, Stage stage, Fold fold) {
+    if (n == 0) return VMN_OK;
+    VMN_TRY(lines_fit(fn, n));
+    VMN_TRY(total_fits(fn, n, ncomp, "too many elements"));
+    const size_t total = n * ncomp, groups = (n + BLOCK - 1) / BLOCK;
+    DevTmp first(ctx), second(ctx), plen(ctx), lens(ctx), bsum(ctx);
+    const uint8_t* rec = nullptr;
+    VMN_TRY(stage(first, second, &rec, total));
+    VMN_TRY(plen.alloc(total * sizeof(uint32_t)));
+    VMN_TRY(lens.alloc(n * sizeof(uint32_t)));
+    VMN_TRY(bsum.alloc((groups + 1) * sizeof(uint64_t)));
+    VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
+    VMN_TRY(fold(first, second, plen.as<uint32_t>(), n, total));
+    VMN_TRY(launch_light(ctx, "textlines", k_textlines_lengths, (unsigned)groups, lens.as<uint32_t>(), (u64*)bsum.p, rec,
+                         (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n, (uint32_t)ncomp, (uint32_t)rbytes, (uint32_t)L, ctx->flags));
+    uint32_t fl = 0;
+    VMN_TRY(write_text_tail(fn, ctx, "textlines", bsum, groups, out, cap, "the buffer is too small for these lines", written, [&](uint8_t* dtext) {
+        VMN_TRY(launch_light(ctx, "textlines", k_textlines_emit, (unsigned)groups, dtext, (const u64*)bsum.p, (const uint32_t*)lens.as<uint32_t>(),
+                             rec, (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n, (uint32_t)ncomp, (uint32_t)rbytes, (uint32_t)L));
+        return read_flag(ctx, &fl);
+    }));
+    if (all_wellformed) *all_wellformed = (fl & TEXTLINES_ILL_FORMED) ? 0 : 1;
+    if (all_utf8) *all_utf8 = (fl & TEXTLINES_NOT_UTF8) ? 0 : 1;
+    return VMN_OK;
+}
+static void textlines_verdicts_clear(size_t* written, int* all_wellformed, int* all_utf8) {
+    *written = 0;
+    if (all_wellformed) *all_wellformed = 1;
+    if (all_utf8) *all_utf8 = 1;
+}
 
 extern "C" int vmn_garrays_from_textlines(vmn_group* grp, size_t ncomp, const char* text, size_t len, vmn_garray** out, size_t* n_out,
                                           int* fits, size_t* first_long_line) {
@@ -2534,120 +2636,56 @@ extern "C" int vmn_garrays_from_textlines(vmn_group* grp, size_t ncomp, const ch
     ARG_CHECK(textlines_ncomp_ok(ncomp), "ncomp out of range");
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
-    for (size_t c = 0; c < ncomp; ++c) out[c] = nullptr;
-    *n_out = 0;
-    *fits = 0;
-    *first_long_line = 0;
+    reader_outs_clear(out, ncomp, n_out, fits, first_long_line);
     const size_t L = vmn_group_encode_length(grp), nbytes = grp->nbytes;
-    ENCODE_GROUP_CHECK(grp, L);
-    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
-
-    TextLines lines(ctx, "textlines");
-    VMN_TRY(lines.count(ctx, utext, len));
-    const size_t nlines = lines.nlines, total = nlines * ncomp;
-
-    // text -> records of all components, the longest admissible line checked on the way
-    DevTmp rec(ctx);
-    if (nlines) {
-        ARG_CHECK(total / ncomp == nlines && total < ((size_t)1 << 40), "too many elements");
-        const size_t blocks = (total * TEXTLINES_LANES + BLOCK - 1) / BLOCK;
-        ARG_CHECK(blocks < ((size_t)1 << 31), "too many elements");
-        VMN_TRY(rec.alloc(total * nbytes + 16));
-        VMN_TRY(lines.walk(ctx));
-        VMN_TRY(launch_light(ctx, "textlines", k_textlines_records, (unsigned)blocks, rec.as<uint8_t>(), lines.text(), (const u64*)lines.starts.p,
-                             (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)ncomp, (uint32_t)nbytes, (uint32_t)L, lines.first_bad()));
-        uint32_t bad = 0;
-        VMN_TRY(lines.read_first_bad(ctx, &bad));
-        if (bad != 0xffffffffu) {
-            *first_long_line = bad;
-            return VMN_OK;
-        }
-    }
-
-    // the records through the import kernel, then v or p - v by the Jacobi symbol of every row, in place
-    std::vector<vmn_garray*> arrays(ncomp, nullptr);
-    int rc = VMN_OK;
-    for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    UNSUPPORTED_IF(L == 0, "messages are encoded over a modular group with p = 2q + 1 that holds at least one byte");
     const vmn_modulus& m = grp->P;
-    for (size_t c = 0; c < ncomp && rc == VMN_OK && nlines; ++c) {
-        note_work(ctx, m, (double)nlines);
-        rc = import_rows_launch(ctx, m, nbytes, rec.as<uint8_t>() + c * nlines * nbytes, nbytes, 0, nlines, arrays[c]->d);
-        if (rc == VMN_OK)
-            rc = with_cfg(m, [&]<class C, class W>(C, W) -> int {
+    // the records through the import kernel, then v or p - v by the Jacobi symbol of every row, in place
+    return textlines_read(__func__, grp, ncomp, text, len, nbytes, L, out, n_out, fits, first_long_line,
+                          [&](TextLines&, const uint8_t* rec, size_t nlines, const OutArrays& arrays) {
+        return import_components(ctx, grp, rec, [&](size_t c) { return c * nlines * nbytes; }, nbytes, 0, nlines, arrays, [&](size_t c) {
+            uint32_t* rows = arrays.a[c]->d;
+            return with_cfg(m, [&]<class C, class W>(C, W) -> int {
                 if constexpr (C::LPE == 1)
-                    return launch_light(ctx, "encode_residue", k_jacobi_fix<C>, grid_for(nlines), arrays[c]->d, nlines, (const uint32_t*)m.d_n);
+                    return launch_light(ctx, "encode_residue", k_jacobi_fix<C>, grid_for(nlines), rows, nlines, (const uint32_t*)m.d_n);
                 else if constexpr (!C::WIDE)
-                    return launch_light(ctx, "encode_residue", k_jacobi_fix_lanes<C>, egrid(m, nlines), arrays[c]->d, nlines,
-                                        (const uint32_t*)m.d_n);
+                    return launch_light(ctx, "encode_residue", k_jacobi_fix_lanes<C>, egrid(m, nlines), rows, nlines, (const uint32_t*)m.d_n);
                 else
                     return VMN_ERR_ARG;
             });
-    }
-    if (rc != VMN_OK) {
-        for (vmn_garray* a : arrays) vmn_garray_free(a);
-        return rc;
-    }
-    for (size_t c = 0; c < ncomp; ++c) out[c] = arrays[c];
-    *n_out = nlines;
-    *fits = 1;
-    return VMN_OK;
+        });
+    });
 }
 
 extern "C" int vmn_garrays_to_textlines(const vmn_garray* const* comps, size_t ncomp, char* out, size_t cap, size_t* written, int* all_wellformed,
                                         int* all_utf8) {
     ARG_CHECK(comps && written && textlines_ncomp_ok(ncomp), "null argument or ncomp out of range");
-    ARG_CHECK(jsonlines_comps_ok(comps, ncomp), "ncomp arrays of one group and one size are needed");
+    ARG_CHECK(same_group_and_size(comps, ncomp), "ncomp arrays of one group and one size are needed");
     vmn_group* grp = comps[0]->grp;
-    const size_t n = comps[0]->n, nbytes = grp->nbytes;
+    const size_t nbytes = grp->nbytes;
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
-    *written = 0;
-    if (all_wellformed) *all_wellformed = 1;
-    if (all_utf8) *all_utf8 = 1;
+    textlines_verdicts_clear(written, all_wellformed, all_utf8);
     const size_t L = vmn_group_encode_length(grp);
-    ENCODE_GROUP_CHECK(grp, L);
-    if (n == 0) return VMN_OK;
-    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
-    const size_t total = n * ncomp;
-    ARG_CHECK(total / ncomp == n && total < ((size_t)1 << 40), "too many elements");
-    // p and q as records, for the fold
-    std::vector<uint8_t> primes(2 * nbytes);
-    hostbig::to_be(grp->P.n_words, primes.data(), nbytes);
-    {
+    UNSUPPORTED_IF(L == 0, "messages are encoded over a modular group with p = 2q + 1 that holds at least one byte");
+    return textlines_write(__func__, ctx, comps[0]->n, ncomp, nbytes, L, out, cap, written, all_wellformed, all_utf8,
+                           [&](DevTmp& rec, DevTmp& dprimes, const uint8_t** folded, size_t total) -> int {
+        // p and q as records, for the fold
+        std::vector<uint8_t> primes(2 * nbytes);
+        hostbig::to_be(grp->P.n_words, primes.data(), nbytes);
         Big q = grp->Q.n_words;
         q.resize(grp->P.n_words.size(), 0);
         hostbig::to_be(q, primes.data() + nbytes, nbytes);
-    }
-    const size_t groups = (n + BLOCK - 1) / BLOCK;
-    DevTmp rec(ctx), dprimes(ctx), plen(ctx), lens(ctx), bsum(ctx), dtext(ctx);
-    VMN_TRY(rec.alloc(total * nbytes + 16));
-    VMN_TRY(dprimes.alloc(primes.size()));
-    VMN_TRY(plen.alloc(total * sizeof(uint32_t)));
-    VMN_TRY(lens.alloc(n * sizeof(uint32_t)));
-    VMN_TRY(bsum.alloc((groups + 1) * sizeof(uint64_t)));
-    VMN_TRY(h2d(ctx, dprimes.p, primes.data(), primes.size()));
-    VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
-    for (size_t c = 0; c < ncomp; ++c) VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, rec.as<uint8_t>() + c * n * nbytes, nbytes, 0));
-    VMN_TRY(launch_light(ctx, "textlines", k_textlines_fold, grid_for(total), rec.as<uint8_t>(), plen.as<uint32_t>(), total, (uint32_t)nbytes,
-                         (uint32_t)L, (const uint8_t*)dprimes.as<uint8_t>(), (const uint8_t*)dprimes.as<uint8_t>() + nbytes, ctx->flags));
-    VMN_TRY(launch_light(ctx, "textlines", k_textlines_lengths, (unsigned)groups, lens.as<uint32_t>(), (u64*)bsum.p,
-                         (const uint8_t*)rec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n, (uint32_t)ncomp, (uint32_t)nbytes,
-                         (uint32_t)L, ctx->flags));
-    VMN_TRY(launch_light(ctx, "textlines", k_jsonlines_offsets, 1u, (u64*)bsum.p, groups, (u64*)bsum.p + groups));
-    uint64_t text_bytes = 0;
-    VMN_TRY(d2h(ctx, &text_bytes, (const u64*)bsum.p + groups, sizeof(text_bytes)));
-    ARG_CHECK(text_bytes <= cap && out, "the buffer is too small for these lines");
-    VMN_TRY(dtext.alloc(text_bytes + 16));
-    VMN_TRY(launch_light(ctx, "textlines", k_textlines_emit, (unsigned)groups, dtext.as<uint8_t>(), (const u64*)bsum.p,
-                         (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)rec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n,
-                         (uint32_t)ncomp, (uint32_t)nbytes, (uint32_t)L));
-    uint32_t fl = 0;
-    VMN_TRY(read_flag(ctx, &fl));
-    VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));
-    *written = (size_t)text_bytes;
-    if (all_wellformed) *all_wellformed = (fl & TEXTLINES_ILL_FORMED) ? 0 : 1;
-    if (all_utf8) *all_utf8 = (fl & TEXTLINES_NOT_UTF8) ? 0 : 1;
-    return VMN_OK;
+        VMN_TRY(rec.alloc(total * nbytes + 16));
+        VMN_TRY(dprimes.alloc(primes.size()));
+        *folded = rec.as<uint8_t>();                // (folded in place)
+        return h2d(ctx, dprimes.p, primes.data(), primes.size());
+    }, [&](DevTmp& rec, DevTmp& dprimes, uint32_t* plen, size_t n, size_t total) {
+        for (size_t c = 0; c < ncomp; ++c)
+            VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, rec.as<uint8_t>() + c * n * nbytes, nbytes, 0));
+        return launch_light(ctx, "textlines", k_textlines_fold, grid_for(total), rec.as<uint8_t>(), plen, total, (uint32_t)nbytes, (uint32_t)L,
+                            (const uint8_t*)dprimes.as<uint8_t>(), (const uint8_t*)dprimes.as<uint8_t>() + nbytes, ctx->flags);
+    });
 }
 
 // ---- the same over curve groups: messages as points (csrc/ec_encode_layout.h, csrc/ec_encode_kernels.h) ---------------------------
@@ -2656,137 +2694,74 @@ extern "C" size_t vmn_ec_group_encode_length(const vmn_group* grp) {
     if (!grp || !grp->curve) return 0;
     return encode::point_encode_length((size_t)hostbig::bit_length(grp->curve->p_words));
 }
-#define EC_ENCODE_GROUP_CHECK(grp, L)                                                                        \
-    do {                                                                                                     \
-        if ((L) == 0) {                                                                                      \
-            set_error("%s: messages are encoded as points over a curve group that holds at least one byte", __func__); \
-            return VMN_ERR_UNSUPPORTED;                                                                      \
-        }                                                                                                    \
-    } while (0)
-
 extern "C" int vmn_ec_arrays_from_textlines(vmn_group* grp, size_t ncomp, const char* text, size_t len, vmn_garray** out, size_t* n_out,
                                             int* fits, size_t* first_long_line) {
     ARG_CHECK(grp && out && n_out && fits && first_long_line && (text || len == 0), "null argument");
     ARG_CHECK(textlines_ncomp_ok(ncomp), "ncomp out of range");
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
-    for (size_t c = 0; c < ncomp; ++c) out[c] = nullptr;
-    *n_out = 0;
-    *fits = 0;
-    *first_long_line = 0;
+    reader_outs_clear(out, ncomp, n_out, fits, first_long_line);
     const size_t L = vmn_ec_group_encode_length(grp), tbytes = L + encode::LENGTH_BYTES;
-    EC_ENCODE_GROUP_CHECK(grp, L);
-    const uint8_t* utext = reinterpret_cast<const uint8_t*>(text);
-
-    TextLines lines(ctx, "textlines");
-    VMN_TRY(lines.count(ctx, utext, len));
-    const size_t nlines = lines.nlines, total = nlines * ncomp;
-
-    // text -> the records T of all components (L + 4 bytes each), the longest admissible line checked on the way
-    DevTmp rec(ctx);
-    if (nlines) {
-        ARG_CHECK(total / ncomp == nlines && total < ((size_t)1 << 40), "too many elements");
-        const size_t blocks = (total * TEXTLINES_LANES + BLOCK - 1) / BLOCK;
-        ARG_CHECK(blocks < ((size_t)1 << 31), "too many elements");
-        VMN_TRY(rec.alloc(total * tbytes + 16));
-        VMN_TRY(lines.walk(ctx));
-        VMN_TRY(launch_light(ctx, "textlines", k_textlines_records, (unsigned)blocks, rec.as<uint8_t>(), lines.text(), (const u64*)lines.starts.p,
-                             (const u64*)lines.ends.p, (uint32_t)nlines, (uint32_t)ncomp, (uint32_t)tbytes, (uint32_t)L, lines.first_bad()));
-        uint32_t bad = 0;
-        VMN_TRY(lines.read_first_bad(ctx, &bad));
-        if (bad != 0xffffffffu) {
-            *first_long_line = bad;
-            return VMN_OK;
-        }
-    }
-
-    // per component: the counter search into the rows (x, x^3 + a x + b), then the smaller root in place.  The word that named
-    // the first long line (0xffffffff here) now receives the first line whose search or root failed.
-    std::vector<vmn_garray*> arrays(ncomp, nullptr);
-    int rc = VMN_OK;
-    for (size_t c = 0; c < ncomp && rc == VMN_OK; ++c) rc = new_garray(grp, nlines, &arrays[c]);
+    UNSUPPORTED_IF(L == 0, "messages are encoded as points over a curve group that holds at least one byte");
+    const char* const fn = __func__;
     const vmn_modulus& m = grp->P;
     const double sqrt_products = grp->curve->ts_s ? 2.0 * (double)m.nbits : (double)m.nbits;      // (Tonelli-Shanks: priced, not counted)
-    for (size_t c = 0; c < ncomp && rc == VMN_OK && nlines; ++c) {
-        rc = with_curve(m, [&]<class E>(E) -> int {
-            note_work(ctx, m, (1.0 + 2.0 * 4.0) * (double)nlines);                // two counters expected, four products each
-            VMN_TRY(launch_light(ctx, "encode_search", k_ec_encode_search<E::S, E::NW, E::KIND>, grid_for(nlines), arrays[c]->d,
-                                 (const uint8_t*)rec.as<uint8_t>() + c * nlines * tbytes, nlines, (uint32_t)tbytes, ecdev(m.ec), lines.first_bad()));
-            note_work(ctx, m, 5.0 * (double)nlines, sqrt_products * (double)nlines);
-            if (m.ec->ts_s != 0) {                                                 // p = 1 mod 4: P-224, secp224k1
-                if constexpr (E::S == 9)
-                    return launch_light(ctx, "encode_root", k_ec_encode_root<E::S, E::KIND, true>, grid_for(nlines), arrays[c]->d, nlines,
-                                        ecdev(m.ec), lines.first_bad());
-                else
-                    return VMN_ERR_UNSUPPORTED;
-            }
-            return launch_light(ctx, "encode_root", k_ec_encode_root<E::S, E::KIND, false>, grid_for(nlines), arrays[c]->d, nlines, ecdev(m.ec),
-                                lines.first_bad());
-        });
-    }
-    uint32_t failed = 0xffffffffu;
-    if (rc == VMN_OK && nlines) rc = lines.read_first_bad(ctx, &failed);
-    if (rc == VMN_OK && failed != 0xffffffffu) {
-        set_error("%s: line %u: no counter gives a point on the curve", __func__, failed);
-        rc = VMN_ERR_FORMAT;
-    }
-    if (rc != VMN_OK) {
-        for (vmn_garray* a : arrays) vmn_garray_free(a);
-        return rc;
-    }
-    for (size_t c = 0; c < ncomp; ++c) out[c] = arrays[c];
-    *n_out = nlines;
-    *fits = 1;
-    return VMN_OK;
+    // the records T (L + 4 bytes each); per component the counter search into the rows (x, x^3 + a x + b), then the smaller
+    // root in place.  The word that named the first long line (no line here) now receives the first line whose search or root failed.
+    return textlines_read(fn, grp, ncomp, text, len, tbytes, L, out, n_out, fits, first_long_line,
+                          [&](TextLines& lines, const uint8_t* rec, size_t nlines, const OutArrays& arrays) -> int {
+        for (size_t c = 0; c < ncomp; ++c) {
+            uint32_t* rows = arrays.a[c]->d;
+            VMN_TRY(with_curve(m, [&]<class E>(E) -> int {
+                note_work(ctx, m, (1.0 + 2.0 * 4.0) * (double)nlines);                // two counters expected, four products each
+                VMN_TRY(launch_light(ctx, "encode_search", k_ec_encode_search<E::S, E::NW, E::KIND>, grid_for(nlines), rows,
+                                     rec + c * nlines * tbytes, nlines, (uint32_t)tbytes, ecdev(m.ec), lines.first_bad()));
+                note_work(ctx, m, 5.0 * (double)nlines, sqrt_products * (double)nlines);
+                if (m.ec->ts_s != 0) {                                                 // p = 1 mod 4: P-224, secp224k1
+                    if constexpr (E::S == 9)
+                        return launch_light(ctx, "encode_root", k_ec_encode_root<E::S, E::KIND, true>, grid_for(nlines), rows, nlines,
+                                            ecdev(m.ec), lines.first_bad());
+                    else
+                        return VMN_ERR_UNSUPPORTED;
+                }
+                return launch_light(ctx, "encode_root", k_ec_encode_root<E::S, E::KIND, false>, grid_for(nlines), rows, nlines, ecdev(m.ec),
+                                    lines.first_bad());
+            }));
+        }
+        bool failed = false;
+        size_t line = 0;
+        VMN_TRY(lines.refused(ctx, &failed, &line));
+        if (failed) {                               // (no first_long_line, fits = 0: a format error with the line in its text)
+            set_error("%s: line %u: no counter gives a point on the curve", fn, (unsigned)line);
+            return VMN_ERR_FORMAT;
+        }
+        return VMN_OK;
+    });
 }
 
 extern "C" int vmn_ec_arrays_to_textlines(const vmn_garray* const* comps, size_t ncomp, char* out, size_t cap, size_t* written,
                                           int* all_wellformed, int* all_utf8) {
     ARG_CHECK(comps && written && textlines_ncomp_ok(ncomp), "null argument or ncomp out of range");
-    ARG_CHECK(jsonlines_comps_ok(comps, ncomp), "ncomp arrays of one group and one size are needed");
+    ARG_CHECK(same_group_and_size(comps, ncomp), "ncomp arrays of one group and one size are needed");
     vmn_group* grp = comps[0]->grp;
-    const size_t n = comps[0]->n, nbytes = grp->nbytes;
+    const size_t nbytes = grp->nbytes;
     vmn_ctx* ctx = LANE(grp->ctx);
     VMN_ENTER(ctx);
-    *written = 0;
-    if (all_wellformed) *all_wellformed = 1;
-    if (all_utf8) *all_utf8 = 1;
+    textlines_verdicts_clear(written, all_wellformed, all_utf8);
     const size_t L = vmn_ec_group_encode_length(grp), tbytes = L + encode::LENGTH_BYTES;
-    EC_ENCODE_GROUP_CHECK(grp, L);
-    if (n == 0) return VMN_OK;
-    ARG_CHECK(n < 0xffffffffull, "2^32 lines or more");
-    const size_t total = n * ncomp;
-    ARG_CHECK(total / ncomp == n && total < ((size_t)1 << 40), "too many elements");
-    const size_t groups = (n + BLOCK - 1) / BLOCK;
-    DevTmp rec(ctx), trec(ctx), plen(ctx), lens(ctx), bsum(ctx), dtext(ctx);
-    VMN_TRY(rec.alloc(total * 2 * nbytes + 16));
-    VMN_TRY(trec.alloc(total * tbytes + 16));
-    VMN_TRY(plen.alloc(total * sizeof(uint32_t)));
-    VMN_TRY(lens.alloc(n * sizeof(uint32_t)));
-    VMN_TRY(bsum.alloc((groups + 1) * sizeof(uint64_t)));
-    VMN_TRY(dev_zero(ctx, ctx->flags, sizeof(uint32_t)));
-    for (size_t c = 0; c < ncomp; ++c)
-        VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, rec.as<uint8_t>() + c * n * 2 * nbytes, 2 * nbytes, 0));
-    VMN_TRY(launch_light(ctx, "textlines", k_ec_textlines_fold, grid_for(total), trec.as<uint8_t>(), plen.as<uint32_t>(),
-                         (const uint8_t*)rec.as<uint8_t>(), total, (uint32_t)nbytes, (uint32_t)L, ctx->flags));
-    VMN_TRY(launch_light(ctx, "textlines", k_textlines_lengths, (unsigned)groups, lens.as<uint32_t>(), (u64*)bsum.p,
-                         (const uint8_t*)trec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n, (uint32_t)ncomp, (uint32_t)tbytes,
-                         (uint32_t)L, ctx->flags));
-    VMN_TRY(launch_light(ctx, "textlines", k_jsonlines_offsets, 1u, (u64*)bsum.p, groups, (u64*)bsum.p + groups));
-    uint64_t text_bytes = 0;
-    VMN_TRY(d2h(ctx, &text_bytes, (const u64*)bsum.p + groups, sizeof(text_bytes)));
-    ARG_CHECK(text_bytes <= cap && out, "the buffer is too small for these lines");
-    VMN_TRY(dtext.alloc(text_bytes + 16));
-    VMN_TRY(launch_light(ctx, "textlines", k_textlines_emit, (unsigned)groups, dtext.as<uint8_t>(), (const u64*)bsum.p,
-                         (const uint32_t*)lens.as<uint32_t>(), (const uint8_t*)trec.as<uint8_t>(), (const uint32_t*)plen.as<uint32_t>(), (uint32_t)n,
-                         (uint32_t)ncomp, (uint32_t)tbytes, (uint32_t)L));
-    uint32_t fl = 0;
-    VMN_TRY(read_flag(ctx, &fl));
-    VMN_TRY(d2h(ctx, out, dtext.p, text_bytes));
-    *written = (size_t)text_bytes;
-    if (all_wellformed) *all_wellformed = (fl & TEXTLINES_ILL_FORMED) ? 0 : 1;
-    if (all_utf8) *all_utf8 = (fl & TEXTLINES_NOT_UTF8) ? 0 : 1;
-    return VMN_OK;
+    UNSUPPORTED_IF(L == 0, "messages are encoded as points over a curve group that holds at least one byte");
+    return textlines_write(__func__, ctx, comps[0]->n, ncomp, tbytes, L, out, cap, written, all_wellformed, all_utf8,
+                           [&](DevTmp& xy, DevTmp& trec, const uint8_t** folded, size_t total) -> int {
+        VMN_TRY(xy.alloc(total * 2 * nbytes + 16));
+        VMN_TRY(trec.alloc(total * tbytes + 16));
+        *folded = trec.as<uint8_t>();
+        return VMN_OK;
+    }, [&](DevTmp& xy, DevTmp& trec, uint32_t* plen, size_t n, size_t total) {
+        for (size_t c = 0; c < ncomp; ++c)
+            VMN_TRY(export_rows_launch(ctx, grp->P, nbytes, comps[c]->d, n, xy.as<uint8_t>() + c * n * 2 * nbytes, 2 * nbytes, 0));
+        return launch_light(ctx, "textlines", k_ec_textlines_fold, grid_for(total), trec.as<uint8_t>(), plen, (const uint8_t*)xy.as<uint8_t>(),
+                            total, (uint32_t)nbytes, (uint32_t)L, ctx->flags);
+    });
 }
 
 extern "C" int vmn_garray_to_be(const vmn_garray* a, uint8_t* be_out) {

@@ -69,19 +69,20 @@ def _members_or_none(comps):
     return comps
 
 
-def parse_native(grp, text, width: int, expected_n: int = 0, report: Optional[dict] = None,
-                 keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
-    """The 2w component arrays ``u_1..u_w, v_1..v_w`` of a native list held in memory (``bytes``, or a host buffer object as
-    ``host_block`` takes them); ``None`` when a line is malformed, a value is out of range or an element is no member of the
-    group -- the raw reader's policy.  ``report`` (a dict) receives ``format_ok``, ``first_bad_line`` (zero-based; only
-    meaningful when ``format_ok`` is false), ``all_in_range`` and ``lines``.  Under a key of width ``keywidth`` = kappa the
-    2 kappa w arrays in flat order, component l kappa + j the key j of plaintext component l."""
+def _write_file(path: str, data) -> None:
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def _parse_list(call, shape, grp, text, expected_n: int, report: Optional[dict], ncomp: int) -> Optional[List[PGroupElementArray]]:
+    """A ciphertext list through ``call(grp, *shape, text, len, expected_n, arrays, lines, format_ok, first_bad_line,
+    all_in_range)``: its ``ncomp`` arrays, or ``None`` on a format defect, a value out of range or a non-member."""
     blk = host_block(text) or host_block(bytes(text))
-    hs = (C.c_void_p * (2 * keywidth * width))()
+    hs = (C.c_void_p * ncomp)()
     n, bad = C.c_size_t(0), C.c_size_t(0)
     fmt, rng = C.c_int(0), C.c_int(1)
-    _check(lib().vmn_garrays_from_hexlines_keyed(grp._h, C.c_size_t(keywidth), C.c_size_t(width), blk[0], C.c_size_t(blk[1]),
-                                                 C.c_size_t(expected_n), hs, C.byref(n), C.byref(fmt), C.byref(bad), C.byref(rng)))
+    _check(call(grp._h, *[C.c_size_t(s) for s in shape], blk[0], C.c_size_t(blk[1]), C.c_size_t(expected_n), hs, C.byref(n),
+                C.byref(fmt), C.byref(bad), C.byref(rng)))
     if report is not None:
         report.update(format_ok=bool(fmt.value), first_bad_line=bad.value, all_in_range=bool(rng.value), lines=n.value)
     if not fmt.value:
@@ -91,6 +92,16 @@ def parse_native(grp, text, width: int, expected_n: int = 0, report: Optional[di
         _free(comps)
         return None
     return _members_or_none(comps)
+
+
+def parse_native(grp, text, width: int, expected_n: int = 0, report: Optional[dict] = None,
+                 keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
+    """The 2w component arrays ``u_1..u_w, v_1..v_w`` of a native list held in memory (``bytes``, or a host buffer object as
+    ``host_block`` takes them); ``None`` when a line is malformed, a value is out of range or an element is no member of the
+    group -- the raw reader's policy.  ``report`` (a dict) receives ``format_ok``, ``first_bad_line`` (zero-based; only
+    meaningful when ``format_ok`` is false), ``all_in_range`` and ``lines``.  Under a key of width ``keywidth`` = kappa the
+    2 kappa w arrays in flat order, component l kappa + j the key j of plaintext component l."""
+    return _parse_list(lib().vmn_garrays_from_hexlines_keyed, (keywidth, width), grp, text, expected_n, report, 2 * keywidth * width)
 
 
 def format_native(comps: Sequence[PGroupElementArray], keywidth: int = 1) -> bytes:
@@ -114,21 +125,7 @@ def json_max_line_bytes(grp, width: int) -> int:
 def parse_json(grp, text, width: int, expected_n: int = 0, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
     """``parse_native`` for a json list: the 2w component arrays, or ``None`` under the same policy, with the same ``report``
     keys.  A curve group raises (the json interface covers modular groups only, as the reference's)."""
-    blk = host_block(text) or host_block(bytes(text))
-    hs = (C.c_void_p * (2 * width))()
-    n, bad = C.c_size_t(0), C.c_size_t(0)
-    fmt, rng = C.c_int(0), C.c_int(1)
-    _check(lib().vmn_garrays_from_jsonlines(grp._h, C.c_size_t(width), blk[0], C.c_size_t(blk[1]), C.c_size_t(expected_n), hs,
-                                            C.byref(n), C.byref(fmt), C.byref(bad), C.byref(rng)))
-    if report is not None:
-        report.update(format_ok=bool(fmt.value), first_bad_line=bad.value, all_in_range=bool(rng.value), lines=n.value)
-    if not fmt.value:
-        return None
-    comps = [PGroupElementArray(grp, C.c_void_p(h)) for h in hs]
-    if not rng.value:
-        _free(comps)
-        return None
-    return _members_or_none(comps)
+    return _parse_list(lib().vmn_garrays_from_jsonlines, (width,), grp, text, expected_n, report, 2 * width)
 
 
 def _json_lines(comps: Sequence[PGroupElementArray], width: int, plain: bool) -> bytes:
@@ -176,9 +173,7 @@ def write_ciphertexts(path: str, comps: Sequence[PGroupElementArray], fmt: str =
     if fmt == "raw":
         proofdir.write_ciphertexts(path, comps, keywidth)
         return
-    text = format_native(comps, keywidth)
-    with open(path, "wb") as f:
-        f.write(text)
+    _write_file(path, format_native(comps, keywidth))
 
 
 def read_plaintexts(grp, path: str, width: int, keywidth: int = 1) -> Optional[List[PGroupElementArray]]:
@@ -204,8 +199,7 @@ def write_plaintexts(path: str, comps: Sequence[PGroupElementArray], fmt: str = 
         data = format_json_plaintexts(comps)
     else:
         data = proofdir._wide_array_tree(comps, keywidth)
-    with open(path, "wb") as f:
-        f.write(data)
+    _write_file(path, data)
 
 
 def convert_ciphertexts(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None,
@@ -246,9 +240,7 @@ def write_list(path: str, comps: Sequence[PGroupElementArray], fmt: str, keywidt
     if fmt != "json":
         write_ciphertexts(path, comps, fmt, keywidth)
         return
-    text = format_json(comps)
-    with open(path, "wb") as f:
-        f.write(text)
+    _write_file(path, format_json(comps))
 
 
 def convert_list(grp, src: str, dst: str, width: int, in_fmt: str, out_fmt: str, report: Optional[dict] = None,
@@ -319,11 +311,14 @@ def encode_texts(grp, text, ncomp: int = 1, report: Optional[dict] = None) -> Op
     ``encode_length`` bytes over the components of element i; ``None`` when a line has more than ncomp * L bytes.  Lines end
     with \\n, \\r or \\r\\n; an empty line is the empty message.  ``report`` receives ``fits``, ``first_long_line``
     (zero-based; only meaningful when ``fits`` is false) and ``lines``."""
+    return _encode_lines(lib().vmn_garrays_from_textlines, grp, text, ncomp, report)
+
+
+def _encode_lines(call, grp, text, ncomp: int, report: Optional[dict]) -> Optional[List[PGroupElementArray]]:
     blk = host_block(text) or host_block(bytes(text))
     hs = (C.c_void_p * ncomp)()
     n, long_line, fits = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
-    _check(lib().vmn_garrays_from_textlines(grp._h, C.c_size_t(ncomp), blk[0], C.c_size_t(blk[1]), hs, C.byref(n), C.byref(fits),
-                                            C.byref(long_line)))
+    _check(call(grp._h, C.c_size_t(ncomp), blk[0], C.c_size_t(blk[1]), hs, C.byref(n), C.byref(fits), C.byref(long_line)))
     if report is not None:
         report.update(fits=bool(fits.value), first_long_line=long_line.value, lines=n.value)
     if not fits.value:
@@ -331,28 +326,31 @@ def encode_texts(grp, text, ncomp: int = 1, report: Optional[dict] = None) -> Op
     return [PGroupElementArray(grp, C.c_void_p(h)) for h in hs]
 
 
-def decode_texts(comps: Sequence[PGroupElementArray], report: Optional[dict] = None) -> bytes:
-    """decodePlaintexts: one line per element -- the messages of its components one after the other, \\n and \\r removed, then
-    \\n.  ``report`` receives ``all_wellformed`` (no element without a message: such a one gives an empty piece) and
-    ``all_utf8`` (every line well-formed UTF-8 before the removal; a line that is not is written byte for byte)."""
+def _decode_lines(call, length, comps: Sequence[PGroupElementArray], report: Optional[dict]) -> bytes:
+    """``length(grp)``: the bytes of a message one element holds, for the size of the buffer."""
     if not comps:
         raise ValueError("no arrays")
     grp, n = comps[0].group, comps[0].size()
     hs = (C.c_void_p * len(comps))(*[a._h for a in comps])
-    cap = max(1, n * (len(comps) * encode_length(grp) + 1))
+    cap = max(1, n * (len(comps) * length(grp) + 1))
     out = C.create_string_buffer(cap)
     written, wf, utf8 = C.c_size_t(0), C.c_int(1), C.c_int(1)
-    _check(lib().vmn_garrays_to_textlines(hs, C.c_size_t(len(comps)), out, C.c_size_t(cap), C.byref(written), C.byref(wf), C.byref(utf8)))
+    _check(call(hs, C.c_size_t(len(comps)), out, C.c_size_t(cap), C.byref(written), C.byref(wf), C.byref(utf8)))
     if report is not None:
         report.update(all_wellformed=bool(wf.value), all_utf8=bool(utf8.value))
     return out.raw[:written.value]
 
 
+def decode_texts(comps: Sequence[PGroupElementArray], report: Optional[dict] = None) -> bytes:
+    """decodePlaintexts: one line per element -- the messages of its components one after the other, \\n and \\r removed, then
+    \\n.  ``report`` receives ``all_wellformed`` (no element without a message: such a one gives an empty piece) and
+    ``all_utf8`` (every line well-formed UTF-8 before the removal; a line that is not is written byte for byte)."""
+    return _decode_lines(lib().vmn_garrays_to_textlines, encode_length, comps, report)
+
+
 def write_decoded_plaintexts(path: str, comps: Sequence[PGroupElementArray]) -> None:
     """``vmnc -plain -outi native``: the list of plaintexts given as its component arrays, as lines of text."""
-    data = decode_texts(comps)
-    with open(path, "wb") as f:
-        f.write(data)
+    _write_file(path, decode_texts(comps))
 
 
 def read_texts(grp, path: str, ncomp: int, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
@@ -374,7 +372,11 @@ def demo_texts(n: int, ncomp_L: int) -> bytes:
 def demo_ciphertexts(grp, y, n: int, rand, width: int = 1) -> List[PGroupElementArray]:
     """demoCiphertexts (:374-428): the ``n`` dummy messages encrypted under the key (g, ``y``): u = g^r, v = y^r encode(text), the
     exponents from ``rand`` (``ring_array(n)``, once per component).  Returns the 2 * width arrays u_1..u_w, v_1..v_w."""
-    msgs = encode_texts(grp, demo_texts(n, width * encode_length(grp)), width)
+    return _demo_ciphertexts(encode_texts, encode_length, grp, y, n, rand, width)
+
+
+def _demo_ciphertexts(encode, length, grp, y, n: int, rand, width: int) -> List[PGroupElementArray]:
+    msgs = encode(grp, demo_texts(n, width * length(grp)), width)
     if msgs is None:
         raise ValueError("the group holds no message")
     us, vs = [], []
@@ -399,39 +401,18 @@ def encode_point_texts(grp, text, ncomp: int = 1, report: Optional[dict] = None)
     """``encode_texts`` over a curve group: line i is cut into pieces of ``point_encode_length`` bytes, each the x coordinate of a
     point under the least counter that puts it on the curve (``vmn_ec_arrays_from_textlines``).  ``None`` when a line has more
     than ncomp * L bytes; ``report`` receives ``fits``, ``first_long_line`` and ``lines``."""
-    blk = host_block(text) or host_block(bytes(text))
-    hs = (C.c_void_p * ncomp)()
-    n, long_line, fits = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
-    _check(lib().vmn_ec_arrays_from_textlines(grp._h, C.c_size_t(ncomp), blk[0], C.c_size_t(blk[1]), hs, C.byref(n), C.byref(fits),
-                                              C.byref(long_line)))
-    if report is not None:
-        report.update(fits=bool(fits.value), first_long_line=long_line.value, lines=n.value)
-    if not fits.value:
-        return None
-    return [PGroupElementArray(grp, C.c_void_p(h)) for h in hs]
+    return _encode_lines(lib().vmn_ec_arrays_from_textlines, grp, text, ncomp, report)
 
 
 def decode_point_texts(comps: Sequence[PGroupElementArray], report: Optional[dict] = None) -> bytes:
     """``decode_texts`` over a curve group (``vmn_ec_arrays_to_textlines``): the message of a point is read from its x coordinate;
     ``report`` receives ``all_wellformed`` and ``all_utf8``."""
-    if not comps:
-        raise ValueError("no arrays")
-    grp, n = comps[0].group, comps[0].size()
-    hs = (C.c_void_p * len(comps))(*[a._h for a in comps])
-    cap = max(1, n * (len(comps) * point_encode_length(grp) + 1))
-    out = C.create_string_buffer(cap)
-    written, wf, utf8 = C.c_size_t(0), C.c_int(1), C.c_int(1)
-    _check(lib().vmn_ec_arrays_to_textlines(hs, C.c_size_t(len(comps)), out, C.c_size_t(cap), C.byref(written), C.byref(wf), C.byref(utf8)))
-    if report is not None:
-        report.update(all_wellformed=bool(wf.value), all_utf8=bool(utf8.value))
-    return out.raw[:written.value]
+    return _decode_lines(lib().vmn_ec_arrays_to_textlines, point_encode_length, comps, report)
 
 
 def write_decoded_point_plaintexts(path: str, comps: Sequence[PGroupElementArray]) -> None:
     """``vmnc -plain -outi native`` of a curve session: the list of plaintexts given as its component arrays, as lines of text."""
-    data = decode_point_texts(comps)
-    with open(path, "wb") as f:
-        f.write(data)
+    _write_file(path, decode_point_texts(comps))
 
 
 def read_point_texts(grp, path: str, ncomp: int, report: Optional[dict] = None) -> Optional[List[PGroupElementArray]]:
@@ -445,15 +426,4 @@ def read_point_texts(grp, path: str, ncomp: int, report: Optional[dict] = None) 
 def demo_point_ciphertexts(grp, y, n: int, rand, width: int = 1) -> List[PGroupElementArray]:
     """``demo_ciphertexts`` over a curve group: the ``n`` dummy messages of ``demo_texts`` as points, encrypted under (g, ``y``).
     Returns the 2 * width arrays u_1..u_w, v_1..v_w."""
-    msgs = encode_point_texts(grp, demo_texts(n, width * point_encode_length(grp)), width)
-    if msgs is None:
-        raise ValueError("the group holds no message")
-    us, vs = [], []
-    for m in msgs:
-        r = grp.ringArray(rand.ring_array(n))
-        t = grp.exp(y, r)
-        us.append(grp.exp(grp.g, r))
-        vs.append(t.mul(m))
-        for a in (r, t, m):
-            a.free()
-    return us + vs
+    return _demo_ciphertexts(encode_point_texts, point_encode_length, grp, y, n, rand, width)
